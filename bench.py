@@ -9,6 +9,10 @@ reference train.py:169-252).  Per-GPU work is fixed as N grows ("weak" scaling).
 
 metric  = splats*px rasterized per second (fwd+bwd) = n_gpus * N_splats * H * W / t_step
 workload = BASELINE.json's metric configuration: 1 M synthetic splats, 800x800, SH degree 3.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else after the timed
+steps (per-step event times, per-stage times and roofline blocks, exchange diagnostics, side workloads, CPU baselines, parity).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -42,7 +46,8 @@ def parse():
     p.add_argument("--height", type=int, default=800)
     p.add_argument("--color", choices=["sh", "precomp"], default="sh")
     p.add_argument("--sh-degree", type=int, default=3)
-    p.add_argument("--cpu-baseline", choices=["auto", "none"], default="auto")
+    p.add_argument("--cpu-baseline", choices=["auto", "none"], default="auto",
+                   help="with --full, rank 0, 1 GPU: the CPU baselines and the parity block")
     p.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the bounded baseline sample")
     p.add_argument("--dp-mode", choices=["shard", "gather", "allreduce"], default="gather",
                    help="N>1, SH path.  'gather' (default) = all-gather of 12 B/splat colour gradients, the SH gradient is rebuilt "
@@ -55,7 +60,7 @@ def parse():
     p.add_argument("--mean-scale", type=float, default=None, help="mean splat scale in world units (default: SURVEY.md 8d rule, "
                                                                    "0.35 N^(-1/3)); larger = denser tile lists")
     p.add_argument("--extra-workloads", choices=["auto", "none"], default="auto",
-                   help="rank 0, 1 GPU: also time the precomputed-colour headline and two dense regimes (a few steps each) and "
+                   help="with --full, rank 0, 1 GPU: also time the precomputed-colour headline and two dense regimes (a few steps each) and "
                         "report them under other_workloads")
     p.add_argument("--inputs", choices=["boundary", "raw-split"], default="boundary",
                    help="'boundary' (default, the reference's call): activated tensors and the concatenated SH tensor; 'raw-split': "
@@ -64,7 +69,19 @@ def parse():
     p.add_argument("--force-dp-path", action="store_true", help="run the chosen --dp-mode step function even with 1 GPU (overhead check)")
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for smoke-testing the control flow)")
     p.add_argument("--single-device", action="store_true", help="smoke test: every rank uses cuda:0 (needs --backend gloo)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure, after the timed steps: per-step event times, the sync-forward pass, "
+                        "per-stage times and the roofline blocks, the N > 1 exchange diagnostics and, on 1 GPU, blend_work, "
+                        "other_workloads, deform_network, the CPU baselines and parity (--extra-workloads / --cpu-baseline select "
+                        "among the last ones).  Without it the run sets up, warms up, times the K steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (images, radii, every gradient) as "
+                        "DIR/<name>.npy (float32 / float64, at most 64 MB: per-splat arrays beyond their share as a fixed seeded "
+                        "sample of rows, listed in splat_index.npy); rank 0 only")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def stage_bytes(stage: str, n: int, vis: float, R: float, hw: int, c_in: int) -> float:
@@ -338,6 +355,54 @@ def blend_work_counters(n, width, height, mean_scale):
                     "(its counters cost registers) where the product runs four: the phase shares are its own"}
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs: all files together
+DUMP_SPLAT_BYTES = 40_000_000  # of which the per-splat arrays (radii, gradients)
+DUMP_IMAGE_BYTES = 23_000_000  # and the images (the rest: .npy headers)
+
+
+def _sample_index(n: int, k: int, seed: int) -> torch.Tensor:
+    """A fixed, sorted sample of k of n indices (CPU generator: the same on every run and build)."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def dump_outputs(path: str, images: dict, per_splat: dict) -> dict:
+    """--dump-outputs: `images` ([C, H, W] tensors) and `per_splat` ([N, ...] tensors) as `path`/<name>.npy, floating-point data in
+    float32 (float64 stays float64), integer data in float64 (exact).  Whatever exceeds its share (DUMP_SPLAT_BYTES /
+    DUMP_IMAGE_BYTES) is written as a fixed seeded sample: rows of the per-splat arrays (splat_index.npy), pixels of the images
+    ([C, P]; pixel_index.npy holds the flat y * W + x).  Returns {name: shape} of the files written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def host(t):
+        t = t.detach().cpu()
+        return t.double() if (not t.is_floating_point() or t.dtype == torch.float64) else t.float()
+
+    files = {}
+    per_splat = {k: host(v) for k, v in per_splat.items() if v is not None}
+    if per_splat:
+        n = next(iter(per_splat.values())).shape[0]
+        row_bytes = 8 + sum(v[0].numel() * v.element_size() for v in per_splat.values())
+        keep = min(n, DUMP_SPLAT_BYTES // row_bytes)
+        if keep < n:
+            idx = _sample_index(n, keep, 0)
+            per_splat = {k: v[idx] for k, v in per_splat.items()}
+            files["splat_index"] = idx.double()
+        files.update(per_splat)
+    images = {k: host(v) for k, v in images.items() if v is not None}
+    if images:
+        px = next(iter(images.values()))[0].numel()
+        pixel_bytes = 8 + sum(v.shape[0] * v.element_size() for v in images.values())
+        keep = min(px, DUMP_IMAGE_BYTES // pixel_bytes)
+        if keep < px:
+            idx = _sample_index(px, keep, 1)
+            images = {k: v.reshape(v.shape[0], -1)[:, idx] for k, v in images.items()}
+            files["pixel_index"] = idx.double()
+        files.update(images)
+    for k, v in files.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v.numpy()))
+    return {k: list(v.shape) for k, v in files.items()}
+
+
 def median(xs):
     xs = sorted(xs)
     n = len(xs)
@@ -593,6 +658,7 @@ def main():
     dp_active = (world > 1 or args.force_dp_path) and use_sh
     modes = {"shard": ["shard", "gather", "allreduce"], "gather": ["gather", "allreduce"], "allreduce": ["allreduce"]}[args.dp_mode]
     state = {"mode": modes[0] if dp_active else "allreduce"}
+    last = {"capture": False}   # --dump-outputs: the outputs of the last timed step (only that step sets `capture`)
 
     def one_step_gather(step_idx: int, record: bool):
         step_cams = [cams[(step_idx * world + r) % len(cams)] for r in range(world)]
@@ -601,6 +667,8 @@ def main():
         def bwd(vi, color, depth, alpha):
             seen["radii_vis"] = None
             torch.autograd.backward((color, depth, alpha), (gi / world, gd / world, ga / world))
+            if last["capture"]:
+                last.update(color=color, depth=depth, alpha=alpha)
 
         if state["mode"] == "shard":
             sh_sharded_step(params, step_cams, bg, args.sh_degree, bwd, rank=rank, world=world)
@@ -637,6 +705,8 @@ def main():
         # gradients are the fixed G tensors: feed them directly instead of spending ~15 small PyTorch kernels
         # (mul/sum/add and their backward) on a stand-in loss that is not part of the rasterizer.
         torch.autograd.backward((color, depth, alpha), (gi, gd, ga))
+        if last["capture"]:
+            last.update(color=color, radii=radii, depth=depth, alpha=alpha)
         if world > 1:
             allreduce_gradients(list(params.values()), world)
         if record:
@@ -650,7 +720,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if dp_active:   # visible splats of one view, for the byte model (the exchange steps do not hand the radii out)
+    if dp_active and args.full:   # visible splats of one view, for the byte model (the exchange steps do not hand the radii out)
         cam0 = cams[0]
         rs0 = GaussianRasterizationSettings(
             image_height=H, image_width=W, tanfovx=math.tan(cam0.FoVx * 0.5), tanfovy=math.tan(cam0.FoVy * 0.5), bg=bg,
@@ -708,51 +778,93 @@ def main():
     ExchangeStats.reset(False)
     rz.host_sync_counters(reset=True)
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         one_step(args.warmup + i)
+    last["capture"] = args.dump_outputs is not None   # the last step keeps its outputs for --dump-outputs
+    one_step(args.warmup + args.steps - 1)
     fence()
     t = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+    last["capture"] = False
     gc.enable()
     gc.collect()   # (now, not as a surprise in the middle of the next pass)
     host_sync = rz.host_sync_counters()
-    # second pass over the same K steps, each bracketed by HIP events on the launch stream (median / min / max of a step) and,
-    # for N > 1, with the exchange instrumentation on
-    for _ in range(3):   # the collector's pause above left the device idle: three untimed cycles before the events pass
+    if args.dump_outputs is not None and rank == 0:
+        # what a caller of the timed step received in the last step: the three images, the radii and every gradient
+        per_splat = {"radii": last.get("radii"), "grad_means2D": means2D.grad}
+        per_splat.update({"grad_" + k: p.grad for k, p in params.items()})
+        shapes = dump_outputs(args.dump_outputs, {k: last.get(k) for k in ("color", "depth", "alpha")}, per_splat)
+        print(f"[bench] outputs of the last timed step -> {args.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
+    last.clear()
+    last["capture"] = False
+    if args.full:
+        # second pass over the same K steps, each bracketed by HIP events on the launch stream (median / min / max of a step) and,
+        # for N > 1, with the exchange instrumentation on
+        for _ in range(3):   # the collector's pause above left the device idle: three untimed cycles before the events pass
+            for i in range(len(cams)):
+                one_step(i)
+        ExchangeStats.reset(world > 1 or args.force_dp_path)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        stream = torch.cuda.current_stream(dev)
+        for i in range(args.steps):
+            marks[i].record(stream)
+            one_step(args.warmup + i)
+            ExchangeStats.end_step()
+        marks[args.steps].record(stream)
+        fence()
+        step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+        med = torch.tensor([median(step_ms)], device=dev, dtype=torch.float64)
+        # The same K steps with EVERY forward waiting for its instance count on the host (the plain facade's default, and what [EXT]
+        # does): the headline above assumes that every capacity / list-length promise holds (static splats, cameras rendered
+        # before: a 100 % hit rate); a loop that meets new counts or first visits pays this figure for those steps.
+        prev_async = rz.set_async_forward(False)
         for i in range(len(cams)):
             one_step(i)
-    ExchangeStats.reset(world > 1 or args.force_dp_path)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    stream = torch.cuda.current_stream(dev)
-    for i in range(args.steps):
-        marks[i].record(stream)
-        one_step(args.warmup + i)
-        ExchangeStats.end_step()
-    marks[args.steps].record(stream)
-    fence()
-    step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-    med = torch.tensor([median(step_ms)], device=dev, dtype=torch.float64)
-    # The same K steps with EVERY forward waiting for its instance count on the host (the plain facade's default, and what [EXT]
-    # does): the headline above assumes that every capacity / list-length promise holds (static splats, cameras rendered
-    # before: a 100 % hit rate); a loop that meets new counts or first visits pays this figure for those steps.
-    prev_async = rz.set_async_forward(False)
-    for i in range(len(cams)):
-        one_step(i)
-    fence()
-    t0s = time.perf_counter()
-    for i in range(args.steps):
-        one_step(args.warmup + i)
-    fence()
-    ms_sync_forward = (time.perf_counter() - t0s) / args.steps * 1e3
-    rz.set_async_forward(prev_async)
+        fence()
+        t0s = time.perf_counter()
+        for i in range(args.steps):
+            one_step(args.warmup + i)
+        fence()
+        ms_sync_forward = (time.perf_counter() - t0s) / args.steps * 1e3
+        rz.set_async_forward(prev_async)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dist.all_reduce(med, op=dist.ReduceOp.MAX)
+        if args.full:
+            dist.all_reduce(med, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     # `ms_per_step` = wall clock of the K timed steps / K -- the estimator `value` uses and the task contract names; the median
     # of the per-step HIP-event times rides beside it (ms_per_step_median: robust against one slow step)
     ms_per_step = elapsed / args.steps * 1e3
-    ms_median = float(med.item())
     value = world * N * H * W * args.steps / elapsed
+    workload = (f"{N} synthetic splats (seed 1234), {W}x{H}, {'SH degree %d' % args.sh_degree if use_sh else 'precomputed colours'}, "
+                f"1 view per GPU per step, colour+depth+alpha outputs, fwd+bwd"
+                + ({"shard": ", SH coefficients sharded by splat range: RCCL all-to-all of colours and colour gradients "
+                             "+ all-reduce of the other per-splat gradients",
+                    "gather": ", RCCL all-gather of colour gradients + all-reduce of the other per-splat gradients",
+                    "allreduce": ", RCCL sum all-reduce of per-splat gradients"}[state["mode"]] if world > 1 else ""))
+    host_sync = dict(host_sync, async_forward="opt-in inside the step (checked_forward: async_forward() + resolve_pending())",
+                     note="timed steps only; the cameras of the cycle were rendered before, so no forward waits MID-forward: each "
+                          "step's ticket is redeemed before its backward (tickets_waited_for counts the redemptions that found "
+                          "stage 1 still running)")
+    if not args.full:
+        # the plain run: the headline line and nothing else (--full adds the passes and blocks below)
+        if rank == 0:
+            print(json.dumps({
+                "metric": "splats*px rasterized/sec (fwd+bwd)", "value": value, "unit": "splat*px/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+                "timing": "value = work / wall-clock of the K timed steps (barrier + synchronize on both sides, max over ranks; nothing "
+                          "but the steps inside); ms_per_step = that wall-clock / K.  The timed step launches its forward without the "
+                          "mid-forward host wait (sr_forward_async) and redeems the ticket before the backward: value assumes a 100 % "
+                          "hit rate of the capacity / list-length promises (static splats, cameras rendered before).  The splat "
+                          "parameters are the same tensors in every step (NOTEBOOK.md section 9.10).  bench.py --full adds per-step "
+                          "event times, the sync-forward figure, per-stage times, roofline blocks and the side measurements",
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": {"workload": workload, "splats": N, "width": W, "height": H, "views_per_step": world, "inputs": args.inputs,
+                           "dp_mode": state["mode"] if (world > 1 or args.force_dp_path) else None},
+                "host_sync": host_sync}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    ms_median = float(med.item())
     exchange = ExchangeStats.summary() if ExchangeStats.enabled else None
     ExchangeStats.reset(False)
 
@@ -794,12 +906,7 @@ def main():
                   "update between two steps costs the forward preprocess ~3 us of this figure (NOTEBOOK.md section 9.10)",
         "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{N} synthetic splats (seed 1234), {W}x{H}, {'SH degree %d' % args.sh_degree if use_sh else 'precomputed colours'}, "
-                               f"1 view per GPU per step, colour+depth+alpha outputs, fwd+bwd"
-                               + ({"shard": ", SH coefficients sharded by splat range: RCCL all-to-all of colours and colour gradients "
-                                            "+ all-reduce of the other per-splat gradients",
-                                   "gather": ", RCCL all-gather of colour gradients + all-reduce of the other per-splat gradients",
-                                   "allreduce": ", RCCL sum all-reduce of per-splat gradients"}[state["mode"]] if world > 1 else ""),
+        "config": {"workload": workload,
                    "splats": N, "width": W, "height": H, "views_per_step": world,
                    "visible_splats": vis, "tile_instances": R, "inputs": args.inputs, "dp_mode": state["mode"] if (world > 1 or args.force_dp_path) else None},
         "roofline": roofline_block(stage_ms, N, vis, R, H * W, c_in, ms_per_step, ms_median, traffic, traffic_why),
@@ -810,10 +917,7 @@ def main():
         "stage_ms": stage_ms, "stage_ms_sum": sum(stage_ms.values()),
         # host synchronisations of the forward inside the timed region (sr_debug_counters): forwards that waited for their
         # instance count (sr_forward: first render of a camera) vs forwards launched without waiting (sr_forward_async)
-        "host_sync": dict(host_sync, async_forward="opt-in inside the step (checked_forward: async_forward() + resolve_pending())",
-                          note="timed steps only; the cameras of the cycle were rendered before, so no forward waits MID-forward: each "
-                               "step's ticket is redeemed before its backward (tickets_waited_for counts the redemptions that found "
-                               "stage 1 still running)"),
+        "host_sync": host_sync,
         # algorithmic bytes of every stage / its measured duration, as a fraction of the 8 TB/s HBM peak
         "stage_hbm_frac": {k: (stage_bytes(k, N, vis, R, H * W, c_in) / (v * 1e-3) / HBM_PEAK if v > 0 else None) for k, v in stage_ms.items()},
     }

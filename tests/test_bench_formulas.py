@@ -137,3 +137,39 @@ def test_rank_count_mismatch_is_a_hard_error():
         env = dict(os.environ, WORLD_SIZE=ws, RANK="0", LOCAL_RANK="0")
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", gpus], capture_output=True, text=True, timeout=120, env=env)
         assert r.returncode != 0 and f"--gpus {gpus} but WORLD_SIZE={ws}" in r.stderr, (gpus, ws, r.stderr[-500:])
+
+
+def test_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs at the headline size (1 M splats, SH degree 3, 800x800): images whole, per-splat arrays as a seeded sample
+    of rows named by splat_index.npy, everything float32 / float64 and at most 64 MB; the sample is the same on every call.
+    Images beyond their share are sampled by pixel (pixel_index.npy)."""
+    import numpy as np
+    import torch
+    n, h, w = 1_000_000, 800, 800
+    g = torch.Generator().manual_seed(5)
+    images = {"color": torch.rand(3, h, w, generator=g), "depth": torch.rand(1, h, w, generator=g), "alpha": torch.rand(1, h, w, generator=g)}
+    per_splat = {"radii": torch.randint(0, 50, (n,), generator=g, dtype=torch.int32), "grad_means2D": torch.randn(n, 3, generator=g),
+                 "grad_means3D": torch.randn(n, 3, generator=g), "grad_scales": torch.randn(n, 3, generator=g),
+                 "grad_rotations": torch.randn(n, 4, generator=g), "grad_opacities": torch.randn(n, 1, generator=g),
+                 "grad_shs": torch.randn(n, 16, 3, generator=g), "absent": None}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), images, per_splat)
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sorted(f.stem for f in files) == sorted(shapes) and "absent" not in shapes
+    assert sum(f.stat().st_size for f in files) <= 64_000_000
+    got = {f.stem: np.load(f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["radii"].dtype == np.float64 and got["grad_shs"].dtype == np.float32
+    assert got["color"].shape == (3, h, w) and np.array_equal(got["color"], images["color"].numpy())
+    idx = got["splat_index"].astype(np.int64)
+    k = len(idx)
+    assert 100_000 <= k < n and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert got["grad_shs"].shape == (k, 16, 3) and np.array_equal(got["grad_shs"], per_splat["grad_shs"].numpy()[idx])
+    assert np.array_equal(got["radii"], per_splat["radii"].numpy()[idx].astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "b"), images, per_splat)
+    assert np.array_equal(np.load(tmp_path / "b" / "splat_index.npy"), got["splat_index"])
+    # a large image: a pixel sample of the flattened channels
+    monkeypatch.setattr(bench, "DUMP_IMAGE_BYTES", 20 * 1000)
+    shapes = bench.dump_outputs(str(tmp_path / "c"), images, {})
+    px = np.load(tmp_path / "c" / "pixel_index.npy").astype(np.int64)
+    assert shapes["color"] == [3, len(px)] and len(px) == 20 * 1000 // (8 + 5 * 4)
+    assert np.array_equal(np.load(tmp_path / "c" / "depth.npy"), images["depth"].numpy().reshape(1, -1)[:, px])

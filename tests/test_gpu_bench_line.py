@@ -1,19 +1,23 @@
 """The JSON line of bench.py, as the driver will see it: schema of the 1-GPU line (median timing, roofline blocks) and of the
-N > 1 line (exchange diagnostics), the latter through two gloo ranks sharing the one GPU of the test box
-(`--backend gloo --single-device`): the control flow, the step functions and the instrumentation are the ones a RCCL run uses."""
+N > 1 line (exchange diagnostics) of `--full` runs, the latter through two gloo ranks sharing the one GPU of the test box
+(`--backend gloo --single-device`): the control flow, the step functions and the instrumentation are the ones a RCCL run uses.
+A plain run prints the headline fields only, and `--dump-outputs` writes the last timed step's outputs, the same on every run."""
+import glob
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 SMALL = ["--splats", "20000", "--width", "256", "--height", "192", "--steps", "4", "--warmup", "2", "--cpu-baseline", "none",
-         "--extra-workloads", "none"]
+         "--extra-workloads", "none", "--full"]
+PLAIN = ["--splats", "20000", "--width", "256", "--height", "192", "--steps", "4", "--warmup", "2"]
 
 
 def _last_json(text):
@@ -43,6 +47,37 @@ def test_single_gpu_line_has_median_timing_and_roofline_blocks(hip_device):
     assert abs(rf["pipeline_frac"] - d["roofline_pipeline"]["frac"]) < 1e-12 and rf["pipeline_frac_vs_6.29"] > rf["pipeline_frac"]
     assert set(rf["stage_bound"]) == set(d["stage_ms"])
     assert "exchange" not in d
+
+
+def _plain_run(dump_dir):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(dump_dir)] + PLAIN,
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return _last_json(r.stdout), {os.path.basename(p)[:-4]: np.load(p) for p in glob.glob(os.path.join(str(dump_dir), "*.npy"))}
+
+
+def test_plain_line_is_the_headline_and_the_dump_is_reproducible(hip_device, tmp_path):
+    """Without --full: the headline fields, K timed steps, nothing measured beyond them.  --dump-outputs: the images, radii and
+    every gradient of the last timed step, float32 / float64, within 64 MB, bit-identical between two runs (fixed inputs,
+    deterministic kernels)."""
+    d, a = _plain_run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["metric"] == "splats*px rasterized/sec (fwd+bwd)" and d["unit"] == "splat*px/s"
+    assert abs(d["value"] - 20000 * 256 * 192 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("ms_per_step_median", "stage_ms", "roofline", "roofline_valu", "other_workloads", "cpu_baseline", "parity"):
+        assert k not in d, k
+    want = {"color": (3, 192, 256), "depth": (1, 192, 256), "alpha": (1, 192, 256), "radii": (20000,), "grad_means2D": (20000, 3),
+            "grad_means3D": (20000, 3), "grad_scales": (20000, 3), "grad_rotations": (20000, 4), "grad_opacities": (20000, 1),
+            "grad_shs": (20000, 16, 3)}
+    assert {k: v.shape for k, v in a.items()} == want
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(os.path.getsize(p) for p in glob.glob(os.path.join(str(tmp_path / "a"), "*.npy"))) <= 64_000_000
+    assert (a["radii"] > 0).any() and np.abs(a["grad_shs"]).max() > 0 and np.isfinite(a["color"]).all()
+    _, b = _plain_run(tmp_path / "b")
+    for k in want:
+        assert np.array_equal(a[k], b[k]), k
 
 
 def _free_port():

@@ -6,7 +6,7 @@
 R=$1; shift; ARGS=$1; shift
 for i in $(seq "$R"); do
   for L in "$@"; do
-    SPLATRASTER_LIB=$(realpath "$L") python bench.py --cpu-baseline none --steps 30 $ARGS | python -c "
+    SPLATRASTER_LIB=$(realpath "$L") python bench.py --full --cpu-baseline none --steps 30 $ARGS | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']
 print('%-28s'%'$L', '%.4f'%d['ms_per_step'], ' '.join('%s=%.4f'%(k[:14],v) for k,v in s.items()))"
