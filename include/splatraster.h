@@ -5,9 +5,10 @@
  *
  * Every entry point takes plain pointers and sizes; no torch / C++ types cross this boundary.
  * All device memory (inputs, outputs, gradients, the three opaque state buffers) is owned by
- * the caller (PyTorch-ROCm tensors, `tensor.data_ptr()`); the library owns nothing persistent (its only state: a pinned
- * read-back word + event per host thread and device, the mutex-guarded event list of the optional stage profiling, and
- * per-device "attribute set" flags of three kernels).
+ * the caller (PyTorch-ROCm tensors, `tensor.data_ptr()`); the library owns nothing persistent (its only state: 64-byte
+ * status blocks of pinned, coherent host memory -- one per host thread and device for sr_forward, a pool per device for the
+ * tickets of sr_forward_async --, the mutex-guarded event list of the optional stage profiling, and per-device "attribute
+ * set" flags of three kernels).
  * Every kernel is launched on the caller-supplied HIP stream.  Functions return 0 on success,
  * a non-zero status otherwise; `sr_last_error()` returns a thread-local message.
  *
@@ -133,17 +134,18 @@ int sr_forward_render(const SrView* view, const SrSplats* splats, void* geom, vo
                       long long instances, void* image, float* out_color, float* out_depth,
                       float* out_alpha, void* hip_stream);
 
-/* Both forward stages in one call WITHOUT draining the pipeline: stage 1 is launched, the instance count is
- * copied to pinned host memory asynchronously, stage 2 is launched right behind it for a binning buffer sized
- * for `binning_capacity` instances (every stage-2 kernel exits immediately if the count exceeds it), and only
- * then does the host wait -- for the early copy, while the GPU keeps running stage 2.  (So the host still blocks once per
- * forward, as upstream's num_rendered read-back does, but only until stage 1 has finished: the GPU never idles.)
+/* Both forward stages in one call WITHOUT draining the pipeline: stage 1 is launched -- its last kernel stores the instance
+ * count and the longest tile list into a status block (pinned, coherent host memory) and then publishes the block's sequence
+ * number; nothing is enqueued in the stream for the read-back, neither a copy nor an event --, stage 2 is launched right behind
+ * it for a binning buffer sized for `binning_capacity` instances (every stage-2 kernel exits immediately if the count exceeds
+ * it), and only then does the host wait: it polls the block while the GPU keeps running stage 2.  (So the host still blocks
+ * once per forward, as upstream's num_rendered read-back does, but only until stage 1 has finished: the GPU never idles.)
  * Returns 0 when the count fits (outputs valid), SR_NEED_CAPACITY when it does not: the caller then allocates
  * sr_binning_bytes(*instances_out) and calls sr_forward_render with instances = *instances_out.
  * The binning buffer is carved for the capacity it was rendered with; pass that same number as `instances`
  * to sr_backward.
- * Threading: the asynchronous read-back uses one pinned word + event per (host thread, device); host threads may call
- * concurrently, each on its own stream and buffers. */
+ * Threading: the read-back uses one status block per (host thread, device); host threads may call concurrently, each on its
+ * own stream and buffers. */
 #define SR_NEED_CAPACITY 2
 int sr_forward(const SrView* view, const SrSplats* splats, void* geom, int* radii, void* binning,
                long long binning_capacity, void* image, float* out_color, float* out_depth, float* out_alpha,
@@ -155,8 +157,8 @@ int sr_forward(const SrView* view, const SrSplats* splats, void* geom, int* radi
  * to 2048 / 4096 / 8192 entries, or all) -- typically what an earlier forward of the same view reported, with headroom.  Both
  * stages are launched back to back and the call returns; every stage-2 kernel exits on the device if the instance count
  * exceeds the capacity, and the blend exits if a list is longer than the launched sort classes cover, so a wrong guess never
- * reads or writes out of bounds -- it leaves the OUTPUTS UNDEFINED.  `*ticket_out` receives a ticket (a pinned status block +
- * an event recorded behind stage 1, pooled inside the library); the caller MUST redeem it with sr_ticket_wait before it uses
+ * reads or writes out of bounds -- it leaves the OUTPUTS UNDEFINED.  `*ticket_out` receives a ticket (a status block of its
+ * own, which stage 1 fills as it does sr_forward's; pooled inside the library); the caller MUST redeem it with sr_ticket_wait before it uses
  * the outputs' gradients (before sr_backward at the latest): it waits for stage 1 of that forward only -- usually long
  * finished -- and returns the instance count and the longest list; the outputs are valid iff
  *     instances <= binning_capacity  and  longest_list <= max(2048, the class bound the hint selected).
@@ -210,8 +212,8 @@ int sr_backward_splats(const SrView* view, const SrSplats* splats, const void* g
                        long long instances, long long instances_rendered, const void* image, const int* radii, void* scratch,
                        const SrGrads* grads, int first_splat, int n_splats, void* hip_stream);
 
-/* Pins the backward blend kernel for A/B measurements and for the test that compares the two: 0 = chosen per launch by the
- * footprint (default), 1 = pixel-per-lane kernel, 2 = entry-per-lane kernel.  The initial value comes from the environment
+/* Pins the backward blend kernel for A/B measurements and for the test that compares the two: 0 = the product choice (default;
+ * the entry-per-lane kernel at every footprint, see sr_backward), 1 = pixel-per-lane kernel, 2 = entry-per-lane kernel.  The initial value comes from the environment
  * variable SPLATRASTER_BWD ("wave" = 1, "quads" = 2), read once when the library is loaded.  Process-wide; returns the
  * previous setting, or -1 for an unknown value (nothing changes). */
 int sr_set_backward_kernel(int which);

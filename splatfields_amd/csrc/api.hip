@@ -66,8 +66,6 @@ struct StageTimer {
 // sr_forward keeps one block per (host thread, device); sr_forward_async hands one out per forward in flight (a "ticket",
 // pooled per device under a mutex).  A few bytes each, created lazily.
 struct StatusBlock { uint32_t* pinned = nullptr; uint32_t* pinned_dev = nullptr; uint32_t seq = 0; hipStream_t stream = nullptr; int dev = 0; };
-typedef StatusBlock HostSync;
-typedef StatusBlock Ticket;
 thread_local StatusBlock g_sync[64];
 std::mutex g_ticket_mutex;
 std::vector<StatusBlock*> g_ticket_free[64];
@@ -113,18 +111,22 @@ int status_block_wait(StatusBlock& b, bool* waited) {
     return 0;
 }
 
-int get_host_sync(HostSync** out) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail("hipGetDevice failed");
-    StatusBlock& h = g_sync[dev];
-    if (!h.pinned) SR_TRY(status_block_init(h, dev));
-    *out = &h;
+int current_device(int* dev) {
+    if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= 64) return fail("hipGetDevice failed");
     return 0;
 }
 
-int ticket_acquire(Ticket** out) {
+// the calling thread's block for the current device (sr_forward, sr_forward_prepare)
+int thread_block(StatusBlock** out) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail("hipGetDevice failed");
+    SR_TRY(current_device(&dev));
+    *out = &g_sync[dev];
+    return (*out)->pinned ? 0 : status_block_init(**out, dev);   // created at the thread's first forward on this device
+}
+
+int ticket_acquire(StatusBlock** out) {
+    int dev = 0;
+    SR_TRY(current_device(&dev));
     {
         std::lock_guard<std::mutex> lock(g_ticket_mutex);
         if (!g_ticket_free[dev].empty()) { *out = g_ticket_free[dev].back(); g_ticket_free[dev].pop_back(); return 0; }
@@ -135,15 +137,15 @@ int ticket_acquire(Ticket** out) {
     *out = t;
     return 0;
 }
-void ticket_recycle(Ticket* t) {
+void ticket_recycle(StatusBlock* t) {
     std::lock_guard<std::mutex> lock(g_ticket_mutex);
     g_ticket_free[t->dev].push_back(t);
 }
 
-// 0 = choose the backward blend kernel by footprint, 1 = pixel-per-lane, 2 = entry-per-lane (sr_set_backward_kernel)
+// 0 = the product choice (entry-per-lane at every footprint), 1 = pixel-per-lane, 2 = entry-per-lane (sr_set_backward_kernel)
 std::atomic<int> g_bwd_kernel{[] {
     const char* sel = getenv("SPLATRASTER_BWD");
-    return !sel ? 0 : (std::string(sel) == "wave" ? 1 : ((std::string(sel) == "quads" || std::string(sel) == "mfma") ? 2 : 0));
+    return !sel ? 0 : (std::string(sel) == "wave" ? 1 : (std::string(sel) == "quads" ? 2 : 0));
 }()};
 
 
@@ -260,6 +262,35 @@ sr::SplatsK make_splats(const SrSplats* s) {
     return k;
 }
 
+// The sort classes a list-length hint asks for: lists of up to 2048 / 4096 / 8192 entries, or (-1) all of them.  The Python
+// facade judges an overflow by the same figure (splatfields_amd/rasterizer.py: _covered_by_hint): change both together.
+long long covered_by_hint(long long hint) { return hint <= 2048 ? 2048 : hint <= 4096 ? 4096 : hint <= 8192 ? 8192 : -1; }
+
+// What every forward / backward entry opens with.  open_call: the arguments validated, the call remembered for the debug
+// snapshot, the kernel-side view and splats.  The entry then checks its own buffers (validate first, buffers second: a call
+// with a bad view AND null buffers reports the view) and carves the opaque ones it uses.
+struct Call {
+    hipStream_t st = nullptr;
+    sr::ViewK v; sr::SplatsK s;
+    sr::Geom g; sr::Binning b; sr::Image im;
+    void carve(const void* geom, void* binning, long long capacity, const void* image) {
+        sr::carve_geom(const_cast<void*>(geom), s.N, v.H, v.W, &g);
+        if (binning) sr::carve_binning(binning, capacity, &b);
+        if (image) sr::carve_image(const_cast<void*>(image), v.H, v.W, &im);
+    }
+};
+
+int open_call(Call& c, const CallContext& ctx, void* hip_stream) {
+    SR_TRY(validate(ctx.view, ctx.splats));
+    g_call = ctx;
+    c.st = static_cast<hipStream_t>(hip_stream);
+    c.v = make_view(ctx.view);
+    c.s = make_splats(ctx.splats);
+    return 0;
+}
+
+bool capacity_in_range(long long r) { return r >= 0 && r < (1ll << 32); }
+
 }  // namespace
 
 extern "C" {
@@ -293,7 +324,7 @@ int launch_stage1(const SrView* view, const sr::ViewK& v, const sr::SplatsK& s, 
 // them after launching the scatter (the GPU keeps working) and then launches only the sort classes that are needed.
 // hs == nullptr: nobody waits; `max_len` = the longest list the sort classes must cover (< 0: launch every class).
 int launch_stage2(const SrView* view, const sr::ViewK& v, const sr::SplatsK& s, const sr::Geom& g, const sr::Binning& b,
-                  const sr::Image& im, float* out_color, float* out_depth, float* out_alpha, HostSync* hs, long long max_len,
+                  const sr::Image& im, float* out_color, float* out_depth, float* out_alpha, StatusBlock* hs, long long max_len,
                   long long expected_len, hipStream_t st) {
     { StageTimer t_(2, st); sr::launch_emit(v, s.N, g, b, st); }
     SR_TRY(after_launch(view, st, "emit"));
@@ -318,18 +349,14 @@ extern "C" {
 
 int sr_forward_prepare(const SrView* view, const SrSplats* splats, void* geom, int* radii,
                        long long* instances_out, void* hip_stream) {
-    SR_TRY(validate(view, splats));
-    g_call = CallContext{view, splats, "snapshot_fw.dump"};
+    Call c;
+    SR_TRY(open_call(c, CallContext{view, splats, "snapshot_fw.dump"}, hip_stream));
     if (!geom || !instances_out || (splats->count > 0 && !radii)) return fail("null geom/radii/instances_out");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const sr::ViewK v = make_view(view);
-    const sr::SplatsK s = make_splats(splats);
-    sr::Geom g;
-    sr::carve_geom(geom, s.N, v.H, v.W, &g);
-    HostSync* hs = nullptr;
-    SR_TRY(get_host_sync(&hs));
-    SR_TRY(launch_stage1(view, v, s, g, radii, hs->pinned_dev, status_block_arm(*hs, st), st));
-    SR_TRY(check_hip(hipStreamSynchronize(st), "sync after prepare"));
+    c.carve(geom, nullptr, 0, nullptr);
+    StatusBlock* hs = nullptr;
+    SR_TRY(thread_block(&hs));
+    SR_TRY(launch_stage1(view, c.v, c.s, c.g, radii, hs->pinned_dev, status_block_arm(*hs, c.st), c.st));
+    SR_TRY(check_hip(hipStreamSynchronize(c.st), "sync after prepare"));
     *instances_out = (long long)hs->pinned[0];
     return 0;
 }
@@ -337,21 +364,15 @@ int sr_forward_prepare(const SrView* view, const SrSplats* splats, void* geom, i
 int sr_forward(const SrView* view, const SrSplats* splats, void* geom, int* radii, void* binning,
                long long binning_capacity, void* image, float* out_color, float* out_depth, float* out_alpha,
                long long* instances_out, void* hip_stream) {
-    SR_TRY(validate(view, splats));
-    g_call = CallContext{view, splats, "snapshot_fw.dump"};
+    Call c;
+    SR_TRY(open_call(c, CallContext{view, splats, "snapshot_fw.dump"}, hip_stream));
     if (!geom || !binning || !image || !out_color || !out_depth || !instances_out || (splats->count > 0 && !radii)) return fail("null buffer");
-    if (binning_capacity < 0 || binning_capacity >= (1ll << 32)) return fail("binning capacity out of range");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const sr::ViewK v = make_view(view);
-    const sr::SplatsK s = make_splats(splats);
-    sr::Geom g; sr::Binning b; sr::Image im;
-    sr::carve_geom(geom, s.N, v.H, v.W, &g);
-    sr::carve_binning(binning, binning_capacity, &b);
-    sr::carve_image(image, v.H, v.W, &im);
-    HostSync* hs = nullptr;
-    SR_TRY(get_host_sync(&hs));
-    SR_TRY(launch_stage1(view, v, s, g, radii, hs->pinned_dev, status_block_arm(*hs, st), st));   // k_scan_small stores the counters into hs->pinned
-    SR_TRY(launch_stage2(view, v, s, g, b, im, out_color, out_depth, out_alpha, hs, -1, -1, st));  // waits inside, GPU busy
+    if (!capacity_in_range(binning_capacity)) return fail("binning capacity out of range");
+    c.carve(geom, binning, binning_capacity, image);
+    StatusBlock* hs = nullptr;
+    SR_TRY(thread_block(&hs));
+    SR_TRY(launch_stage1(view, c.v, c.s, c.g, radii, hs->pinned_dev, status_block_arm(*hs, c.st), c.st));   // k_scan_small stores the counters into hs->pinned
+    SR_TRY(launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, hs, -1, -1, c.st));  // waits inside, GPU busy
     const long long total = (long long)hs->pinned[0];
     *instances_out = total;
     g_last_longest = (long long)hs->pinned[1];
@@ -361,45 +382,32 @@ int sr_forward(const SrView* view, const SrSplats* splats, void* geom, int* radi
 int sr_forward_render(const SrView* view, const SrSplats* splats, void* geom, void* binning,
                       long long instances, void* image, float* out_color, float* out_depth,
                       float* out_alpha, void* hip_stream) {
-    SR_TRY(validate(view, splats));
-    g_call = CallContext{view, splats, "snapshot_fw.dump"};
+    Call c;
+    SR_TRY(open_call(c, CallContext{view, splats, "snapshot_fw.dump"}, hip_stream));
     if (!geom || !binning || !image || !out_color || !out_depth) return fail("null buffer");
-    if (instances < 0 || instances >= (1ll << 32)) return fail("instance count out of range");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const sr::ViewK v = make_view(view);
-    const sr::SplatsK s = make_splats(splats);
-    sr::Geom g; sr::Binning b; sr::Image im;
-    sr::carve_geom(geom, s.N, v.H, v.W, &g);
-    sr::carve_binning(binning, instances, &b);
-    sr::carve_image(image, v.H, v.W, &im);
-    return launch_stage2(view, v, s, g, b, im, out_color, out_depth, out_alpha, nullptr, -1, -1, st);
+    if (!capacity_in_range(instances)) return fail("instance count out of range");
+    c.carve(geom, binning, instances, image);
+    return launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, nullptr, -1, -1, c.st);
 }
 
 int sr_forward_async(const SrView* view, const SrSplats* splats, void* geom, int* radii, void* binning,
                      long long binning_capacity, long long longest_list_hint, long long longest_list_expected, void* image,
                      float* out_color, float* out_depth, float* out_alpha, void** ticket_out, void* hip_stream) {
-    SR_TRY(validate(view, splats));
-    g_call = CallContext{view, splats, "snapshot_fw.dump"};
+    Call c;
+    SR_TRY(open_call(c, CallContext{view, splats, "snapshot_fw.dump"}, hip_stream));
     if (!geom || !binning || !image || !out_color || !out_depth || !ticket_out || (splats->count > 0 && !radii)) return fail("null buffer");
-    if (binning_capacity < 0 || binning_capacity >= (1ll << 32)) return fail("binning capacity out of range");
+    if (!capacity_in_range(binning_capacity)) return fail("binning capacity out of range");
     if (longest_list_hint < 0) return fail("longest_list_hint must be >= 0");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const sr::ViewK v = make_view(view);
-    const sr::SplatsK s = make_splats(splats);
-    sr::Geom g; sr::Binning b; sr::Image im;
-    sr::carve_geom(geom, s.N, v.H, v.W, &g);
-    sr::carve_binning(binning, binning_capacity, &b);
-    sr::carve_image(image, v.H, v.W, &im);
-    // the sort classes the hint asks for: lists up to 2048 / 4096 / 8192 entries, or all of them
-    const long long covered = longest_list_hint <= 2048 ? 2048 : longest_list_hint <= 4096 ? 4096 : longest_list_hint <= 8192 ? 8192 : -1;
-    b.sorted_up_to = covered < 0 ? 0xffffffffu : (uint32_t)covered;
-    Ticket* t = nullptr;
+    c.carve(geom, binning, binning_capacity, image);
+    const long long covered = covered_by_hint(longest_list_hint);
+    c.b.sorted_up_to = covered < 0 ? 0xffffffffu : (uint32_t)covered;
+    StatusBlock* t = nullptr;
     SR_TRY(ticket_acquire(&t));
-    int rc = launch_stage1(view, v, s, g, radii, t->pinned_dev, status_block_arm(*t, st), st);
-    if (!rc) rc = launch_stage2(view, v, s, g, b, im, out_color, out_depth, out_alpha, nullptr, covered,
-                                longest_list_expected >= 0 && longest_list_expected <= longest_list_hint ? longest_list_expected : -1, st);
+    int rc = launch_stage1(view, c.v, c.s, c.g, radii, t->pinned_dev, status_block_arm(*t, c.st), c.st);
+    if (!rc) rc = launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, nullptr, covered,
+                                longest_list_expected >= 0 && longest_list_expected <= longest_list_hint ? longest_list_expected : -1, c.st);
     if (rc) {   // nothing of this call may still write the block when it is handed out again
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(c.st);
         ticket_recycle(t);
         return rc;
     }
@@ -410,7 +418,7 @@ int sr_forward_async(const SrView* view, const SrSplats* splats, void* geom, int
 
 int sr_ticket_wait(void* ticket, long long* instances_out, long long* longest_list_out) {
     if (!ticket) return fail("null ticket");
-    Ticket* t = static_cast<Ticket*>(ticket);
+    StatusBlock* t = static_cast<StatusBlock*>(ticket);
     bool waited = false;
     const int rc = status_block_wait(*t, &waited);
     if (waited) g_counters[2].fetch_add(1, std::memory_order_relaxed);
@@ -428,9 +436,7 @@ int sr_ticket_wait(void* ticket, long long* instances_out, long long* longest_li
 
 long long sr_last_longest_list(void) { return g_last_longest; }
 
-int sr_ticket_release(void* ticket) {
-    return sr_ticket_wait(ticket, nullptr, nullptr);
-}
+int sr_ticket_release(void* ticket) { return sr_ticket_wait(ticket, nullptr, nullptr); }
 
 int sr_debug_counters(long long* out4, int reset) {
     if (!out4) return fail("null pointer in sr_debug_counters");
@@ -444,8 +450,8 @@ int backward_impl(int what, const SrView* view, const SrSplats* splats, const vo
                   long long instances, long long instances_rendered, const void* image, const int* radii,
                   const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* scratch,
                   const SrGrads* grads, int first, int count, void* hip_stream) {
-    SR_TRY(validate(view, splats));
-    g_call = CallContext{view, splats, "snapshot_bw.dump", dL_dcolor, dL_ddepth, dL_dalpha};
+    Call c;
+    SR_TRY(open_call(c, CallContext{view, splats, "snapshot_bw.dump", dL_dcolor, dL_ddepth, dL_dalpha}, hip_stream));
     if (!geom || !binning || !image || !scratch) return fail("null buffer");
     if ((what & 1) && !dL_dcolor) return fail("null buffer");
     if ((what & 2) && !grads) return fail("null buffer");
@@ -459,13 +465,9 @@ int backward_impl(int what, const SrView* view, const SrSplats* splats, const vo
         if (first < 0 || count < 0 || (first % sr::kBlock) != 0) return fail("splat range must start at a multiple of 256");
     }
     if (splats->raw_params & SR_FORWARD_ONLY) return fail("the forward of these buffers was run with SR_FORWARD_ONLY");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const sr::ViewK v = make_view(view);
-    const sr::SplatsK s = make_splats(splats);
-    sr::Geom g; sr::Binning b; sr::Image im;
-    sr::carve_geom(const_cast<void*>(geom), s.N, v.H, v.W, &g);
-    sr::carve_binning(binning, instances, &b);   // Binning::reached is written by the backward blend (splatraster.h)
-    sr::carve_image(const_cast<void*>(image), v.H, v.W, &im);
+    c.carve(geom, binning, instances, image);   // Binning::reached is written by the backward blend (splatraster.h)
+    const hipStream_t st = c.st;
+    const sr::SplatsK& s = c.s;
     float* slots = static_cast<float*>(scratch);
     if (what & 1) {
         StageTimer t_(5, st);
@@ -476,11 +478,11 @@ int backward_impl(int what, const SrView* view, const SrSplats* splats, const vo
         // instances per splat 0.156 vs 0.262, 7.4: 0.136 vs 0.212, 15: 0.129 vs 0.186, 67: 0.157 vs 0.210, 225: 0.182 vs 0.211,
         // 715: 0.163 vs 0.179, 1270: 0.168 vs 0.171.)  The pixel-per-lane kernel (render.hip) stays as an independently written
         // second implementation of the same slots: SPLATRASTER_BWD=wave / sr_set_backward_kernel(1) select it, the tests and
-        // tools/fuzz_backward.py compare the two ("mfma", the name of rounds 2-3, is accepted for "quads").
+        // tools/fuzz_backward.py compare the two.
         const int pinned = g_bwd_kernel.load(std::memory_order_relaxed);   // sr_set_backward_kernel / SPLATRASTER_BWD at load time
         const bool wave_kernel = pinned == 1;
-        if (wave_kernel) sr::launch_render_backward(v, g, b, im, dL_dcolor, dL_ddepth, dL_dalpha, slots, st);
-        else sr::launch_render_backward_quads(v, g, b, im, dL_dcolor, dL_ddepth, dL_dalpha, slots, st);
+        if (wave_kernel) sr::launch_render_backward(c.v, c.g, c.b, c.im, dL_dcolor, dL_ddepth, dL_dalpha, slots, st);
+        else sr::launch_render_backward_quads(c.v, c.g, c.b, c.im, dL_dcolor, dL_ddepth, dL_dalpha, slots, st);
     }
     if (what & 1) SR_TRY(after_launch(view, st, "render_backward"));
     if (what & 2) {
@@ -494,7 +496,7 @@ int backward_impl(int what, const SrView* view, const SrSplats* splats, const vo
         // small footprints (fewer than SR_BWD_SLOT_SPEC_BELOW instances per splat on average; unknown counts as small): the
         // variant that requests a splat's first gradient slots together with their `reached` bytes
         const bool small_fp = !(instances_rendered >= 0 && instances_rendered > (long long)SR_BWD_SLOT_SPEC_BELOW * (long long)s.N);
-        { StageTimer t_(6, st); sr::launch_preprocess_backward(v, s, g, radii, slots, b.reached, gr, first, count, small_fp, st); }
+        { StageTimer t_(6, st); sr::launch_preprocess_backward(c.v, s, c.g, radii, slots, c.b.reached, gr, first, count, small_fp, st); }
         SR_TRY(after_launch(view, st, "preprocess_backward"));
     }
     return 0;

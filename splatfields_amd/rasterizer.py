@@ -15,8 +15,11 @@ There is no CPU path: tensors must live on a HIP device and the library must be 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
@@ -75,7 +78,8 @@ def depth_gradient_enabled() -> bool:
 # safely, so it is OFF for the plain drop-in facade (`GaussianRasterizer.forward / forward_ex` called from an unmodified
 # training loop: the reference also renders with gradients enabled and never back-propagates, train.py:379-387, where nothing
 # would ever redeem a ticket) and ON inside the step functions that do redeem and re-render transparently
-# (splatfields_amd/view_parallel.py `_checked`, bench.py's step: `with async_forward(): ...; resolve_pending()`).
+# (`redeemed` below, which the steps of splatfields_amd/view_parallel.py go through; bench.py's step: `with async_forward(): ...;
+# resolve_pending()`).
 #   SPLATRASTER_ASYNC=1 / set_async_forward(True): on for every forward of cameras seen before -- the caller takes over the duty
 #       to call `resolve_pending()` (and to re-render on RasterizerOverflow) before using the outputs;
 #   SPLATRASTER_ASYNC=0 / set_async_forward(False): off everywhere, also inside the step functions;
@@ -83,7 +87,7 @@ def depth_gradient_enabled() -> bool:
 # First renders of a camera (or of a new splat count: after densification) and renders under no_grad always wait.
 _ASYNC = {"1": True, "true": True, "True": True, "on": True, "0": False, "false": False, "False": False, "off": False}.get(
     os.environ.get("SPLATRASTER_ASYNC", ""), None)
-_LIST_HEADROOM = 1.25
+_HEADROOM = 1.25   # what a launch is promised beyond what the last render showed: instances (capacity) and longest tile list
 
 
 class RasterizerOverflow(RuntimeError):
@@ -134,7 +138,7 @@ def host_sync_counters(reset: bool = False) -> dict:
             "tickets_created": int(out[3])}
 
 
-_BWD_KERNELS = {None: 0, "auto": 0, "wave": 1, "quads": 2, "mfma": 2}   # "mfma": the name rounds 2-3 gave the entry-per-lane kernel
+_BWD_KERNELS = {None: 0, "auto": 0, "wave": 1, "quads": 2}
 
 
 def set_backward_kernel(which) -> str:
@@ -145,13 +149,6 @@ def set_backward_kernel(which) -> str:
     return {0: "auto", 1: "wave", 2: "quads"}[prev]
 
 
-# Per-device estimate of the instance count used to size the binning buffer BEFORE the count is known, so that
-# the forward never drains the GPU pipeline (include/splatraster.h: sr_forward).  Grows on demand.
-_CAPACITY = {}
-_INSTANCES_PER_SPLAT = {}
-_CAPACITY_HEADROOM = 1.25
-
-
 def _round_capacity(instances: int) -> int:
     """Capacity for `instances` tile-splat instances: 25 % headroom, rounded UP to eight steps per power of two.  The sizes of
     the binning buffer and of the backward scratch follow the capacity, and a training loop renders a different view -- a
@@ -159,35 +156,86 @@ def _round_capacity(instances: int) -> int:
     maximum changed both allocation sizes, and the caching allocator answered with two fresh hipMallocs of ~100 MB (tens of
     milliseconds of host time each; seen as one 80 ms step in a 20-step run).  Quantised, the sizes change only when the
     count grows by more than a step (<= 12.5 %)."""
-    c = max(int(instances * _CAPACITY_HEADROOM) + 1024, 1 << 16)
+    c = max(int(instances * _HEADROOM) + 1024, 1 << 16)
     step = 1 << (c.bit_length() - 4)
     return (c + step - 1) // step * step
-# The library takes concurrent calls from host threads that render on their own streams (include/splatraster.h); these two
-# module-level estimates are the only state the facade shares between them: updated under a lock (read-modify-write of a max).
-import threading
-import weakref
-_CAPACITY_LOCK = threading.Lock()
+
+
+def _covered_by_hint(hint: int) -> int:
+    """The longest tile list the sort classes launched for a list-length hint cover: 2048 / 4096 / 8192 entries, or all.  The
+    library makes the same choice from the hint it is handed (csrc/api.hip: covered_by_hint) and has no entry that reports it:
+    change both together."""
+    return 2048 if hint <= 2048 else 4096 if hint <= 4096 else 8192 if hint <= 8192 else 1 << 62
+
+
+class _Promise(NamedTuple):
+    """What one launch of a forward was promised before its instance count was known."""
+    key: tuple                  # (device index, splat count, H, W): the row of the capacity table
+    capacity: int               # tile-splat instances the binning buffer holds
+    hint: Optional[int] = None  # None: the launch waits for its count (sr_forward); else the longest list to sort for, with headroom
+    expected: int = -1          # ... and without
+    covered: int = 0            # the longest list the sort classes of `hint` cover
+
+
+# What finished forwards have taught the facade, used to size the binning buffer BEFORE the instance count is known, so that
+# the forward never drains the GPU pipeline (include/splatraster.h: sr_forward).  Grows on demand.
+# The library takes concurrent calls from host threads that render on their own streams (include/splatraster.h); this is the
+# only state the facade shares between them: read (`plan`) and updated (`record`) under one lock (read-modify-write of a max).
+class _Estimates:
+    """The one owner of `capacity`, `per_splat`, the view packs' `seen` and LAST_INSTANCES: `record` alone writes them."""
+
+    CAPACITY_ROWS = 4096   # a long training run changes the splat count thousands of times
+    SEEN_ROWS = 64         # ... and so does densification for one camera
+
+    def __init__(self):
+        self.capacity = {}    # (device index, n, H, W) -> capacity that size needed so far
+        self.per_splat = {}   # (device index, H, W) -> most instances per splat this image size has shown
+        self.lock = threading.Lock()
+
+    def plan(self, device_index: int, n: int, H: int, W: int, view, may_async: bool) -> _Promise:
+        key = (device_index, n, H, W)
+        # known size: what it needed before; new size (the cloud was densified / pruned): the instances-per-splat ratio
+        # this image size has shown so far, so that the first forward after a densification step does not fall into the
+        # re-run path
+        with self.lock:
+            ratio = self.per_splat.get((device_index, H, W))
+            capacity = self.capacity.get(key) or (max(4 * n, 1 << 16) if ratio is None else _round_capacity(int(ratio * n)))
+            before = view.seen.get(n) if may_async else None
+        # this camera was rendered with this splat count before, within the capacity: launch without waiting (see _ASYNC above)
+        if before is None or _round_capacity(before[0]) > capacity:
+            return _Promise(key, capacity)
+        hint = int(before[1] * _HEADROOM) + 1
+        return _Promise(key, capacity, hint, int(before[1]), _covered_by_hint(hint))
+
+    def record(self, promise: _Promise, view, instances: int, longest: int) -> None:
+        """A forward launched on `promise` reported `instances` and a longest tile list of `longest` (< 0: unknown)."""
+        global LAST_INSTANCES
+        dev, n, H, W = key = promise.key
+        rkey = (dev, H, W)
+        with self.lock:
+            self.capacity[key] = max(self.capacity.get(key, 0), _round_capacity(instances))
+            if len(self.capacity) > self.CAPACITY_ROWS:
+                self.capacity.clear()
+            self.per_splat[rkey] = max(self.per_splat.get(rkey, 0.0), instances / max(n, 1))
+            if longest >= 0:   # what the next render of this camera with this splat count may assume
+                if len(view.seen) > self.SEEN_ROWS:
+                    view.seen.clear()
+                view.seen[n] = (int(instances), int(longest))
+            LAST_INSTANCES = instances
+
+
+_ESTIMATES = _Estimates()
 _TLS = threading.local()   # .pending: this host thread's forwards whose ticket has not been redeemed yet
 _PENDING_LOCK = threading.Lock()   # a thread's pending list is appended to by that thread and pruned by whoever redeems a ticket
                                    # (usually autograd's device thread): every mutation happens under this lock
 
 
-def _record_view(view, n: int, instances: int, longest: int) -> None:
-    """what the next render of this camera with this splat count may assume (kept on the cached view pack)"""
-    if longest >= 0:
-        if len(view.seen) > 64:   # densification changes the count thousands of times in a long run
-            view.seen.clear()
-        view.seen[n] = (int(instances), int(longest))
-
-
 class _Pending:
     """One forward launched by sr_forward_async: its ticket and what it was promised."""
 
-    def __init__(self, lib, ticket, capacity: int, covered: int, view, n: int, key, rkey):
-        self.lib, self.ticket, self.capacity, self.covered = lib, ticket, int(capacity), int(covered)
-        self.view, self.n, self.key, self.rkey = view, n, key, rkey
-        self.instances = None
-        self.error = None
+    def __init__(self, lib, ticket, promise: _Promise, view):
+        self.lib, self.ticket, self.promise, self.view = lib, ticket, promise, view
+        self.outcome = None   # of the one resolve that redeemed the ticket: the instance count, or the exception it raised
         # weak: a forward whose outputs are dropped without a backward (evaluation code that forgot no_grad) must not pin its
         # ticket -- the autograd ctx owns this object, and __del__ hands the ticket back
         lst = getattr(_TLS, "pending", None)
@@ -201,32 +249,33 @@ class _Pending:
 
     def resolve(self) -> int:
         """Redeems the ticket (waits for stage 1 of that forward if it is still running); returns the instance count or raises
-        RasterizerOverflow.  Idempotent."""
+        RasterizerOverflow, or what the library reported.  Idempotent: a later call repeats the outcome of the first."""
         if self.ticket is not None:
             ticket, self.ticket = self.ticket, None
-            inst, longest = C.c_longlong(0), C.c_longlong(0)
-            rc = self.lib.sr_ticket_wait(ticket, C.byref(inst), C.byref(longest))
-            lst = self._list
-            with _PENDING_LOCK:
-                lst[:] = [r for r in lst if r() is not None and r() is not self]
-            _lib.check(rc)
-            self.instances = int(inst.value)
-            instances, longest = int(inst.value), int(longest.value)
-            with _CAPACITY_LOCK:
-                _CAPACITY[self.key] = max(_CAPACITY.get(self.key, 0), _round_capacity(instances))
-                _INSTANCES_PER_SPLAT[self.rkey] = max(_INSTANCES_PER_SPLAT.get(self.rkey, 0.0), instances / max(self.n, 1))
-            _record_view(self.view, self.n, instances, longest)
-            global LAST_INSTANCES
-            LAST_INSTANCES = instances
-            if instances > self.capacity or longest > max(self.covered, 2048):
-                self.error = RasterizerOverflow(
-                    f"the forward of this view was launched without waiting for its instance count (sr_forward_async) for at most "
-                    f"{self.capacity} tile-splat instances and tile lists of up to {max(self.covered, 2048)} entries, but the view has "
-                    f"{instances} instances and a list of {longest}: it has no result (its outputs are NaN).  Nothing has been applied "
-                    f"and the estimates are corrected: re-run the step (or splatfields_amd.rasterizer.set_async_forward(False))")
-        if self.error is not None:
-            raise self.error
-        return self.instances
+            try:
+                self.outcome = self._redeem(ticket)
+            except Exception as e:  # noqa: BLE001 -- stored, raised below and by every later call
+                self.outcome = e
+        if isinstance(self.outcome, Exception):
+            raise self.outcome
+        return self.outcome
+
+    def _redeem(self, ticket):
+        inst, longest = C.c_longlong(0), C.c_longlong(0)
+        rc = self.lib.sr_ticket_wait(ticket, C.byref(inst), C.byref(longest))
+        with _PENDING_LOCK:
+            self._list[:] = [r for r in self._list if r() is not None and r() is not self]
+        _lib.check(rc)
+        instances, longest, promise = int(inst.value), int(longest.value), self.promise
+        _ESTIMATES.record(promise, self.view, instances, longest)
+        covered = max(promise.covered, 2048)
+        if instances > promise.capacity or longest > covered:
+            return RasterizerOverflow(
+                f"the forward of this view was launched without waiting for its instance count (sr_forward_async) for at most "
+                f"{promise.capacity} tile-splat instances and tile lists of up to {covered} entries, but the view has "
+                f"{instances} instances and a list of {longest}: it has no result (its outputs are NaN).  Nothing has been applied "
+                f"and the estimates are corrected: re-run the step (or splatfields_amd.rasterizer.set_async_forward(False))")
+        return instances
 
     def __del__(self):   # a forward whose outputs were dropped without a backward: hand the ticket back
         t, self.ticket = getattr(self, "ticket", None), None
@@ -256,18 +305,29 @@ def resolve_pending() -> None:
         raise err
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def redeemed(render_fn, scope: bool = False):
+    """`render_fn()`'s outputs with every asynchronously launched forward of this host thread redeemed HERE, before the caller
+    back-propagates: a forward whose promise did not hold has no result and is rendered once more (the estimates are corrected
+    by then), so a step function never sees RasterizerOverflow in the middle of an autograd pass and a rank never re-issues
+    collectives.  `scope`: inside an `async_forward()` scope -- for the step functions, the callers that launch is for."""
+    with async_forward() if scope else contextlib.nullcontext():
+        out = render_fn()
+        try:
+            resolve_pending()
+        except RasterizerOverflow:
+            out = render_fn()
+            resolve_pending()
+    return out
 
 
-def _f32c(t: torch.Tensor, device) -> torch.Tensor:
-    """fp32, on `device`, contiguous -- the camera tensors arrive strided (scene/cameras.py:68,74)."""
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """data pointer or None (ctypes takes either for a void* argument and for a pointer field of a struct)"""
+    return None if t is None else t.data_ptr()
 
 
-def _as_input(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
-    """The tensor itself when the kernels can read it in place (fp32, contiguous, on `device`: the normal case, no
-    Python or GPU work), otherwise a converted copy."""
+def _f32c(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
+    """fp32, contiguous, on `device`: the tensor itself when the kernels can read it in place (the normal case, no Python or
+    GPU work), otherwise a detached converted copy -- the camera tensors arrive strided (scene/cameras.py:68,74)."""
     if t is None:
         return None
     if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
@@ -343,9 +403,7 @@ class _ViewPack:
 
 
 def _splats_struct(n, means3D, opacities, scales, rotations, cov3D, shs, colors, raw_params: int = 0, shs_rest=None) -> _lib.SrSplats:
-    g = lambda t: None if t is None else t.data_ptr()
-    return _lib.SrSplats(int(n), g(means3D), g(opacities), g(scales), g(rotations), g(cov3D), g(shs), g(colors), int(raw_params),
-                         g(shs_rest))
+    return _lib.SrSplats(int(n), *map(_ptr, (means3D, opacities, scales, rotations, cov3D, shs, colors)), int(raw_params), _ptr(shs_rest))
 
 
 def _aligned16(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -356,6 +414,79 @@ def _stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _check_inputs(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest, slice_hook, color_grad_sink):
+    """The per-splat inputs as the kernels read them (fp32, contiguous, on means3D's device; None for an absent or empty one),
+    validated: (means3D, opacities [N], scales, rotations, cov3D, shs, colors, shs_rest, sh_coeffs)."""
+    if not means3D.is_cuda:
+        raise RuntimeError("splatfields_amd rasterizer has no CPU path: tensors must be on a HIP ('cuda') device")
+    dev = means3D.device
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    n = means3D.shape[0]
+    f = lambda t: _f32c(t, dev)
+    means3D_c, opac_c = f(means3D), f(opacities).reshape(-1)
+    sh_c, col_c, sc_c, rot_c, cov_c = f(_opt(sh)), f(_opt(colors_precomp)), f(_opt(scales)), f(_opt(rotations)), f(_opt(cov3Ds_precomp))
+    if opac_c.numel() != n:
+        raise RuntimeError("opacities must have dimensions (num_points, 1)")
+    for name, t, last in (("shs", sh_c, None), ("colors_precomp", col_c, 3), ("scales", sc_c, 3),
+                          ("rotations", rot_c, 4), ("cov3D_precomp", cov_c, 6)):
+        if t is not None and (t.shape[0] != n or (last is not None and t.shape[-1] != last)):
+            raise RuntimeError(f"{name} has an unexpected shape {tuple(t.shape)} for {n} points")
+    if sh_c is not None and (sh_c.dim() != 3 or sh_c.shape[2] != 3):
+        raise RuntimeError("shs must have dimensions (num_points, K, 3)")
+    sh_coeffs = 0 if sh_c is None else int(sh_c.shape[1])
+    rest_c = None
+    if _opt(sh_rest) is not None:
+        # the reference's two SH parameters, `_features_dc` [N,1,3] + `_features_rest` [N,15,3], without concatenating them
+        rest_c = _aligned16(f(sh_rest))
+        sh_c = _aligned16(sh_c)
+        if sh_c is None or sh_c.shape[1] != 1 or rest_c.dim() != 3 or tuple(rest_c.shape) != (n, 15, 3):
+            raise RuntimeError("with shs_rest, shs must be [N,1,3] (dc) and shs_rest [N,15,3]")
+        sh_coeffs = 16
+
+    if slice_hook is not None:
+        # checked here, not in the backward: an exception raised inside the autograd thread of ONE rank would leave the
+        # other ranks waiting in their collectives
+        if cov_c is not None:
+            raise ValueError("slice_hook requires scales / rotations inputs (cov3D_precomp is not supported in the sliced backward)")
+        if rest_c is not None:
+            raise ValueError("slice_hook requires the concatenated shs tensor (shs_rest is not supported in the sliced backward)")
+        if sh_c is not None and color_grad_sink is None:
+            raise ValueError("slice_hook requires color_grad_sink on the SH path (the sliced backward hands over colour gradients)")
+    return means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, rest_c, sh_coeffs
+
+
+def _launch_forward(lib, view, splats, n: int, H: int, W: int, dev, may_async: bool, radii, color, depth, alpha):
+    """Allocates the state buffers and launches both stages for the planned capacity, ticketed or waiting.  Returns (geom,
+    binning, image, capacity, instances, pending): a ticketed launch has `pending` and no `instances` yet."""
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        geom = torch.empty(lib.sr_geom_bytes(n, H, W), dtype=torch.uint8, device=dev)
+        image = torch.empty(lib.sr_image_bytes(H, W), dtype=torch.uint8, device=dev)
+        promise = _ESTIMATES.plan(dev.index, n, H, W, view, may_async)
+        capacity = promise.capacity
+        binning = torch.empty(lib.sr_binning_bytes(capacity, H, W), dtype=torch.uint8, device=dev)
+        state, outs = (C.byref(view.struct), C.byref(splats), _ptr(geom)), (_ptr(image), _ptr(color), _ptr(depth), _ptr(alpha))
+        if promise.hint is not None:
+            # this camera was rendered with this splat count before: launch without waiting (see _ASYNC above)
+            ticket = C.c_void_p()
+            _lib.check(lib.sr_forward_async(*state, _ptr(radii), _ptr(binning), capacity, promise.hint, promise.expected, *outs,
+                                            C.byref(ticket), stream))
+            return geom, binning, image, capacity, None, _Pending(lib, ticket, promise, view)
+        inst = C.c_longlong(0)
+        status = lib.sr_forward(*state, _ptr(radii), _ptr(binning), capacity, *outs, C.byref(inst), stream)
+        if status != _lib.SR_NEED_CAPACITY:
+            _lib.check(status)
+        instances = int(inst.value)
+        _ESTIMATES.record(promise, view, instances, int(lib.sr_last_longest_list()))
+        if status == _lib.SR_NEED_CAPACITY:
+            # first call for this size, or the cloud grew: re-run stage 2 with a buffer that fits
+            capacity = _round_capacity(instances)
+            binning = torch.empty(lib.sr_binning_bytes(capacity, H, W), dtype=torch.uint8, device=dev)
+            _lib.check(lib.sr_forward_render(*state, _ptr(binning), capacity, *outs, stream))
+    return geom, binning, image, capacity, instances, None
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """Autograd bridge; the counterpart of [EXT] ``_RasterizeGaussians``."""
 
@@ -364,58 +495,20 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings: GaussianRasterizationSettings, color_grad_sink=None, raw_params: int = 0, sh_rest=None,
                 slice_hook=None, grad_mode: bool = True):
         lib = _lib.load()
-        if not means3D.is_cuda:
-            raise RuntimeError("splatfields_amd rasterizer has no CPU path: tensors must be on a HIP ('cuda') device")
-        dev = means3D.device
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")
-        n = means3D.shape[0]
+        means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, rest_c, sh_coeffs = _check_inputs(
+            means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest, slice_hook, color_grad_sink)
+        dev, n = means3D.device, means3D.shape[0]
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
-        f = lambda t: _as_input(t, dev)
-        means3D_c, opac_c = f(means3D), f(opacities).reshape(-1)
-        sh_c, col_c, sc_c, rot_c, cov_c = f(_opt(sh)), f(_opt(colors_precomp)), f(_opt(scales)), f(_opt(rotations)), f(_opt(cov3Ds_precomp))
-        if opac_c.numel() != n:
-            raise RuntimeError("opacities must have dimensions (num_points, 1)")
-        for name, t, last in (("shs", sh_c, None), ("colors_precomp", col_c, 3), ("scales", sc_c, 3),
-                              ("rotations", rot_c, 4), ("cov3D_precomp", cov_c, 6)):
-            if t is not None and (t.shape[0] != n or (last is not None and t.shape[-1] != last)):
-                raise RuntimeError(f"{name} has an unexpected shape {tuple(t.shape)} for {n} points")
-        if sh_c is not None and (sh_c.dim() != 3 or sh_c.shape[2] != 3):
-            raise RuntimeError("shs must have dimensions (num_points, K, 3)")
-        sh_coeffs = 0 if sh_c is None else int(sh_c.shape[1])
-        rest_c = None
-        if _opt(sh_rest) is not None:
-            # the reference's two SH parameters, `_features_dc` [N,1,3] + `_features_rest` [N,15,3], without concatenating them
-            rest_c = _aligned16(f(sh_rest))
-            sh_c = _aligned16(sh_c)
-            if sh_c is None or sh_c.shape[1] != 1 or rest_c.dim() != 3 or tuple(rest_c.shape) != (n, 15, 3):
-                raise RuntimeError("with shs_rest, shs must be [N,1,3] (dc) and shs_rest [N,15,3]")
-            sh_coeffs = 16
-
-        if slice_hook is not None:
-            # checked here, not in the backward: an exception raised inside the autograd thread of ONE rank would leave the
-            # other ranks waiting in their collectives
-            if cov_c is not None:
-                raise ValueError("slice_hook requires scales / rotations inputs (cov3D_precomp is not supported in the sliced backward)")
-            if rest_c is not None:
-                raise ValueError("slice_hook requires the concatenated shs tensor (shs_rest is not supported in the sliced backward)")
-            if sh_c is not None and color_grad_sink is None:
-                raise ValueError("slice_hook requires color_grad_sink on the SH path (the sliced backward hands over colour gradients)")
         view = _ViewPack.get(raster_settings, dev, sh_coeffs)
-        color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
-        depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
+        color, depth, alpha = (torch.empty(c, H, W, dtype=torch.float32, device=dev) for c in (3, 1, 1))
         radii = torch.empty(n, dtype=torch.int32, device=dev)  # k_preprocess writes every element
-        ctx.raster_settings = raster_settings
-        ctx.color_grad_sink = color_grad_sink
-        ctx.slice_hook = slice_hook
+        ctx.raster_settings, ctx.color_grad_sink, ctx.slice_hook = raster_settings, color_grad_sink, slice_hook
         # nothing to differentiate (rendering / evaluation under no_grad): the forward skips what only the backward reads
         # (`needs_input_grad` reflects the inputs' requires_grad flags even under torch.no_grad(): the caller's grad mode --
         # autograd switches it off inside this function -- arrives as an argument)
         if not grad_mode or (not any(ctx.needs_input_grad[:8]) and not (len(ctx.needs_input_grad) > 11 and ctx.needs_input_grad[11])):
             raw_params = int(raw_params) | _lib.SR_FORWARD_ONLY
         ctx.raw_params = int(raw_params)
-        ctx.sh_coeffs = sh_coeffs
         ctx.n = n
         ctx.opac_shape = tuple(opacities.shape)
         ctx.in_dtypes = [None if t is None else t.dtype for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)]
@@ -431,59 +524,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.save_for_backward()
             return color, radii, depth, alpha
 
-        with torch.cuda.device(dev):
-            stream = _stream_ptr(dev)
-            splats = _splats_struct(n, means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, raw_params, rest_c)
-            geom = torch.empty(lib.sr_geom_bytes(n, H, W), dtype=torch.uint8, device=dev)
-            image = torch.empty(lib.sr_image_bytes(H, W), dtype=torch.uint8, device=dev)
-            inst = C.c_longlong(0)
-            key = (dev.index, n, H, W)
-            # known size: what it needed before; new size (the cloud was densified / pruned): the instances-per-splat ratio
-            # this image size has shown so far, so that the first forward after a densification step does not fall into the
-            # re-run path
-            with _CAPACITY_LOCK:
-                ratio = _INSTANCES_PER_SPLAT.get((dev.index, H, W))
-                capacity = _CAPACITY.get(key) or (max(4 * n, 1 << 16) if ratio is None else _round_capacity(int(ratio * n)))
-            rkey = (dev.index, H, W)
-            before = view.seen.get(n) if (async_forward_enabled() and not (int(raw_params) & _lib.SR_FORWARD_ONLY)) else None
-            if before is not None and _round_capacity(before[0]) <= capacity:
-                # this camera was rendered with this splat count before: launch without waiting (see _ASYNC above)
-                binning = torch.empty(lib.sr_binning_bytes(capacity, H, W), dtype=torch.uint8, device=dev)
-                hint = int(before[1] * _LIST_HEADROOM) + 1
-                covered = 2048 if hint <= 2048 else 4096 if hint <= 4096 else 8192 if hint <= 8192 else 1 << 62
-                ticket = C.c_void_p()
-                _lib.check(lib.sr_forward_async(C.byref(view.struct), C.byref(splats), _ptr(geom), _ptr(radii), _ptr(binning),
-                                                capacity, hint, int(before[1]), _ptr(image), _ptr(color), _ptr(depth), _ptr(alpha),
-                                                C.byref(ticket), stream))
-                ctx.pending = _Pending(lib, ticket, capacity, covered, view, n, key, rkey)
-                ctx.instances = None
-                ctx.capacity = capacity
-                ctx.view_pack = view
-                ctx.save_for_backward(means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, radii, geom, binning, image, rest_c)
-                return color, radii, depth, alpha
-            binning = torch.empty(lib.sr_binning_bytes(capacity, H, W), dtype=torch.uint8, device=dev)
-            status = lib.sr_forward(C.byref(view.struct), C.byref(splats), _ptr(geom), _ptr(radii), _ptr(binning),
-                                    capacity, _ptr(image), _ptr(color), _ptr(depth), _ptr(alpha), C.byref(inst), stream)
-            instances = int(inst.value)
-            _record_view(view, n, instances, int(lib.sr_last_longest_list()))
-            if status == _lib.SR_NEED_CAPACITY:
-                # first call for this size, or the cloud grew: re-run stage 2 with a buffer that fits
-                capacity = _round_capacity(instances)
-                binning = torch.empty(lib.sr_binning_bytes(capacity, H, W), dtype=torch.uint8, device=dev)
-                _lib.check(lib.sr_forward_render(C.byref(view.struct), C.byref(splats), _ptr(geom), _ptr(binning),
-                                                 capacity, _ptr(image), _ptr(color), _ptr(depth), _ptr(alpha), stream))
-            else:
-                _lib.check(status)
-            with _CAPACITY_LOCK:
-                _CAPACITY[key] = max(_CAPACITY.get(key, 0), _round_capacity(instances))
-                if len(_CAPACITY) > 4096:  # a long training run changes the splat count thousands of times
-                    _CAPACITY.clear()
-                _INSTANCES_PER_SPLAT[rkey] = max(_INSTANCES_PER_SPLAT.get(rkey, 0.0), instances / max(n, 1))
-        global LAST_INSTANCES
-        LAST_INSTANCES = instances
-        ctx.pending = None
-        ctx.instances = instances
-        ctx.capacity = capacity
+        splats = _splats_struct(n, means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, raw_params, rest_c)
+        # a forward that nothing will differentiate always waits: nothing would redeem its ticket before the image is used
+        may_async = async_forward_enabled() and not (ctx.raw_params & _lib.SR_FORWARD_ONLY)
+        geom, binning, image, ctx.capacity, ctx.instances, ctx.pending = _launch_forward(
+            lib, view, splats, n, H, W, dev, may_async, radii, color, depth, alpha)
         ctx.view_pack = view
         ctx.save_for_backward(means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, radii, geom, binning, image, rest_c)
         return color, radii, depth, alpha
@@ -502,7 +547,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         means3D, opac, sc, rot, cov, sh, col, radii, geom, binning, image, sh_rest = ctx.saved_tensors
         dev = means3D.device
         H, W = int(rs.image_height), int(rs.image_width)
-        g = lambda t: _as_input(t, dev)
+        g = lambda t: _f32c(t, dev)
         grad_color = g(grad_color)
         if grad_color is None:
             grad_color = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
@@ -531,8 +576,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             stream = _stream_ptr(dev)
             splats = _splats_struct(n, means3D, opac, sc, rot, cov, sh, col, ctx.raw_params, sh_rest)
             scratch = torch.empty(lib.sr_backward_scratch_bytes(ctx.capacity), dtype=torch.uint8, device=dev)
-            p = lambda t: None if t is None else t.data_ptr()
-            grads = _lib.SrGrads(p(d_means3D), p(d_means2D), p(d_opac), p(d_sc), p(d_rot), p(d_cov), p(d_sh), p(d_col), p(d_rest))
+            grads = _lib.SrGrads(*map(_ptr, (d_means3D, d_means2D, d_opac, d_sc, d_rot, d_cov, d_sh, d_col, d_rest)))
             if hook is None:
                 _lib.check(lib.sr_backward(C.byref(view.struct), C.byref(splats), _ptr(geom), _ptr(binning), ctx.capacity, ctx.instances,
                                            _ptr(image), _ptr(radii), _ptr(grad_color), _ptr(grad_depth), _ptr(grad_alpha),

@@ -16,19 +16,6 @@ from . import rasterizer as _rz
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
 
-def _redeemed(render_fn):
-    """`render_fn()`'s outputs with every asynchronously launched forward of this host thread checked (rasterizer.py:
-    sr_forward_async; only when the caller has switched that on): a forward whose capacity promise did not hold has no result
-    and is rendered again -- the estimates are corrected by then."""
-    out = render_fn()
-    try:
-        _rz.resolve_pending()
-    except _rz.RasterizerOverflow:
-        out = render_fn()
-        _rz.resolve_pending()
-    return out
-
-
 def render(viewpoint_camera, gaussian_dict: dict, pipe, bg_color: torch.Tensor, scaling_modifier=1.0,
            return_opacity=True, two_pass=False):
     means3D = gaussian_dict['means3D']
@@ -65,8 +52,9 @@ def render(viewpoint_camera, gaussian_dict: dict, pipe, bg_color: torch.Tensor, 
         fwd = lambda: rasterizer(**kw) + (None,)
     else:
         fwd = lambda: rasterizer.forward_ex(**kw)
-    # pipe.debug: nothing leaves this function unchecked (with SPLATRASTER_ASYNC=1 a forward may have been launched on a promise)
-    rendered_image, radii, depth, alpha = _redeemed(fwd) if getattr(pipe, "debug", False) else fwd()
+    # pipe.debug: nothing leaves this function unchecked (with SPLATRASTER_ASYNC=1 a forward may have been launched on a promise:
+    # rasterizer.redeemed renders one whose promise did not hold again)
+    rendered_image, radii, depth, alpha = _rz.redeemed(fwd) if getattr(pipe, "debug", False) else fwd()
     opacity_image = None
     if return_opacity:
         if two_pass:
@@ -111,6 +99,6 @@ def render_model(viewpoint_camera, gaussians, pipe, bg_color: torch.Tensor, scal
     fwd = lambda: GaussianRasterizer(raster_settings=rs).forward_raw(
         means3D=means3D, means2D=screenspace_points, opacity_logits=gaussians._opacity, log_scales=log_scales,
         quaternions=gaussians._rotation, **kw)
-    rendered_image, radii, depth, alpha = _redeemed(fwd) if getattr(pipe, "debug", False) else fwd()
+    rendered_image, radii, depth, alpha = _rz.redeemed(fwd) if getattr(pipe, "debug", False) else fwd()
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
             "radii": radii, "opacity": alpha if return_opacity else None, "depth": depth}

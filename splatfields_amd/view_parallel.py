@@ -20,6 +20,8 @@ from typing import Callable, Iterable, List, Sequence
 import torch
 import torch.distributed as dist
 
+from .rasterizer import redeemed
+
 
 def shard_views(views: Sequence, rank: int, world: int) -> list:
     """Round-robin deal of this step's view list (reference train.py:158-163 builds the list)."""
@@ -101,22 +103,6 @@ class _Window:
             self.b.record(torch.cuda.current_stream(self.dev))
             (ExchangeStats._inner if self.inner else ExchangeStats._win).append((self.a, self.b))
         return False
-
-
-def _checked(render_fn: Callable):
-    """``render_fn()`` launches a forward -- without waiting for its instance count when the camera was rendered before
-    (rasterizer.py: sr_forward_async) -- and returns its outputs.  The ticket is redeemed HERE, before the caller
-    back-propagates: a forward whose capacity guess did not hold is re-rendered (the estimates are corrected by then), so the
-    step functions never see RasterizerOverflow in the middle of an autograd pass -- and a rank never re-issues collectives."""
-    from . import rasterizer as rz
-    with rz.async_forward():   # the tickets are redeemed right here: this is the caller the asynchronous launch is for
-        out = render_fn()
-        try:
-            rz.resolve_pending()
-        except rz.RasterizerOverflow:
-            out = render_fn()
-            rz.resolve_pending()
-    return out
 
 
 def _nbytes(t: torch.Tensor) -> float:
@@ -387,9 +373,9 @@ def sh_gather_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_fn
             tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
             projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
         sink = []
-        color, radii, depth, alpha = _checked(lambda: GaussianRasterizer(rs).forward_ex(
+        color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
             means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-            shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink))
+            shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink), scope=True)
         # the rasterizer's backward accumulates the 4 small gradients (incl. the view-direction term in means3D) and hands
         # over the clamp-masked colour gradient instead of writing 192 B/splat of SH gradient
         backward_fn(vi, color, depth, alpha)
@@ -452,9 +438,9 @@ def _sh_gather_step_sliced(params, cams, bg, sh_degree, backward_fn, scaling_mod
         projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
     hook = _SlicedGatherHook(slices, world, group, dev)
     sink = []
-    color, radii, depth, alpha = _checked(lambda: GaussianRasterizer(rs).forward_ex(
+    color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
         means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-        shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink, slice_hook=hook))
+        shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink, slice_hook=hook), scope=True)
     campos_all = _campos_of(cams, dev)          # gathered[r] is view r (one view per rank: V == world)
     d_shs = torch.empty_like(shs, dtype=torch.float32)
     backward_fn(vi, color, depth, alpha)    # blend, then per slice: per-splat backward + hook.on_slice (collectives issued)
@@ -599,9 +585,9 @@ def sh_sharded_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_f
             image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
             tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
             projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
-        color, radii, depth, alpha = _checked(lambda: GaussianRasterizer(rs).forward_ex(
+        color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
             means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-            colors_precomp=cols, scales=params["scales"], rotations=params["rotations"]))
+            colors_precomp=cols, scales=params["scales"], rotations=params["rotations"]), scope=True)
         backward_fn(vi, color, depth, alpha)
         g = cols.grad if cols.grad is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
         dcol_send[:, slot].reshape(world * shard, 3)[:n].copy_(g) if k == 1 else \
@@ -658,7 +644,7 @@ def view_parallel_step(params: List[torch.Tensor], views: Sequence, render_loss:
             tot = l if tot is None else tot + l
         return tot
 
-    total = _checked(losses)
+    total = redeemed(losses, scope=True)
     n_views = len(views)
     if total is not None:
         # local contribution to the global mean; summed (not averaged) across ranks below
@@ -720,7 +706,7 @@ def field_view_parallel_step(compute_splats: Callable[[], dict], views: Sequence
             tot = l if tot is None else tot + l
         return tot
 
-    total = _checked(losses)
+    total = redeemed(losses, scope=True)
     n_views = len(views)
     ref = outputs[keys[0]]
     if total is not None:

@@ -117,14 +117,14 @@ def test_a_capacity_guess_that_does_not_hold_raises_before_any_gradient_and_the_
     _step(sp, [cam], bg, grads)
     inst_small = pack.seen[N][0]
     key = (sp["means3D"].device.index, N, H, W)
-    rz._CAPACITY[key] = rz._round_capacity(inst_small)            # as if only the small cloud had ever been seen
+    rz._ESTIMATES.capacity[key] = rz._round_capacity(inst_small)   # as if only the small cloud had ever been seen
     p = _leaves(big)
     (c, r, d, a), m2 = _forward(p, cam, bg)
     loss = (c * grads[0]).sum() + (d * grads[1]).sum() + (a * grads[2]).sum()
     with pytest.raises(rz.RasterizerOverflow, match="re-run the step"):
         loss.backward()
     assert all(v.grad is None for v in p.values())                # nothing was applied
-    assert rz._CAPACITY[key] >= pack.seen[N][0] > inst_small      # the estimates are corrected ...
+    assert rz._ESTIMATES.capacity[key] >= pack.seen[N][0] > inst_small   # the estimates are corrected ...
     g, out = _step(big, [cam], bg, grads)                         # ... so the retry goes through (asynchronously again)
     for k in NAMES:
         assert torch.equal(g[k], ref_g[k]), k
@@ -181,7 +181,7 @@ def test_resolve_pending_and_the_step_functions_re_render_transparently(scene):
         pack = rz._ViewPack.get(_settings(cam, bg), sp["means3D"].device, 16)
         pack.seen[N] = (pack.seen[N][0] // 8, pack.seen[N][1])
     key = (sp["means3D"].device.index, N, H, W)
-    rz._CAPACITY[key] = rz._round_capacity(rz.LAST_INSTANCES // 8)
+    rz._ESTIMATES.capacity[key] = rz._round_capacity(rz.LAST_INSTANCES // 8)
     rz.host_sync_counters(reset=True)
     got = run()                                                   # no exception: redeemed before the backward, re-rendered
     assert rz.host_sync_counters()["async_forwards"] > len(cams)  # at least one forward was launched twice
@@ -256,7 +256,7 @@ def test_a_stale_promise_cannot_be_consumed_silently(scene):
     pack = rz._ViewPack.get(_settings(cam, bg), sp["means3D"].device, 16)
     inst_small = pack.seen[N][0]
     key = (sp["means3D"].device.index, N, H, W)
-    rz._CAPACITY[key] = rz._round_capacity(inst_small)            # only the small cloud has ever been seen
+    rz._ESTIMATES.capacity[key] = rz._round_capacity(inst_small)   # only the small cloud has ever been seen
     p = _leaves(big)
     (c, r, d, a), m2 = _forward(p, cam, bg)
     loss = (c * grads[0]).sum() + (d * grads[1]).sum() + (a * grads[2]).sum()
@@ -270,7 +270,7 @@ def test_a_stale_promise_cannot_be_consumed_silently(scene):
     # render(): with pipe.debug nothing unchecked leaves the function -- the stale forward is rendered again inside
     from types import SimpleNamespace
     from splatfields_amd.render import render
-    rz._CAPACITY[key] = rz._round_capacity(inst_small)
+    rz._ESTIMATES.capacity[key] = rz._round_capacity(inst_small)
     pack.seen[N] = (inst_small, pack.seen[N][1])
     gd_ = {"means3D": big["means3D"], "active_sh_degree": 3, "gaussian_opacity": big["opacities"], "gaussian_scales": big["scales"],
            "gaussian_rotations": big["rotations"], "gaussian_features": big["shs"]}

@@ -336,10 +336,10 @@ def test_capacity_regrow_path_gives_identical_results(hip_device):
     sp, cam, st, grads = make_scene(5000, 160, 96, mean_scale=0.03)
     out_a, g_a = run_hip(sp, st, grads, hip_device)          # capacity learned by now
     key = (torch.device(hip_device).index or 0, 5000, 96, 160)
-    assert key in rz._CAPACITY
-    rz._CAPACITY[key] = 64                                     # far below the ~100k instances of this scene
+    assert key in rz._ESTIMATES.capacity
+    rz._ESTIMATES.capacity[key] = 64   # far below the ~100k instances of this scene
     out_b, g_b = run_hip(sp, st, grads, hip_device)
-    assert rz._CAPACITY[key] > 64 and rz.LAST_INSTANCES > 64
+    assert rz._ESTIMATES.capacity[key] > 64 and rz.LAST_INSTANCES > 64
     for k in out_a:
         assert torch.equal(out_a[k], out_b[k]), k
     for k in g_a:

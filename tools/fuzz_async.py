@@ -73,7 +73,7 @@ def main():
         rz.set_async_forward(True)
         pack.seen.clear(); pack.seen.update(before)           # the waiting render refreshed the record: make it stale again
         key = (dev.index, n, h, w)
-        rz._CAPACITY[key] = rz._round_capacity(before[n][0])  # ... and the capacity: as if only the first cloud had been seen
+        rz._ESTIMATES.capacity[key] = rz._round_capacity(before[n][0])  # ... and the capacity: as if only the first cloud had been seen
         outcome = "held"
         try:
             got2 = step(sp2, rs, grads, use_sh)
