@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -41,6 +42,15 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+
+
+def settings_from_camera(cam, bg, sh_degree, scale_modifier=1.0, debug=False) -> GaussianRasterizationSettings:
+    """The settings of one view from a camera object of the reference (scene/cameras.py: ``image_height, image_width, FoVx, FoVy,
+    world_view_transform, full_proj_transform, camera_center``), as gaussian_renderer/__init__.py:59-72 builds them."""
+    return GaussianRasterizationSettings(
+        image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+        tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scale_modifier, viewmatrix=cam.world_view_transform,
+        projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=bool(debug))
 
 
 LAST_INSTANCES = 0  # tile-splat instances of the most recent forward (diagnostics / bench)

@@ -8,12 +8,10 @@ the work; ``two_pass=True`` reproduces the reference's call pattern literally; (
 screen-space dummy follows ``means3D`` instead of the literal "cuda" (:49)."""
 from __future__ import annotations
 
-import math
-
 import torch
 
 from . import rasterizer as _rz
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterizer import GaussianRasterizer, settings_from_camera
 
 
 def render(viewpoint_camera, gaussian_dict: dict, pipe, bg_color: torch.Tensor, scaling_modifier=1.0,
@@ -38,12 +36,7 @@ def render(viewpoint_camera, gaussian_dict: dict, pipe, bg_color: torch.Tensor, 
         pass
 
     def settings(bg):
-        return GaussianRasterizationSettings(
-            image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-            tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-            bg=bg, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-            projmatrix=viewpoint_camera.full_proj_transform, sh_degree=active_sh_degree,
-            campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(pipe, "debug", False)))
+        return settings_from_camera(viewpoint_camera, bg, active_sh_degree, scaling_modifier, getattr(pipe, "debug", False))
 
     rasterizer = GaussianRasterizer(raster_settings=settings(bg_color))
     kw = dict(means3D=means3D, means2D=screenspace_points, shs=gaussian_features, colors_precomp=gaussian_rgb,
@@ -85,12 +78,8 @@ def render_model(viewpoint_camera, gaussians, pipe, bg_color: torch.Tensor, scal
         screenspace_points.retain_grad()
     except Exception:
         pass
-    rs = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=int(gaussians.active_sh_degree),
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=bool(getattr(pipe, "debug", False)))
+    rs = settings_from_camera(viewpoint_camera, bg_color, int(gaussians.active_sh_degree), scaling_modifier,
+                              getattr(pipe, "debug", False))
     dc, rest = gaussians._features_dc, gaussians._features_rest
     if rest.shape[1] == 15:
         kw = dict(shs=dc, shs_rest=rest)

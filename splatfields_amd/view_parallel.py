@@ -12,15 +12,23 @@ SH gradient at all.
 
 Densification statistics (`viewspace_points.grad`, `radii`) are per view; this harness keeps the
 reference's "last view wins" rule (train.py:178, :282, :307) on every rank for its own last view.
+
+Layout of the module: every step function resolves rank and world in `_rank_world`, renders through `_render` and issues its
+collectives through one `_Exchange`, which also books their bytes and times the exchange windows for `ExchangeStats`;
+`_issue_gradient_reduce` / `_land` are the "large gradients alone, small ones packed" exchange of `allreduce_gradients` and
+`view_parallel_step`.
 """
 from __future__ import annotations
 
+import contextlib
+import math
 from typing import Callable, Iterable, List, Sequence
 
 import torch
 import torch.distributed as dist
 
-from .rasterizer import redeemed
+from . import sh as shmod
+from .rasterizer import GaussianRasterizer, redeemed, settings_from_camera, slice_ranges
 
 
 def shard_views(views: Sequence, rank: int, world: int) -> list:
@@ -37,9 +45,23 @@ PACK_BELOW_BYTES = 64 << 20
 # (ReduceOp.AVG, all_gather_into_tensor, device all_to_all_single) the multi-GPU steps rely on.
 FORCE_COLLECTIVES = False
 
+_GEOMETRIC = ["means3D", "scales", "rotations", "opacities"]
+
 
 def _exchange(world: int) -> bool:
     return world > 1 or (FORCE_COLLECTIVES and dist.is_initialized())
+
+
+def _rank_world(rank, world, group, n_views: int = None):
+    """(rank, world) of a step: what the caller passed, else the process group's, else a single process.  `n_views`: for the
+    steps that deal every rank the same number of views."""
+    if world is None:
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if rank is None:
+        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if n_views is not None and n_views % world != 0:
+        raise ValueError("the number of views must be a multiple of the number of ranks")
+    return rank, world
 
 
 class ExchangeStats:
@@ -48,7 +70,7 @@ class ExchangeStats:
     orders it behind the collective), summed over the step's phases; the local compute that ran inside those windows (what
     the exchange is overlapped with); and the bytes every GPU puts on the wire under the ring model RCCL uses on a
     point-to-point xGMI node: all-reduce of S bytes 2 (G-1)/G S, all-gather / all-to-all of S bytes in total (G-1)/G S.
-    The caller brackets a step with ``end_step()``.  Off by default (no events are created)."""
+    The caller brackets a step with ``end_step()``.  Off by default (no events are created).  `_Exchange` is what fills it."""
     enabled = False
     _win: list = []        # (start, end) events of the current step's exchange windows
     _inner: list = []      # (start, end) events of compute inside them
@@ -58,12 +80,6 @@ class ExchangeStats:
     @classmethod
     def reset(cls, on: bool):
         cls.enabled, cls._win, cls._inner, cls._bytes, cls.steps = bool(on), [], [], 0.0, []
-
-    @classmethod
-    def note(cls, kind: str, nbytes: float, world: int):
-        if cls.enabled and world > 0:
-            f = (world - 1) / world
-            cls._bytes += nbytes * (2.0 * f if kind == "all_reduce" else f)
 
     @classmethod
     def end_step(cls):
@@ -83,30 +99,106 @@ class ExchangeStats:
                 "steps": len(cls.steps)}
 
 
-class _Window:
-    """`with _Window(dev):` = the exchange window of one step; `with _Window(dev, inner=True):` = compute inside it."""
+class _Works:
+    """Several pending collectives, waited for as one."""
 
-    def __init__(self, dev, inner: bool = False):
-        self.on = ExchangeStats.enabled and torch.device(dev).type == "cuda"
-        self.inner = inner
-        self.dev = dev
+    def __init__(self, works):
+        self.works = works
 
-    def __enter__(self):
-        if self.on:
-            self.a = torch.cuda.Event(enable_timing=True)
-            self.b = torch.cuda.Event(enable_timing=True)
-            self.a.record(torch.cuda.current_stream(self.dev))
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.b.record(torch.cuda.current_stream(self.dev))
-            (ExchangeStats._inner if self.inner else ExchangeStats._win).append((self.a, self.b))
-        return False
+    def wait(self):
+        for w in self.works:
+            w.wait()
 
 
-def _nbytes(t: torch.Tensor) -> float:
-    return float(t.numel() * t.element_size())
+class _Exchange:
+    """The collectives of one step over `group`, and their accounting: every method issues its collective asynchronously, books
+    the bytes it puts on the wire with `ExchangeStats` and returns something with ``.wait()``.  `active` is False where the step
+    runs without an exchange (one rank, `_exchange`); nothing else may be called then.
+
+    The exchange window of `ExchangeStats` is ``with ex.window():``, or `open()` where the first collective is issued and
+    `close()` where the last one has been waited for (the sliced gather step issues its first from inside the backward);
+    ``with ex.compute():`` marks local compute inside it."""
+
+    def __init__(self, world: int, group, dev):
+        self.world, self.group, self.dev = world, group, dev
+        self.active = _exchange(world)
+        self.backend = dist.get_backend(group) if self.active else None
+        self._opened = None
+
+    # ---- ExchangeStats ----
+    def _mark(self):
+        if not (ExchangeStats.enabled and torch.device(self.dev).type == "cuda"):
+            return None
+        e = torch.cuda.Event(enable_timing=True)
+        e.record(torch.cuda.current_stream(self.dev))
+        return e
+
+    def _book(self, tensors, all_reduce: bool = False):
+        if ExchangeStats.enabled and self.world > 0:
+            f = (self.world - 1) / self.world
+            ExchangeStats._bytes += float(sum(t.numel() * t.element_size() for t in tensors)) * (2.0 * f if all_reduce else f)
+
+    def open(self):
+        if self._opened is None:
+            self._opened = self._mark()
+
+    def close(self):
+        if self._opened is not None:
+            ExchangeStats._win.append((self._opened, self._mark()))
+            self._opened = None
+
+    @contextlib.contextmanager
+    def window(self):
+        self.open()
+        try:
+            yield
+        finally:
+            self.close()
+
+    @contextlib.contextmanager
+    def compute(self):
+        a = self._mark()
+        try:
+            yield
+        finally:
+            if a is not None:
+                ExchangeStats._inner.append((a, self._mark()))
+
+    # ---- collectives ----
+    def all_reduce(self, t: torch.Tensor, op=dist.ReduceOp.SUM):
+        self._book([t], all_reduce=True)
+        return dist.all_reduce(t, op=op, group=self.group, async_op=True)
+
+    def all_reduce_many(self, tensors: Sequence[torch.Tensor]):
+        """SUM all-reduce of several contiguous tensors in place as ONE launch where the backend can group them (RCCL:
+        ncclGroupStart / End through torch's coalescing manager -- the tensors stay where they are, no packing copy)."""
+        self._book(tensors, all_reduce=True)
+        tensors = [t for t in tensors if t.numel() > 0]
+        if self.backend == "nccl" and hasattr(dist, "_coalescing_manager") and tensors:
+            try:
+                with dist._coalescing_manager(group=self.group, device=tensors[0].device, async_ops=True) as cm:
+                    for t in tensors:
+                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+                return cm
+            except Exception:  # noqa: BLE001 -- an older torch without async coalescing: one collective per tensor below
+                pass
+        return _Works([dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True) for t in tensors])
+
+    def all_gather(self, out: torch.Tensor, inp: torch.Tensor):
+        """out [world, ...] = every rank's contiguous `inp` [...]"""
+        self._book([out])
+        return dist.all_gather_into_tensor(out.view(-1), inp.reshape(-1), group=self.group, async_op=True)
+
+    def all_to_all(self, out: torch.Tensor, inp: torch.Tensor):
+        """Equal-split all-to-all of contiguous buffers [world, ...].  RCCL moves device buffers directly; gloo (the CPU-backend
+        tests) only implements it for host tensors, so it is staged through the host there (and has finished on return)."""
+        self._book([inp])
+        if self.backend == "gloo" and inp.is_cuda:
+            o = torch.empty(out.shape, dtype=out.dtype)
+            dist.all_to_all_single(o, inp.cpu(), group=self.group)
+            out.copy_(o)
+            return _Works([])
+        return dist.all_to_all_single(out, inp, group=self.group, async_op=True)
 
 
 # xGMI on an 8 x MI355X node: every GPU has 7 point-to-point links of ~153 GB/s (both directions together; ~76.8 GB/s each
@@ -182,6 +274,49 @@ def pack_gradients(grads: Sequence[torch.Tensor]):
         off += g.numel()
     return flat, views
 
+def _fill_missing_grads(tensors: Iterable[torch.Tensor]) -> None:
+    """A tensor without a gradient on this rank (it rendered no view, or the tensor did not reach its loss) takes part in the
+    exchange with zeros, so that all ranks issue the same collectives."""
+    for p in tensors:
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+
+
+def _issue_gradient_reduce(ex: _Exchange, params: Sequence[torch.Tensor], op, *, alone: Callable = None,
+                           behind_large: Sequence[torch.Tensor] = (), extra: torch.Tensor = None):
+    """Issues the all-reduce of every ``p.grad``: the large tensors (and those `alone(p)` names) in place, largest first, so that
+    the largest ring starts while the rest is queued; then `behind_large`; then the small ones packed, one buffer per dtype in
+    first-seen order, the scalar `extra` riding last in the buffer of its dtype.  Returns ``(works, reduced, packed)``: the
+    pending collectives, every tensor they reduce, and per packed buffer ``(its parameters, the views of their segments [+ the
+    view of extra])`` for `_land`."""
+    big = sorted((p for p in params if p.grad.numel() * p.grad.element_size() >= PACK_BELOW_BYTES or (alone is not None and alone(p))),
+                 key=lambda p: -p.grad.numel())
+    reduced = [p.grad for p in big] + list(behind_large)
+    works = [ex.all_reduce(t, op) for t in reduced]
+    by_dtype = {}
+    for p in params:
+        if not any(p is b for b in big):
+            by_dtype.setdefault(p.grad.dtype, []).append(p)
+    if extra is not None:
+        by_dtype.setdefault(extra.dtype, [])
+    packed = []
+    for dtype, ps in by_dtype.items():
+        rides = [extra.reshape(1)] if extra is not None and dtype == extra.dtype else []
+        flat, views = pack_gradients([p.grad for p in ps] + rides)
+        works.append(ex.all_reduce(flat, op))
+        reduced.append(flat)
+        packed.append((ps, views))
+    return works, reduced, packed
+
+
+def _land(works, packed) -> None:
+    """Waits for the collectives of `_issue_gradient_reduce` and re-points every packed ``p.grad`` at its segment."""
+    for w in works:
+        w.wait()
+    for ps, views in packed:
+        for p, v in zip(ps, views):
+            p.grad = v
+
 
 def allreduce_gradients(params: Iterable[torch.Tensor], world: int, group=None, *, sh_param: torch.Tensor = None,
                         sh_active_coeffs: int = None, restore_none: bool = False) -> None:
@@ -205,55 +340,27 @@ def allreduce_gradients(params: Iterable[torch.Tensor], world: int, group=None, 
         return
     params = list(params)
     had_grad = [p.grad is not None for p in params]
-    for p in params:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
+    _fill_missing_grads(params)
     all_params = params
     sh_slice = None
     if sh_param is not None and sh_active_coeffs is not None and sh_param.grad is not None and sh_param.grad.dim() == 3 \
             and 0 < sh_active_coeffs < sh_param.grad.shape[1]:
         params = [p for p in params if p is not sh_param]
         sh_slice = sh_param.grad[:, :sh_active_coeffs].contiguous()
-    big = sorted((p for p in params if p.grad.numel() * p.grad.element_size() >= PACK_BELOW_BYTES),
-                 key=lambda p: -p.grad.numel())
-    small = [p for p in params if p.grad.numel() * p.grad.element_size() < PACK_BELOW_BYTES]
     # RCCL averages in the collective itself (no extra pass over 236 B/splat); gloo (CPU tests) has no AVG
-    avg = dist.get_backend(group) == "nccl"
+    ex = _Exchange(world, group, all_params[0].grad.device if all_params else "cpu")
+    avg = ex.backend == "nccl"
     op = dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM
-    dev = all_params[0].grad.device if all_params else "cpu"
     flags = None
-    with _Window(dev):
-        works = [dist.all_reduce(p.grad, op=op, group=group, async_op=True) for p in big]
-        for p in big:
-            ExchangeStats.note("all_reduce", _nbytes(p.grad), world)
-        if sh_slice is not None:
-            works.append(dist.all_reduce(sh_slice, op=op, group=group, async_op=True))
-            ExchangeStats.note("all_reduce", _nbytes(sh_slice), world)
-        by_dtype = {}
-        for p in small:
-            by_dtype.setdefault(p.grad.dtype, []).append(p)
-        packed = []
-        for ps in by_dtype.values():
-            flat, views = pack_gradients([p.grad for p in ps])
-            works.append(dist.all_reduce(flat, op=op, group=group, async_op=True))
-            ExchangeStats.note("all_reduce", _nbytes(flat), world)
-            packed.append((ps, flat, views))
+    with ex.window():
+        works, reduced, packed = _issue_gradient_reduce(ex, params, op, behind_large=[] if sh_slice is None else [sh_slice])
         if restore_none:
-            flags = torch.tensor([1.0 if h else 0.0 for h in had_grad], dtype=torch.float32, device=dev)
-            works.append(dist.all_reduce(flags, op=dist.ReduceOp.SUM, group=group, async_op=True))
-        for w in works:
-            w.wait()
+            flags = torch.tensor([1.0 if h else 0.0 for h in had_grad], dtype=torch.float32, device=ex.dev)
+            works.append(ex.all_reduce(flags))
+        _land(works, packed)
     if not avg:
-        scale = 1.0 / world
-        for p in big:
-            p.grad.mul_(scale)
-        for _, flat, _ in packed:
-            flat.mul_(scale)
-        if sh_slice is not None:
-            sh_slice.mul_(scale)
-    for ps, _, views in packed:
-        for p, v in zip(ps, views):
-            p.grad = v
+        for t in reduced:
+            t.mul_(1.0 / world)
     if sh_slice is not None:
         sh_param.grad[:, :sh_slice.shape[1]].copy_(sh_slice)
     if flags is not None:
@@ -262,29 +369,27 @@ def allreduce_gradients(params: Iterable[torch.Tensor], world: int, group=None, 
                 p.grad = None   # no rank had a gradient for it: as in the single-process loop, the optimizer skips it
 
 
-def _all_reduce_many(tensors: Sequence[torch.Tensor], group=None):
-    """SUM all-reduce of several contiguous tensors in place, asynchronously, as ONE launch where the backend can group them
-    (RCCL: ncclGroupStart / End through torch's coalescing manager -- the tensors stay where they are, no packing copy);
-    returns an object with .wait()."""
-    tensors = [t for t in tensors if t.numel() > 0]
+def _render(params: dict, cam, bg, sh_degree: int, scaling_modifier: float, **color):
+    """(color, radii, depth, alpha) of one view of a step, launched without the mid-forward host wait and with its ticket
+    redeemed before the caller back-propagates.  `color`: ``shs=`` (+ ``color_grad_sink=``, ``slice_hook=``) or
+    ``colors_precomp=``, as `GaussianRasterizer.forward_ex` takes them."""
+    rs = settings_from_camera(cam, bg, sh_degree, scaling_modifier)
+    means3D = params["means3D"]
+    return redeemed(lambda: GaussianRasterizer(rs).forward_ex(
+        means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
+        scales=params["scales"], rotations=params["rotations"], **color), scope=True)
 
-    class _Works:
-        def __init__(self, ws):
-            self.ws = ws
 
-        def wait(self):
-            for w in self.ws:
-                w.wait()
-
-    if dist.get_backend(group) == "nccl" and hasattr(dist, "_coalescing_manager") and tensors:
-        try:
-            with dist._coalescing_manager(group=group, device=tensors[0].device, async_ops=True) as cm:
-                for t in tensors:
-                    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-            return _Works([cm])
-        except Exception:  # noqa: BLE001 -- an older torch without async coalescing: one collective per tensor below
-            pass
-    return _Works([dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True) for t in tensors])
+def _reduce_outside_grads(ex: _Exchange, params: dict, keys: Sequence[str]):
+    """Gradients that reached the leaves `keys` OUTSIDE the rasterizer (scale / opacity / SH regularisers, any extra loss term of
+    backward_fn) where the rasterizer's backward handed autograd nothing for them: whatever ``.grad`` holds now is that part.  It
+    is summed over the ranks by one packed all-reduce of its own.  Every rank runs the same backward_fn, so every rank finds the
+    same set (the usual data-parallel assumption).  Returns ``(work, {key: reduced fp32 gradient})``."""
+    keys = [k for k in keys if params[k].grad is not None]
+    if not keys:
+        return _Works([]), {}
+    flat, views = pack_gradients([params[k].grad.detach().to(torch.float32) for k in keys])
+    return ex.all_reduce(flat), dict(zip(keys, views))
 
 
 class _SlicedGatherHook:
@@ -294,28 +399,22 @@ class _SlicedGatherHook:
     stream goes on with the next slice (0.09 ms of per-splat backward at 1 M splats) and, afterwards, with the SH-gradient
     rebuild of the slices whose colour gradients have arrived."""
 
-    def __init__(self, slices: int, world: int, group, dev):
-        self.slices, self.world, self.group, self.dev = int(slices), world, group, dev
+    def __init__(self, slices: int, ex: _Exchange):
+        self.slices, self.ex = int(slices), ex
         self.buf = None
         self.pending = []     # (lo, hi, gathered [world, hi - lo, 3], gather work, reduce works)
-        self.window = None    # ExchangeStats: opens when the first collective is issued (inside the backward)
 
     def buffers(self, n: int) -> dict:
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.dev)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.ex.dev)
         self.buf = {"means3D": new(n, 3), "scales": new(n, 3), "rotations": new(n, 4), "opacities": new(n, 1), "colors": new(n, 3)}
         return self.buf
 
     def on_slice(self, j: int, lo: int, hi: int) -> None:
-        b = self.buf
-        if self.window is None:
-            self.window = _Window(self.dev)
-            self.window.__enter__()
-        gathered = torch.empty(self.world, hi - lo, 3, dtype=torch.float32, device=self.dev)
-        gw = dist.all_gather_into_tensor(gathered.view(-1), b["colors"][lo:hi].reshape(-1), group=self.group, async_op=True)
-        ExchangeStats.note("all_gather", _nbytes(gathered), self.world)
-        geo = [b[k][lo:hi] for k in ("means3D", "scales", "rotations", "opacities")]
-        rw = _all_reduce_many(geo, self.group)
-        ExchangeStats.note("all_reduce", sum(_nbytes(t) for t in geo), self.world)
+        ex, b = self.ex, self.buf
+        ex.open()   # the exchange window opens with the first collective, inside the backward
+        gathered = torch.empty(ex.world, hi - lo, 3, dtype=torch.float32, device=ex.dev)
+        gw = ex.all_gather(gathered, b["colors"][lo:hi])
+        rw = ex.all_reduce_many([b[k][lo:hi] for k in _GEOMETRIC])
         self.pending.append((lo, hi, gathered, gw, rw))
 
 
@@ -345,75 +444,52 @@ def sh_gather_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_fn
     per splat, same collectives per row).  Loss terms of ``backward_fn`` that reach the parameters OUTSIDE the rasterizer
     (regularisers on scales / opacities / SH, ...) are supported in both forms: their gradients are summed over the ranks by one
     extra packed all-reduce and added (every rank must run the same ``backward_fn``, as in any data-parallel step)."""
-    import math
-    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
-    from . import sh as shmod
-    if world is None:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(rank, world, group, n_views=len(cams))
     V = len(cams)
-    if V % world != 0:
-        raise ValueError("the number of views must be a multiple of the number of ranks")
-    names = ["means3D", "scales", "rotations", "opacities"]
     for p in params.values():
         p.grad = None
     means3D, shs = params["means3D"], params["shs"]
     dev = means3D.device
     n = means3D.shape[0]
+    ex = _Exchange(world, group, dev)
     mine = list(range(rank, V, world))
     slices = GATHER_SLICES if slices is None else int(slices)
-    if _exchange(world) and len(mine) == 1 and slices > 1 and n >= 512:
-        return _sh_gather_step_sliced(params, cams, bg, sh_degree, backward_fn, scaling_modifier, rank, world, group, slices, mine[0])
+    if ex.active and len(mine) == 1 and slices > 1 and n >= 512:
+        return _sh_gather_step_sliced(params, cams, bg, sh_degree, backward_fn, scaling_modifier, ex, slices, mine[0])
     dcol_views = []
-    for slot, vi in enumerate(mine):
-        cam = cams[vi]
-        rs = GaussianRasterizationSettings(
-            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-            tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
-            projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
+    for vi in mine:
         sink = []
-        color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
-            means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-            shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink), scope=True)
+        color, radii, depth, alpha = _render(params, cams[vi], bg, sh_degree, scaling_modifier, shs=shs, color_grad_sink=sink)
         # the rasterizer's backward accumulates the 4 small gradients (incl. the view-direction term in means3D) and hands
         # over the clamp-masked colour gradient instead of writing 192 B/splat of SH gradient
         backward_fn(vi, color, depth, alpha)
         dcol_views.append(sink.pop())
-    for k in names:
-        if params[k].grad is None:
-            params[k].grad = torch.zeros_like(params[k])
+    _fill_missing_grads(params[k] for k in _GEOMETRIC)
     # an SH gradient that did not come through the rasterizer (it hands over colour gradients here): an SH regulariser of
     # backward_fn; summed over the ranks and added to the rebuilt gradient below
     sh_extra = params["shs"].grad
     dcol_local = dcol_views[0][None] if len(dcol_views) == 1 else torch.stack(dcol_views)
     campos_all = _campos_of(cams, dev)
-    if _exchange(world):
+    if ex.active:
         gathered = torch.empty(world, len(mine), n, 3, dtype=torch.float32, device=dev)
         # gathered[r, slot] is view r + slot*world
         order = [r + sl * world for r in range(world) for sl in range(len(mine))]
         dcol_all = gathered.reshape(world * len(mine), n, 3)
         campos_used = campos_all if order == list(range(V)) else campos_all[torch.tensor(order, device=dev)]
-        with _Window(dev):
+        with ex.window():
             # the collectives run in issue order on RCCL's stream: the all-gather first (the SH rebuild needs it), then ONE
             # all-reduce of the four geometric gradients packed back to back (44 B/splat), which overlaps the SH rebuild
-            gather_work = dist.all_gather_into_tensor(gathered.view(-1), dcol_local.view(-1), group=group, async_op=True)
-            ExchangeStats.note("all_gather", _nbytes(gathered), world)
-            flat, views = pack_gradients([params[k].grad for k in names])
-            reduce_work = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True)
-            ExchangeStats.note("all_reduce", _nbytes(flat), world)
-            extra_work = None
-            if sh_extra is not None:
-                sh_extra = sh_extra.detach().to(torch.float32).contiguous()
-                extra_work = dist.all_reduce(sh_extra, op=dist.ReduceOp.SUM, group=group, async_op=True)
-                ExchangeStats.note("all_reduce", _nbytes(sh_extra), world)
+            gather_work = ex.all_gather(gathered, dcol_local)
+            flat, views = pack_gradients([params[k].grad for k in _GEOMETRIC])
+            reduce_work = ex.all_reduce(flat)
+            extra_work, outside = _reduce_outside_grads(ex, params, ["shs"])
+            sh_extra = outside.get("shs")
             gather_work.wait()
-            with _Window(dev, inner=True):
+            with ex.compute():
                 d_shs = shmod.sh_backward(means3D, shs, campos_used, dcol_all, sh_degree, want_shs=True)
             reduce_work.wait()
-            if extra_work is not None:
-                extra_work.wait()
-        for k, v in zip(names, views):
+            extra_work.wait()
+        for k, v in zip(_GEOMETRIC, views):
             params[k].grad = v
     else:
         d_shs = shmod.sh_backward(means3D, shs, campos_all, dcol_local, sh_degree, want_shs=True)
@@ -422,60 +498,36 @@ def sh_gather_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_fn
     params["shs"].grad = d_shs if d_shs.dtype == params["shs"].dtype else d_shs.to(params["shs"].dtype)
 
 
-def _sh_gather_step_sliced(params, cams, bg, sh_degree, backward_fn, scaling_modifier, rank, world, group, slices, vi) -> None:
+def _sh_gather_step_sliced(params, cams, bg, sh_degree, backward_fn, scaling_modifier, ex: _Exchange, slices, vi) -> None:
     """`sh_gather_step` with one view per rank and the exchange started slice by slice from inside the backward."""
-    import math
-    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
-    from . import sh as shmod
-    names = ["means3D", "scales", "rotations", "opacities"]
     means3D, shs = params["means3D"], params["shs"]
-    dev = means3D.device
-    V = len(cams)
-    cam = cams[vi]
-    rs = GaussianRasterizationSettings(
-        image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
-        projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
-    hook = _SlicedGatherHook(slices, world, group, dev)
-    sink = []
-    color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
-        means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-        shs=shs, scales=params["scales"], rotations=params["rotations"], color_grad_sink=sink, slice_hook=hook), scope=True)
-    campos_all = _campos_of(cams, dev)          # gathered[r] is view r (one view per rank: V == world)
+    hook = _SlicedGatherHook(slices, ex)
+    color, radii, depth, alpha = _render(params, cams[vi], bg, sh_degree, scaling_modifier, shs=shs, color_grad_sink=[],
+                                         slice_hook=hook)
+    campos_all = _campos_of(cams, ex.dev)       # gathered[r] is view r (one view per rank: V == world)
     d_shs = torch.empty_like(shs, dtype=torch.float32)
     backward_fn(vi, color, depth, alpha)    # blend, then per slice: per-splat backward + hook.on_slice (collectives issued)
     if hook.buf is None:                    # nothing reached the rasterizer's backward (zero upstream gradients)
         hook.buffers(means3D.shape[0])
         for t in hook.buf.values():
             t.zero_()
-        from .rasterizer import slice_ranges
         for j, (lo, hi) in enumerate(slice_ranges(means3D.shape[0], slices)):
             hook.on_slice(j, lo, hi)
-    # Gradients that reached the leaves OUTSIDE the rasterizer (scale / opacity regularisers, any extra loss term of
-    # backward_fn): the rasterizer's backward handed autograd nothing for these inputs (its part sits in the hook's buffers and is
-    # already on the wire), so whatever `.grad` holds now is that extra part.  It is summed over the ranks by one packed
-    # all-reduce of its own and added below -- the unsliced path gets the same result through autograd's accumulation.  Every
-    # rank runs the same backward_fn, so every rank finds the same set of extras (the usual data-parallel assumption).
-    extra_names = [k for k in names + ["shs"] if params[k].grad is not None]
-    extra_work, extra_views = None, []
-    if extra_names:
-        flat, extra_views = pack_gradients([params[k].grad.detach().to(torch.float32) for k in extra_names])
-        extra_work = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True)
-        ExchangeStats.note("all_reduce", _nbytes(flat), world)
+    # the rasterizer's part of every gradient sits in the hook's buffers and is already on the wire: what `.grad` holds now came
+    # from outside it, and is added below -- the unsliced path gets the same result through autograd's accumulation
+    extra_work, outside = _reduce_outside_grads(ex, params, _GEOMETRIC + ["shs"])
     m_det, s_det = means3D.detach(), shs.detach()
     for lo, hi, gathered, gw, rw in hook.pending:
         gw.wait()
-        with _Window(dev, inner=True):
+        with ex.compute():
             shmod.sh_backward(m_det[lo:hi], s_det[lo:hi], campos_all, gathered, sh_degree, want_shs=True, out=d_shs[lo:hi])
     for _, _, _, _, rw in hook.pending:
         rw.wait()
-    if extra_work is not None:
-        extra_work.wait()
-    if hook.window is not None:
-        hook.window.__exit__(None, None, None)
-    out = {k: hook.buf[k].view(params[k].shape) for k in names}
+    extra_work.wait()
+    ex.close()
+    out = {k: hook.buf[k].view(params[k].shape) for k in _GEOMETRIC}
     out["shs"] = d_shs
-    for k, v in zip(extra_names, extra_views):
+    for k, v in outside.items():
         out[k] += v.view(out[k].shape)
     for k, g in out.items():
         # the kernels compute in fp32; a parameter of another dtype gets its gradient in its own (as the unsliced path does)
@@ -500,18 +552,6 @@ def _campos_of(cams: Sequence, dev) -> torch.Tensor:
     _CAMPOS_CACHE[key] = (out, versions, src)
     return out
 
-
-def _all_to_all(out: torch.Tensor, inp: torch.Tensor, group=None) -> None:
-    """Equal-split all-to-all of contiguous buffers [world, ...].  RCCL moves device buffers directly; gloo (the CPU-backend
-    tests) only implements it for host tensors, so it is staged through the host there."""
-    if dist.get_backend(group) == "gloo" and inp.is_cuda:
-        o = torch.empty(out.shape, dtype=out.dtype)
-        dist.all_to_all_single(o, inp.cpu(), group=group)
-        out.copy_(o)
-    else:
-        dist.all_to_all_single(out, inp, group=group)
-
-
 def sh_sharded_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_fn: Callable, *, scaling_modifier: float = 1.0,
                     rank: int = None, world: int = None, group=None):
     """View-parallel step with the SH coefficients SHARDED by splat range (ZeRO-style for the 192 B/splat tensor that is 80 %
@@ -531,23 +571,15 @@ def sh_sharded_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_f
     owned shard and is returned as ``(lo, hi, d_shs[hi - lo, K, 3])`` -- what a sharded optimizer consumes; ``shs.grad`` is
     left ``None``.  ``params["shs"]`` may be the full tensor (only rows lo:hi are read) -- ``backward_fn`` as in
     `sh_gather_step`."""
-    import math
-    from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
-    from . import sh as shmod
-    if world is None:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(rank, world, group, n_views=len(cams))
     V = len(cams)
-    if V % world != 0:
-        raise ValueError("the number of views must be a multiple of the number of ranks")
     k = V // world
-    names = ["means3D", "scales", "rotations", "opacities"]
     for p in params.values():
         p.grad = None
     means3D, shs = params["means3D"], params["shs"]
     dev = means3D.device
     n = means3D.shape[0]
+    ex = _Exchange(world, group, dev)
     shard = (n + world - 1) // world
     lo, hi = min(n, rank * shard), min(n, (rank + 1) * shard)
     n_own = hi - lo
@@ -556,54 +588,46 @@ def sh_sharded_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_f
     campos = _campos_of([cams[vi] for vi in order], dev)
     m_own, sh_own = means3D.detach()[lo:hi], shs.detach()[lo:hi]
 
+    def exchanged(send):
+        """what the all-to-all of `send` [world, k, shard, 3] delivers here (one exchange window each)"""
+        if not ex.active:
+            return send
+        recv = torch.empty_like(send)
+        with ex.window():
+            ex.all_to_all(recv, send).wait()
+        return recv
+
+    def buffer(padded: bool):
+        """communication buffer [world, k, shard, 3]; rows that nothing writes (the pad of a short last shard) must be zero"""
+        return (torch.zeros if padded else torch.empty)(world, k, shard, 3, dtype=torch.float32, device=dev)
+
     # 1. colours of my shard for every view -> the ranks that render them
-    send = torch.zeros(world, k, shard, 3, dtype=torch.float32, device=dev) if n_own < shard else \
-        torch.empty(world, k, shard, 3, dtype=torch.float32, device=dev)
+    send = buffer(padded=n_own < shard)
     keep = None
     if n_own == shard:   # the usual case: the kernel writes straight into the communication buffer
         _, keep = shmod.sh_forward_views(m_own, sh_own, campos, sh_degree, out=send.view(V, shard, 3))
     elif n_own > 0:      # short last shard: pad rows stay zero
         col_own, keep = shmod.sh_forward_views(m_own, sh_own, campos, sh_degree)     # [V, n_own, 3] each
         send.view(V, shard, 3)[:, :n_own].copy_(col_own)
-    if _exchange(world):
-        recv = torch.empty_like(send)
-        with _Window(dev):
-            _all_to_all(recv, send, group)
-            ExchangeStats.note("all_to_all", _nbytes(send), world)
-    else:
-        recv = send
+    recv = exchanged(send)
     # recv[s, slot] = colours of shard s for my view `slot`
 
     # 2. my views on the precomputed-colour path
-    dcol_send = torch.zeros(world, k, shard, 3, dtype=torch.float32, device=dev) if world * shard != n else \
-        torch.empty(world, k, shard, 3, dtype=torch.float32, device=dev)
+    dcol_send = buffer(padded=world * shard != n)
     for slot in range(k):
         vi = rank + slot * world
-        cam = cams[vi]
         cols = recv[:, slot].reshape(world * shard, 3)[:n].contiguous().requires_grad_(True)
-        rs = GaussianRasterizationSettings(
-            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
-            tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
-            projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=False)
-        color, radii, depth, alpha = redeemed(lambda: GaussianRasterizer(rs).forward_ex(
-            means3D=means3D, means2D=torch.zeros_like(means3D, requires_grad=True), opacities=params["opacities"],
-            colors_precomp=cols, scales=params["scales"], rotations=params["rotations"]), scope=True)
+        color, radii, depth, alpha = _render(params, cams[vi], bg, sh_degree, scaling_modifier, colors_precomp=cols)
         backward_fn(vi, color, depth, alpha)
         g = cols.grad if cols.grad is not None else torch.zeros(n, 3, dtype=torch.float32, device=dev)
-        dcol_send[:, slot].reshape(world * shard, 3)[:n].copy_(g) if k == 1 else \
+        if k == 1:
+            dcol_send[:, slot].reshape(world * shard, 3)[:n].copy_(g)
+        else:
             dcol_send[:, slot].copy_(torch.nn.functional.pad(g, (0, 0, 0, world * shard - n)).view(world, shard, 3))
-    for name in names:
-        if params[name].grad is None:
-            params[name].grad = torch.zeros_like(params[name])
+    _fill_missing_grads(params[name] for name in _GEOMETRIC)
 
     # 3. colour gradients back to the shard owners; SH gradient (and the view-direction term) of my shard from all views
-    if _exchange(world):
-        dcol_recv = torch.empty_like(dcol_send)
-        with _Window(dev):
-            _all_to_all(dcol_recv, dcol_send, group)
-            ExchangeStats.note("all_to_all", _nbytes(dcol_send), world)
-    else:
-        dcol_recv = dcol_send
+    dcol_recv = exchanged(dcol_send)
     d_shs = None
     if n_own > 0:
         dcol = dcol_recv.view(V, shard, 3)[:, :n_own] * keep                          # clamp mask of each view
@@ -613,14 +637,31 @@ def sh_sharded_step(params: dict, cams: Sequence, bg, sh_degree: int, backward_f
         params["means3D"].grad[lo:hi] += d_means
 
     # 4. the geometric gradients of all views
-    if _exchange(world):
-        with _Window(dev):
-            flat, views = pack_gradients([params[name].grad for name in names])
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-            ExchangeStats.note("all_reduce", _nbytes(flat), world)
-        for name, v_ in zip(names, views):
+    if ex.active:
+        with ex.window():
+            flat, views = pack_gradients([params[name].grad for name in _GEOMETRIC])
+            ex.all_reduce(flat).wait()
+        for name, v_ in zip(_GEOMETRIC, views):
             params[name].grad = v_
     return lo, hi, d_shs
+
+
+def _backward_local_share(losses_of_my_views: Callable, n_views: int, like: torch.Tensor) -> torch.Tensor:
+    """Back-propagates this rank's contribution to the mean loss over all `n_views` views -- the sum of the losses of its own
+    views / n_views; summed (not averaged) across ranks afterwards -- and returns it detached; a zero like `like` if the rank
+    rendered nothing.  The forwards of the rank's views are enqueued back to back (none waits once its camera is known)."""
+    def total_loss():
+        tot = None
+        for l in losses_of_my_views():
+            tot = l if tot is None else tot + l
+        return tot
+
+    total = redeemed(total_loss, scope=True)
+    if total is None:
+        return torch.zeros((), device=like.device, dtype=like.dtype)
+    share = total / n_views
+    share.backward()
+    return share.detach()
 
 
 def view_parallel_step(params: List[torch.Tensor], views: Sequence, render_loss: Callable, *, rank: int = None,
@@ -629,45 +670,21 @@ def view_parallel_step(params: List[torch.Tensor], views: Sequence, render_loss:
     parameters.  After the call every rank holds, in ``p.grad``, the gradient of
     ``mean_{v in views} render_loss(v)`` -- exactly what the single-process loop of the reference
     computes -- and the returned tensor is that mean loss (all-reduced)."""
-    if world is None:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(rank, world, group)
     for p in params:
         p.grad = None
     mine = shard_views(views, rank, world)
-
-    def losses():
-        tot = None
-        for v in mine:   # the forwards of the rank's views are enqueued back to back (none waits once its camera is known)
-            l = render_loss(v)
-            tot = l if tot is None else tot + l
-        return tot
-
-    total = redeemed(losses, scope=True)
-    n_views = len(views)
-    if total is not None:
-        # local contribution to the global mean; summed (not averaged) across ranks below
-        (total / n_views).backward()
-        local = (total / n_views).detach()
-    else:
-        local = torch.zeros((), device=params[0].device, dtype=params[0].dtype)
-    if _exchange(world):
-        for p in params:
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-        big = sorted((p for p in params if p.grad.numel() * p.grad.element_size() >= PACK_BELOW_BYTES or p.grad.dtype != local.dtype),
-                     key=lambda q: -q.numel())
-        small = [p for p in params if not any(p is b for b in big)]
-        works = [dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=group, async_op=True) for p in big]
-        # the small gradients and the scalar loss share one buffer and one collective
-        flat, views = pack_gradients([p.grad for p in small] + [local.reshape(1)])
-        works.append(dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group, async_op=True))
-        for w in works:
-            w.wait()
-        for p, v in zip(small, views):
-            p.grad = v
-        local = views[-1].reshape(())
+    local = _backward_local_share(lambda: (render_loss(v) for v in mine), len(views), params[0])
+    ex = _Exchange(world, group, local.device)
+    if ex.active:
+        _fill_missing_grads(params)
+        with ex.window():
+            # a gradient of another dtype than the loss goes alone; the small ones and the scalar loss share one buffer and
+            # one collective
+            works, _, packed = _issue_gradient_reduce(ex, params, dist.ReduceOp.SUM, alone=lambda p: p.grad.dtype != local.dtype,
+                                                      extra=local)
+            _land(works, packed)
+        local = packed[0][1][-1].reshape(())   # one buffer (every packed gradient is of the loss's dtype), the loss last
     return local
 
 
@@ -687,10 +704,7 @@ def field_view_parallel_step(compute_splats: Callable[[], dict], views: Sequence
     ``render_loss(splats, view) -> scalar`` renders one view from the given attribute tensors.  Gradients accumulate into the
     ``.grad`` of whatever leaves ``compute_splats`` used (the caller zeroes them, as with a plain backward).  Returns the mean
     loss over all views."""
-    if world is None:
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    rank, world = _rank_world(rank, world, group)
     outputs = compute_splats()
     keys = [k for k, v in outputs.items() if torch.is_tensor(v) and v.requires_grad]
     # detached copies are the "parameters" of the rendering part of the step
@@ -698,26 +712,14 @@ def field_view_parallel_step(compute_splats: Callable[[], dict], views: Sequence
     for k in keys:
         splats[k] = outputs[k].detach().requires_grad_(True)
     mine = shard_views(views, rank, world)
-
-    def losses():
-        tot = None
-        for v in mine:
-            l = render_loss(splats, v)
-            tot = l if tot is None else tot + l
-        return tot
-
-    total = redeemed(losses, scope=True)
-    n_views = len(views)
     ref = outputs[keys[0]]
-    if total is not None:
-        (total / n_views).backward()
-        local = (total / n_views).detach().to(ref.dtype)
-    else:
-        local = torch.zeros((), device=ref.device, dtype=ref.dtype)
+    local = _backward_local_share(lambda: (render_loss(splats, v) for v in mine), len(views), ref).to(ref.dtype)
     grads = [splats[k].grad if splats[k].grad is not None else torch.zeros_like(splats[k]) for k in keys]
-    if _exchange(world):
-        flat, views_ = pack_gradients([g.to(ref.dtype) for g in grads] + [local.reshape(1)])
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    ex = _Exchange(world, group, ref.device)
+    if ex.active:
+        with ex.window():
+            flat, views_ = pack_gradients([g.to(ref.dtype) for g in grads] + [local.reshape(1)])
+            ex.all_reduce(flat).wait()
         grads, local = views_[:-1], views_[-1].reshape(())
     torch.autograd.backward([outputs[k] for k in keys], [g.to(outputs[k].dtype) for k, g in zip(keys, grads)])
     return local

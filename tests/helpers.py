@@ -2,14 +2,59 @@
 (-> C ABI), and tolerance-aware comparison against the oracle."""
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
+import torch.distributed as dist
 
 from oracle import torch_oracle as O
 from splatfields_amd.synthetic import make_camera, make_splats, make_upstream_grads
 
 GRAD_NAMES_SH = ["means3D", "scales", "rotations", "opacities", "shs", "means2D"]
+
+
+class CollectiveLog(list):
+    """What `record_collectives` yields: one `(collective, reduce op, dtype, element count)` per call, in issue order (the
+    count is that of the reduced tensor, of the gathered OUTPUT of an all-gather, of the INPUT of an all-to-all);
+    `.tensors[i]` is that tensor of call i."""
+
+    def __init__(self):
+        super().__init__()
+        self.tensors = []
+
+
+@contextlib.contextmanager
+def record_collectives():
+    """Wraps the `torch.distributed` entry points splatfields_amd.view_parallel issues its collectives through and logs every
+    call; the calls themselves go through unchanged."""
+    log = CollectiveLog()
+    ops = {dist.ReduceOp.SUM: "SUM", dist.ReduceOp.AVG: "AVG"}
+    real = {k: getattr(dist, k) for k in ("all_reduce", "all_gather_into_tensor", "all_to_all_single")}
+
+    def all_reduce(tensor, op=dist.ReduceOp.SUM, *a, **kw):
+        log.append(("all_reduce", ops[op], tensor.dtype, tensor.numel()))
+        log.tensors.append(tensor)
+        return real["all_reduce"](tensor, op, *a, **kw)
+
+    def all_gather_into_tensor(output_tensor, input_tensor, *a, **kw):
+        log.append(("all_gather", None, output_tensor.dtype, output_tensor.numel()))
+        log.tensors.append(output_tensor)
+        return real["all_gather_into_tensor"](output_tensor, input_tensor, *a, **kw)
+
+    def all_to_all_single(output, input, *a, **kw):
+        log.append(("all_to_all", None, input.dtype, input.numel()))
+        log.tensors.append(input)
+        return real["all_to_all_single"](output, input, *a, **kw)
+
+    wrapped = {"all_reduce": all_reduce, "all_gather_into_tensor": all_gather_into_tensor, "all_to_all_single": all_to_all_single}
+    for k, f in wrapped.items():
+        setattr(dist, k, f)
+    try:
+        yield log
+    finally:
+        for k, f in real.items():
+            setattr(dist, k, f)
 
 
 def make_scene(n, width, height, *, seed=1234, view=1, sh_degree=3, bg=(1.0, 1.0, 1.0), mean_scale=None,

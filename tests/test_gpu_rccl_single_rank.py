@@ -12,10 +12,13 @@ import torch
 import torch.distributed as dist
 
 from splatfields_amd.synthetic import make_camera, make_splats, make_upstream_grads
+from tests.helpers import record_collectives
 
 pytestmark = pytest.mark.gpu
 N, W, H, V, DEG = 5000, 144, 112, 2, 3
 NAMES = ["means3D", "scales", "rotations", "opacities", "shs"]
+F32 = torch.float32
+GEO = N * (3 + 3 + 4 + 1)   # elements of the four geometric gradients packed back to back
 
 
 @pytest.fixture(scope="module")
@@ -64,7 +67,9 @@ def test_every_exchange_scheme_runs_on_rccl(hip_device, rccl_group):
 
     # 1. all-gather of colour gradients + packed SUM all-reduce
     p = {k: sp[k].clone().requires_grad_(True) for k in NAMES}
-    vp.sh_gather_step(p, cams, bg, DEG, bwd, rank=0, world=1)
+    with record_collectives() as log:
+        vp.sh_gather_step(p, cams, bg, DEG, bwd, rank=0, world=1)
+    assert list(log) == [("all_gather", None, F32, V * N * 3), ("all_reduce", "SUM", F32, GEO)]
     for k in NAMES:
         close(p[k].grad, ref[k], ("gather", k))
 
@@ -73,15 +78,26 @@ def test_every_exchange_scheme_runs_on_rccl(hip_device, rccl_group):
     ref1 = _reference(sp, cams[:1], gi, gd, ga, dev)
     for slices in (1, 4):
         p = {k: sp[k].clone().requires_grad_(True) for k in NAMES}
-        vp.sh_gather_step(p, cams[:1], bg, DEG, lambda vi, c, d, a: torch.autograd.backward((c, d, a), (gi, gd, ga)), rank=0, world=1,
-                          slices=slices)
+        with record_collectives() as log:
+            vp.sh_gather_step(p, cams[:1], bg, DEG, lambda vi, c, d, a: torch.autograd.backward((c, d, a), (gi, gd, ga)), rank=0,
+                              world=1, slices=slices)
         torch.cuda.synchronize()
+        if slices == 1:
+            assert list(log) == [("all_gather", None, F32, N * 3), ("all_reduce", "SUM", F32, GEO)]
+        else:   # range by range: the all-gather of its colour gradients, then its rows of the four geometric gradients, grouped
+            expected = []
+            for lo, hi in ((0, 1280), (1280, 2560), (2560, 3840), (3840, N)):
+                expected.append(("all_gather", None, F32, (hi - lo) * 3))
+                expected += [("all_reduce", "SUM", F32, (hi - lo) * c) for c in (3, 3, 4, 1)]
+            assert list(log) == expected
         for k in NAMES:
             close(p[k].grad, ref1[k], ("gather sliced", slices, k))
 
     # 2. SH sharded by splat range: two device all-to-all + packed all-reduce
     p = {k: sp[k].clone().requires_grad_(True) for k in NAMES}
-    lo, hi, d_shs = vp.sh_sharded_step(p, cams, bg, DEG, bwd, rank=0, world=1)
+    with record_collectives() as log:
+        lo, hi, d_shs = vp.sh_sharded_step(p, cams, bg, DEG, bwd, rank=0, world=1)
+    assert list(log) == [("all_to_all", None, F32, V * N * 3), ("all_to_all", None, F32, V * N * 3), ("all_reduce", "SUM", F32, GEO)]
     assert (lo, hi) == (0, N)
     close(d_shs, ref["shs"], ("shard", "shs"))
     for k in NAMES[:4]:
@@ -103,9 +119,11 @@ def test_every_exchange_scheme_runs_on_rccl(hip_device, rccl_group):
         old = vp.PACK_BELOW_BYTES
         vp.PACK_BELOW_BYTES = 200_000   # shs.grad (5000 x 16 x 3 x 4 B) goes alone, the rest packed
         try:
-            vp.allreduce_gradients(list(p.values()), 1, sh_param=p["shs"], sh_active_coeffs=active)
+            with record_collectives() as log:
+                vp.allreduce_gradients(list(p.values()), 1, sh_param=p["shs"], sh_active_coeffs=active)
         finally:
             vp.PACK_BELOW_BYTES = old
+        assert list(log) == [("all_reduce", "AVG", F32, N * (16 if active is None else active) * 3), ("all_reduce", "AVG", F32, GEO)]
         torch.cuda.synchronize()
         for k in NAMES:
             close(p[k].grad, before[k], ("allreduce", k, active))   # mean over one rank
@@ -126,7 +144,9 @@ def test_every_exchange_scheme_runs_on_rccl(hip_device, rccl_group):
             rotations=params[2])
         return (color * gi).sum() + (depth * gd).sum() + (alpha * ga).sum()
 
-    loss = vp.view_parallel_step(params, cams, render_loss, rank=0, world=1)
+    with record_collectives() as log:
+        loss = vp.view_parallel_step(params, cams, render_loss, rank=0, world=1)
+    assert list(log) == [("all_reduce", "SUM", F32, GEO + N * 16 * 3 + 1)]   # everything is small: one buffer, the loss last
     assert torch.isfinite(loss)
     for t, k in zip(params, NAMES):
         close(t.grad, ref[k], ("view_parallel_step", k))

@@ -180,3 +180,22 @@ def test_redeemed_renders_once_more_after_an_overflow(monkeypatch):
     finally:
         rz.set_async_forward(prev)
         keep.clear()
+
+
+def test_settings_from_camera_is_the_mapping_render_builds():
+    """`settings_from_camera` is the one product-side mapping from a reference camera object to the settings tuple: field for
+    field what `render.render` / `render_model` wrote out by hand (gaussian_renderer/__init__.py:59-72)."""
+    import math
+    import torch
+    cam = SimpleNamespace(image_height=torch.tensor(96), image_width=160.0, FoVx=0.9, FoVy=0.6, world_view_transform=torch.eye(4),
+                          full_proj_transform=torch.ones(4, 4), camera_center=torch.tensor([1.0, 2.0, 3.0]))
+    bg = torch.ones(3)
+    for kw, scale, debug in (({}, 1.0, False), ({"scale_modifier": 0.5, "debug": 1}, 0.5, True)):
+        rs = rz.settings_from_camera(cam, bg, 2, **kw)
+        by_hand = rz.GaussianRasterizationSettings(
+            image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+            tanfovy=math.tan(cam.FoVy * 0.5), bg=bg, scale_modifier=scale, viewmatrix=cam.world_view_transform,
+            projmatrix=cam.full_proj_transform, sh_degree=2, campos=cam.camera_center, prefiltered=False, debug=debug)
+        assert rs._fields == by_hand._fields
+        for name, a, b in zip(rs._fields, rs, by_hand):
+            assert (a is b) if torch.is_tensor(b) else (type(a) is type(b) and a == b), name
