@@ -27,6 +27,9 @@
  *   sr_densification_stats
  *        <- reference train.py:280-286 and scene/gaussian_model.py:427-438 (`add_densification_stats`): the
  *           consumers of `radii` and `viewspace_points.grad`, fused into one kernel.
+ *   sr_photometric_forward / sr_photometric_backward
+ *        <- reference train.py:183-193 with utils/loss_utils.py:18 (`l1_loss`) and :33-76 (`ssim`): the loss between
+ *           `render()` and `loss.backward()`, as one kernel each way plus a fixed-order reduction.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -229,6 +232,32 @@ int sr_mark_visible(int n_splats, const float* means3D, const float* viewmatrix,
  * Any of the three outputs may be NULL. */
 int sr_densification_stats(int n_splats, const float* dL_dmeans2D, const int* radii, float* grad_accum, float* denom,
                            float* max_radii2D, void* hip_stream);
+
+/* The photometric loss of a training step (reference train.py:183-193, utils/loss_utils.py:18 and :33-76), fused:
+ *   l1 = mean|image - gt|;   ssim[b] = mean over item b of the structural similarity map (11-tap Gaussian window, sigma 1.5,
+ *   float32 taps, zero padding of 5, C1 = 0.01^2, C2 = 0.03^2);   mask_l1 = mean|clamp(alpha, 0, 1) - gt_mask|;
+ *   loss = (1 - lambda_dssim) l1 + lambda_dssim (1 - mean_b ssim[b]) + lambda_mask mask_l1.
+ * image, gt: [batch, channels, height, width] float32; alpha, gt_mask: [batch, height, width] (both or neither).  Any size
+ * >= 1: a plane smaller than the window is an ordinary case.  All four results are written to device memory (ssim: `batch`
+ * floats); nothing is read back and nothing waits: both calls only enqueue on `hip_stream`.
+ * `workspace`: sr_loss_workspace_bytes(batch * channels, height, width) bytes, the per-workgroup partial sums, which one
+ * workgroup adds in a fixed order (no floating-point atomics: results are bit-identical from call to call).
+ * `maps`: NULL, or sr_loss_maps_bytes(batch * channels, height, width) bytes that receive the three per-pixel derivative
+ * maps sr_photometric_backward reads.  `ssim` may be NULL when lambda_dssim = 0 and maps = NULL: the window is then skipped.
+ *
+ * sr_photometric_backward writes, with g = upstream[upstream_per_item ? b : 0] read on the device,
+ *   dL_dimage = g (w_l1 d l1/d image + w_ssim d ssim/d image),   dL_dalpha (may be NULL) = g w_mask d mask_l1/d alpha,
+ * where `ssim` is the mean over all items, or item b's own with upstream_per_item.  The loss above is w_l1 = 1 - lambda_dssim,
+ * w_ssim = -lambda_dssim, w_mask = lambda_mask.  sign(0) = 0; clamp passes the gradient for 0 <= alpha <= 1.
+ * `maps` may be NULL when w_ssim = 0. */
+size_t sr_loss_workspace_bytes(int planes, int height, int width);
+size_t sr_loss_maps_bytes(int planes, int height, int width);
+int sr_photometric_forward(int batch, int channels, int height, int width, const float* image, const float* gt,
+                           const float* alpha, const float* gt_mask, float lambda_dssim, float lambda_mask, void* workspace,
+                           float* maps, float* loss, float* l1, float* ssim, float* mask_l1, void* hip_stream);
+int sr_photometric_backward(int batch, int channels, int height, int width, const float* image, const float* gt,
+                            const float* alpha, const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask,
+                            const float* upstream, int upstream_per_item, float* dL_dimage, float* dL_dalpha, void* hip_stream);
 
 /* SH colour evaluation as a stand-alone stage (the SH part of the forward preprocess; reference utils/sh_utils.py:57-112,
  * extract_geo.py:40-44): colors[N,3] = max(sum_k basis_k(dir) shs[k] + 0.5, 0), clamped[N] bit c set where channel c was

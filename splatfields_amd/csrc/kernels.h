@@ -77,6 +77,17 @@ size_t triplane_backward_workspace(int N, int C, int H, int W);
 size_t knn_workspace_bytes(int n);
 void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream_t st);
 
+// loss.hip
+bool loss_shape_ok(int batch, int channels, int H, int W);
+size_t loss_workspace_bytes(int planes, int H, int W);
+size_t loss_maps_bytes(int planes, int H, int W);
+void launch_loss_forward(int batch, int channels, int H, int W, const float* image, const float* gt, const float* alpha,
+                         const float* gt_mask, float lambda_dssim, float lambda_mask, void* workspace, float* maps, float* loss,
+                         float* l1, float* ssim, float* mask_l1, hipStream_t st);
+void launch_loss_backward(int batch, int channels, int H, int W, const float* image, const float* gt, const float* alpha,
+                          const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask, const float* g, int g_per_item,
+                          float* dL_dimage, float* dL_dalpha, hipStream_t st);
+
 // sh.hip
 void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
                        unsigned char* clamped, hipStream_t st);
