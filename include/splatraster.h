@@ -30,6 +30,9 @@
  *   sr_photometric_forward / sr_photometric_backward
  *        <- reference train.py:183-193 with utils/loss_utils.py:18 (`l1_loss`) and :33-76 (`ssim`): the loss between
  *           `render()` and `loss.backward()`, as one kernel each way plus a fixed-order reduction.
+ *   sr_knn_graph + sr_moran_forward / sr_moran_backward, sr_moran_weights / sr_moran_weights_backward
+ *        <- reference extract_geo.py:100-143 (`query_nn`, `morans_measure`, `morans_loss`) as train.py:203-215 calls them:
+ *           [EXT] pytorch3d.ops.knn.knn_points and the [N,F,K,K] temporaries of the Moran's I regulariser.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -284,6 +287,47 @@ int sr_sh_backward(int n_splats, int sh_coeffs, int sh_degree, int n_views, cons
  * scene/gaussian_model.py:105.  `workspace` holds sr_knn_workspace_bytes(n) bytes of device memory. */
 size_t sr_knn_workspace_bytes(int n_points);
 int sr_knn3_mean_dist2(int n_points, const float* points, float* mean_dist2, void* workspace, void* hip_stream);
+
+/* The K nearest points of every point, itself included (exact; 2 <= k <= SR_KNN_MAX_K <= n_points), nearest first, ordered
+ * by (squared distance, index): nn_ix [n,k] int32.  Replaces [EXT] pytorch3d.ops.knn.knn_points(pts, pts, K) of reference
+ * extract_geo.py:101-103.  Also written, for the kernels below: order [n] (the points in grid-cell order, by index inside a
+ * cell), and the reverse adjacency rev_start [n+1] / rev_edges [n k] -- per point the edges p * k + slot that end there, in
+ * ascending order.  `workspace`: sr_knn_graph_workspace_bytes(n, k) bytes (0 = sizes out of range). */
+#define SR_KNN_MAX_K 8
+size_t sr_knn_graph_workspace_bytes(int n_points, int k);
+int sr_knn_graph(int n_points, int k, const float* points, int* nn_ix, unsigned* order, unsigned* rev_start, unsigned* rev_edges,
+                 void* workspace, void* hip_stream);
+
+/* Moran's I regulariser (reference extract_geo.py:100-143 as called by train.py:203-215).  Item p has k rows r_a and a k x k
+ * matrix c: with `points` [rows,3], r_a = nn_ix[p,a] and c_ab = 1 / |q_a - q_b| where that distance exceeds eps, eps elsewhere
+ * and on the diagonal; with `weight` [n,k,k] (exactly one of the two is given), c = weight[p] and r_a = nn_ix ? nn_ix[p,a] :
+ * p k + a.  For each of the n_tensors (1 .. SR_MORAN_MAX_TENSORS) feature tensors features[t] [rows, widths[t]]:
+ *   m[p,f] = k sum_ab c_ab x_a x_b / (sum_ab c_ab (sum_a x_a^2 + 1e-4)),  x_a = features[t][r_a, f],
+ *   mean_t = mean_{p,f} m,  term_t = 1 - clamp(mean_t, 0, 1).
+ * sr_moran_forward writes out [1 + 2 n_tensors] = sum_t term_t | term_t | mean_t.  `workspace`: sr_moran_workspace_bytes(n,
+ * n_tensors), per-workgroup partial sums added in a fixed order.  `order` (may be NULL) is the order the items are walked in.
+ * sr_moran_backward reads `out` and the upstream gradient of out[0] on the device and writes, for every non-NULL
+ * dL_dfeatures[t], the gradient of features[t] (zeros where the clamp of term t is shut); dL_dpoints [rows,3] (points given,
+ * may be NULL) or dL_dweight [n,k,k] (weight given, may be NULL).  Contributions are stored per edge in `edges`
+ * (sr_moran_edges_bytes(n, k, sum of the widths whose dL_dfeatures[t] is not NULL)) and added per row in edge order through rev_start / rev_edges (required with
+ * nn_ix; without nn_ix every row has one edge): no floating-point atomics, identical bits from call to call.
+ * sr_moran_weights writes `query_nn`'s weights [n,k,k] = c / max(sum c, 1e-5); sr_moran_weights_backward its gradient to
+ * the points (`edges`: sr_moran_edges_bytes(n, k, 0)).  With out = NULL sr_moran_backward differentiates sum_t mean_t instead
+ * (`morans_measure`: no clamp).  No entry point waits for the device. */
+#define SR_MORAN_MAX_TENSORS 8
+size_t sr_moran_workspace_bytes(int n_items, int n_tensors);
+size_t sr_moran_edges_bytes(int n_items, int k, int channels);
+int sr_moran_forward(int n_items, int k, float eps, const float* points, const float* weight, const int* nn_ix,
+                     const unsigned* order, int n_tensors, const float* const* features, const int* widths, void* workspace,
+                     float* out, void* hip_stream);
+int sr_moran_backward(int n_items, int k, float eps, const float* points, const float* weight, const int* nn_ix,
+                      const unsigned* order, const unsigned* rev_start, const unsigned* rev_edges, int n_tensors,
+                      const float* const* features, const int* widths, const float* out, const float* upstream, void* edges,
+                      float* const* dL_dfeatures, float* dL_dpoints, float* dL_dweight, void* hip_stream);
+int sr_moran_weights(int n_points, int k, float eps, const float* points, const int* nn_ix, float* weights, void* hip_stream);
+int sr_moran_weights_backward(int n_points, int k, float eps, const float* points, const int* nn_ix, const unsigned* rev_start,
+                              const unsigned* rev_edges, const float* dL_dweights, void* edges, float* dL_dpoints,
+                              void* hip_stream);
 
 /* Densification / pruning of the splat set on the device: reference scene/gaussian_model.py:411-425 (`densify_and_prune`) with
  * :394-409 (`densify_and_clone`), :355-380 (`densify_and_split`, N = 2), :306-353 (`densification_postfix`) and :272-304

@@ -2,3 +2,4 @@
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 from .render import render  # noqa: F401
 from .losses import l1_loss, photometric_loss, ssim  # noqa: F401
+from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401

@@ -61,6 +61,7 @@ class SrResFieldJob(C.Structure):
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 MLP_MAX_GRAD_JOBS, MLP_MAX_GRAD_TASKS = 16, 128
 MLP_MAX_PACK_JOBS = 32
+MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatraster.h: SR_MORAN_MAX_TENSORS, SR_KNN_MAX_K
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
 
 
@@ -100,6 +101,18 @@ SYMBOLS = {
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "sr_knn_workspace_bytes": (C.c_size_t, [C.c_int]),
     "sr_knn3_mean_dist2": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_knn_graph_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sr_knn_graph": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_moran_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sr_moran_edges_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sr_moran_forward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_moran_backward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_moran_weights": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_moran_weights_backward": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sr_loss_maps_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sr_photometric_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,

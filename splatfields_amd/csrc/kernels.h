@@ -76,6 +76,31 @@ size_t triplane_backward_workspace(int N, int C, int H, int W);
 // knn.hip
 size_t knn_workspace_bytes(int n);
 void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream_t st);
+constexpr int kKnnMinK = 2, kKnnMaxK = 8;
+size_t knn_graph_workspace_bytes(int n, int k);   // 0 for sizes out of range
+void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* order, uint32_t* rev_start, uint32_t* rev_edges, void* workspace,
+                      hipStream_t st);
+
+// moran.hip
+constexpr int kMoranMaxTensors = SR_MORAN_MAX_TENSORS;
+// the feature tensors of one call: x[t] is [rows, width[t]]; dx[t] (backward) may be NULL; offset[] are the running widths,
+// edge_offset[] the running widths of the tensors with a dx: only those have columns in the per-edge buffer
+struct MoranTensors {
+    int count, channels, edge_channels;
+    const float* x[kMoranMaxTensors]; float* dx[kMoranMaxTensors];
+    int width[kMoranMaxTensors], offset[kMoranMaxTensors], edge_offset[kMoranMaxTensors];
+};
+// where the K x K spatial weights of item p come from: `points` (c_ab from the distances of the K gathered positions) or
+// `weight` [n, K, K] given; nn_ix NULL: item p's rows are p K .. p K + K - 1; order NULL: items in index order
+struct MoranSource { int n, k; float eps; const float* points; const float* weight; const int* nn_ix; const uint32_t* order; };
+size_t moran_workspace_bytes(int n, int n_tensors);
+size_t moran_edges_bytes(int n, int k, int channels);
+void launch_moran_forward(const MoranSource& s, const MoranTensors& t, void* workspace, float* out, hipStream_t st);
+void launch_moran_backward(const MoranSource& s, const MoranTensors& t, const uint32_t* rev_start, const uint32_t* rev_edges, const float* out,
+                           const float* upstream, void* edges, float* d_points, float* d_weight, hipStream_t st);
+void launch_moran_weights(const MoranSource& s, float* weights, hipStream_t st);
+void launch_moran_weights_backward(const MoranSource& s, const uint32_t* rev_start, const uint32_t* rev_edges, const float* d_weights,
+                                   void* edges, float* d_points, hipStream_t st);
 
 // loss.hip
 bool loss_shape_ok(int batch, int channels, int H, int W);

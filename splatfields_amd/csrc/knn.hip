@@ -6,6 +6,9 @@
 // Exact k-NN (k = 3, self excluded by index) on a uniform grid: points are counting-sorted into ~N/2 cells, and each
 // point searches growing cubes of cells until its 3rd-best squared distance is <= (ring * cell_size)^2, which
 // no point outside the cube can beat.  The published CUDA code does the same job with a Morton sort + box pruning.
+//
+// Second half of the file: the K-nearest-neighbour GRAPH (2 <= K <= 8, self included) of the Moran's I regulariser on the same
+// grid -- the counterpart of [EXT] pytorch3d.ops.knn.knn_points at reference extract_geo.py:101-103.
 #include "kernels.h"
 
 namespace sr {
@@ -67,12 +70,9 @@ __global__ void k_knn_count(int n, const float* __restrict__ pts, const float* _
     atomicAdd(&count[(c.z * g.gy + c.y) * g.gx + c.x], 1u);
 }
 
-// exclusive scan of count[0..cells) by one workgroup -> start[0..cells]; cursor := 0
-__global__ void __launch_bounds__(1024) k_knn_scan(const float* __restrict__ bounds, int n, int max_cells, const uint32_t* __restrict__ count,
-                                                   uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
-    __shared__ uint32_t s_wave[16];
-    const KnnGrid g = make_grid(bounds, n, max_cells);
-    const int cells = g.gx * g.gy * g.gz;
+// exclusive scan of count[0..cells) by one workgroup of 1024 -> start[0..cells]; cursor := 0
+__device__ __forceinline__ void scan_counts(int cells, const uint32_t* __restrict__ count, uint32_t* __restrict__ start,
+                                            uint32_t* __restrict__ cursor, uint32_t* s_wave) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     uint32_t carry = 0;
     for (int base = 0; base < cells; base += 1024) {
@@ -88,6 +88,13 @@ __global__ void __launch_bounds__(1024) k_knn_scan(const float* __restrict__ bou
         __syncthreads();
     }
     if (tid == 0) start[cells] = carry;
+}
+
+__global__ void __launch_bounds__(1024) k_knn_scan(const float* __restrict__ bounds, int n, int max_cells, const uint32_t* __restrict__ count,
+                                                   uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
+    __shared__ uint32_t s_wave[16];
+    const KnnGrid g = make_grid(bounds, n, max_cells);
+    scan_counts(g.gx * g.gy * g.gz, count, start, cursor, s_wave);
 }
 
 __global__ void k_knn_fill(int n, const float* __restrict__ pts, const float* __restrict__ bounds, int max_cells, const uint32_t* __restrict__ start,
@@ -167,6 +174,151 @@ void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream
     hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(1024), 0, st, bounds, n, max_cells, count, start, cursor);
     hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, cursor, order);
     hipLaunchKernelGGL(k_knn_search, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, order, out);
+}
+
+// ---- k-nearest-neighbour graph (self included) and its reverse adjacency: the Moran regulariser's neighbourhoods ----
+//
+// The same grid and the same growing-cube stop rule as above.  Everything that the unordered integer cursor of k_knn_fill
+// touches is put into a fixed order before it is used: a cell's points by index (k_rank_segments), the K-best list by
+// (squared distance, index), a target's incoming edges by edge id = source * K + slot (k_rank_segments again).
+
+// slot s of a segmented list filled through a cursor -> its place by value inside its segment.  key[] names the segment
+// of a value (NULL: the value's grid cell).  Work is the sum of the squared segment lengths, spread over all slots.
+__global__ void k_rank_segments(int slots, const uint32_t* __restrict__ unordered, const int* __restrict__ key, int n, const float* __restrict__ pts,
+                                const float* __restrict__ bounds, int max_cells, const uint32_t* __restrict__ start, uint32_t* __restrict__ ordered) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    const uint32_t v = unordered[s];
+    int seg;
+    if (key) seg = key[v];
+    else {
+        const KnnGrid g = make_grid(bounds, n, max_cells);
+        const int3 c = cell_of(g, pts[3 * (size_t)v], pts[3 * (size_t)v + 1], pts[3 * (size_t)v + 2]);
+        seg = (c.z * g.gy + c.y) * g.gx + c.x;
+    }
+    const uint32_t lo = start[seg], hi = start[seg + 1];
+    uint32_t rank = 0;
+    for (uint32_t k = lo; k < hi; ++k) rank += unordered[k] < v ? 1u : 0u;
+    ordered[lo + rank] = v;
+}
+
+template <int K>
+__device__ __forceinline__ void knn_insert_k(float d, uint32_t j, float (&bd)[K], uint32_t (&bj)[K]) {
+    if (!(d < bd[K - 1] || (d == bd[K - 1] && j < bj[K - 1]))) return;
+    bd[K - 1] = d; bj[K - 1] = j;
+#pragma unroll
+    for (int s = K - 1; s > 0; --s) {
+        const bool up = bd[s] < bd[s - 1] || (bd[s] == bd[s - 1] && bj[s] < bj[s - 1]);
+        const float td = bd[s - 1]; const uint32_t tj = bj[s - 1];
+        bd[s - 1] = up ? bd[s] : td; bj[s - 1] = up ? bj[s] : tj;
+        bd[s] = up ? td : bd[s]; bj[s] = up ? tj : bj[s];
+    }
+}
+
+// thread t serves point order[t]: neighbouring threads search the same cells
+template <int K>
+__global__ void __launch_bounds__(256) k_knn_search_k(int n, const float* __restrict__ pts, const float* __restrict__ bounds, int max_cells,
+                                                      const uint32_t* __restrict__ start, const uint32_t* __restrict__ order, int* __restrict__ nn_ix) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t i = order[t];
+    const KnnGrid g = make_grid(bounds, n, max_cells);
+    const float px = pts[3 * (size_t)i], py = pts[3 * (size_t)i + 1], pz = pts[3 * (size_t)i + 2];
+    const int3 c = cell_of(g, px, py, pz);
+    float bd[K]; uint32_t bj[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { bd[k] = 3.0e38f; bj[k] = 0xffffffffu; }
+    const int rmax = max(g.gx, max(g.gy, g.gz));
+    for (int r = 0; r <= rmax; ++r) {
+        for (int dz = -r; dz <= r; ++dz) {
+            const int z = c.z + dz; if (z < 0 || z >= g.gz) continue;
+            for (int dy = -r; dy <= r; ++dy) {
+                const int y = c.y + dy; if (y < 0 || y >= g.gy) continue;
+                const bool face = (dz == -r || dz == r || dy == -r || dy == r);
+                const int step = face ? 1 : max(2 * r, 1);
+                for (int dx = -r; dx <= r; dx += step) {
+                    const int x = c.x + dx; if (x < 0 || x >= g.gx) continue;
+                    const int cell = (z * g.gy + y) * g.gx + x;
+                    for (uint32_t k = start[cell]; k < start[cell + 1]; ++k) {
+                        const uint32_t j = order[k];
+                        const float ddx = pts[3 * (size_t)j] - px, ddy = pts[3 * (size_t)j + 1] - py, ddz = pts[3 * (size_t)j + 2] - pz;
+                        knn_insert_k<K>(ddx * ddx + ddy * ddy + ddz * ddz, j, bd, bj);
+                    }
+                }
+            }
+        }
+        const float safe = r * g.cell;   // an unvisited point is at least this far: strictly below, so that one at exactly the
+        if (bd[K - 1] < safe * safe) break;   // K-th distance with a lower index is still met
+    }
+    // fewer than K comparable points (non-finite coordinates): the point stands in for the missing ones, so that every
+    // index can be gathered
+#pragma unroll
+    for (int k = 0; k < K; ++k) nn_ix[(size_t)i * K + k] = bj[k] < (uint32_t)n ? (int)bj[k] : (int)i;
+}
+
+__global__ void k_rev_count(int edges, const int* __restrict__ nn_ix, uint32_t* __restrict__ count) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < edges) atomicAdd(&count[nn_ix[e]], 1u);
+}
+
+__global__ void __launch_bounds__(1024) k_rev_scan(int n, const uint32_t* __restrict__ count, uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
+    __shared__ uint32_t s_wave[16];
+    scan_counts(n, count, start, cursor, s_wave);
+}
+
+__global__ void k_rev_fill(int edges, const int* __restrict__ nn_ix, const uint32_t* __restrict__ start, uint32_t* __restrict__ cursor,
+                           uint32_t* __restrict__ unordered) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= edges) return;
+    const int t = nn_ix[e];
+    unordered[start[t] + atomicAdd(&cursor[t], 1u)] = (uint32_t)e;
+}
+
+size_t knn_graph_workspace_bytes(int n, int k) {
+    if (n <= 0 || k < kKnnMinK || k > kKnnMaxK) return 0;
+    const size_t cells = (size_t)(n > 2 ? n : 2);
+    return align_up(8 * sizeof(float), 256) + 3 * align_up((cells + 1) * sizeof(uint32_t), 256) + align_up((size_t)n * sizeof(uint32_t), 256) +
+           align_up((size_t)n * k * sizeof(uint32_t), 256);
+}
+
+template <int K>
+static void launch_search_k(int nb, int n, const float* pts, const float* bounds, int max_cells, const uint32_t* start, const uint32_t* order,
+                            int* nn_ix, hipStream_t st) {
+    hipLaunchKernelGGL(k_knn_search_k<K>, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, order, nn_ix);
+}
+
+void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* order, uint32_t* rev_start, uint32_t* rev_edges, void* workspace,
+                      hipStream_t st) {
+    Carver c{static_cast<char*>(workspace), 0};
+    const int max_cells = n > 2 ? n : 2;
+    float* bounds = c.take<float>(8);
+    uint32_t* count = c.take<uint32_t>((size_t)max_cells + 1);
+    uint32_t* start = c.take<uint32_t>((size_t)max_cells + 1);
+    uint32_t* cursor = c.take<uint32_t>((size_t)max_cells + 1);
+    uint32_t* unordered = c.take<uint32_t>((size_t)n);
+    uint32_t* unordered_edges = c.take<uint32_t>((size_t)n * k);
+    const int nb = (n + 255) / 256, edges = n * k, eb = (edges + 255) / 256;
+    hipMemsetAsync(count, 0, sizeof(uint32_t) * ((size_t)max_cells + 1), st);
+    hipLaunchKernelGGL(k_knn_bounds, dim3(1), dim3(1024), 0, st, n, pts, bounds);
+    hipLaunchKernelGGL(k_knn_count, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, count);
+    hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(1024), 0, st, bounds, n, max_cells, count, start, cursor);
+    hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, cursor, unordered);
+    hipLaunchKernelGGL(k_rank_segments, dim3(nb), dim3(256), 0, st, n, unordered, (const int*)nullptr, n, pts, bounds, max_cells, start, order);
+    switch (k) {
+        case 2: launch_search_k<2>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 3: launch_search_k<3>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 4: launch_search_k<4>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 5: launch_search_k<5>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 6: launch_search_k<6>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 7: launch_search_k<7>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        default: launch_search_k<8>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+    }
+    // reverse adjacency: per target, the edges that end there, by edge id
+    hipMemsetAsync(count, 0, sizeof(uint32_t) * ((size_t)n + 1), st);
+    hipLaunchKernelGGL(k_rev_count, dim3(eb), dim3(256), 0, st, edges, nn_ix, count);
+    hipLaunchKernelGGL(k_rev_scan, dim3(1), dim3(1024), 0, st, n, count, rev_start, cursor);
+    hipLaunchKernelGGL(k_rev_fill, dim3(eb), dim3(256), 0, st, edges, nn_ix, rev_start, cursor, unordered_edges);
+    hipLaunchKernelGGL(k_rank_segments, dim3(eb), dim3(256), 0, st, edges, unordered_edges, nn_ix, n, pts, bounds, max_cells, rev_start, rev_edges);
 }
 
 }  // namespace sr
