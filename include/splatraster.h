@@ -33,6 +33,9 @@
  *   sr_knn_graph + sr_moran_forward / sr_moran_backward, sr_moran_weights / sr_moran_weights_backward
  *        <- reference extract_geo.py:100-143 (`query_nn`, `morans_measure`, `morans_loss`) as train.py:203-215 calls them:
  *           [EXT] pytorch3d.ops.knn.knn_points and the [N,F,K,K] temporaries of the Moran's I regulariser.
+ *   sr_adam_step
+ *        <- reference train.py:314-322 (`gaussians.optimizer.step()`), the `torch.optim.Adam` of scene/gaussian_model.py:130-139:
+ *           every tensor of the step in one launch.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -351,6 +354,32 @@ int sr_densify_plan(int n_splats, const float* log_scales, int scale_cols, const
 int sr_densify_gather(int n_splats, int row_floats, const float* src, float* dst, const int* dest, int mode,
                       const float* log_scales, int scale_cols, const float* rotations, const float* unit_normals,
                       void* hip_stream);
+
+/* The Adam step of a training iteration (reference train.py:314-322; the optimizer is `torch.optim.Adam(l, lr=0.0, eps=1e-15)`
+ * over six tensors, scene/gaussian_model.py:130-139): ONE launch updates every tensor of the call.  Per element, in float32
+ * with correctly rounded division and square root,
+ *   m = m + one_minus_beta1 (g - m);   v = v + one_minus_beta2 (g^2 - v);        (= beta m + (1 - beta) g, weights summing to 1)
+ *   p = p - step_size * m / (sqrt(v) / bias_correction2_sqrt + eps).
+ * The scalars of a job are computed by the caller in double, as torch.optim.Adam does with capturable=False, and rounded to
+ * float32 once:  step_size = lr / (1 - beta1^t),  bias_correction2_sqrt = sqrt(1 - beta2^t),  one_minus_beta = 1 - beta
+ * (rounded from the double difference: 1.0f - 0.999f is off by 1.3e-5 of its value).
+ * param / grad / exp_avg / exp_avg_sq: `count` contiguous floats each (count <= 2^31 - 1), 4-byte aligned; where the four
+ * addresses agree modulo 16 the body moves as 16-byte vectors and only the unaligned head and tail go element by element.
+ * `visible` (may be NULL): one byte per row, `rows` of them; every job must then have count == rows * row, and the elements
+ * of a row whose byte is 0 are neither read nor changed: parameter and both moments keep their bits (the semantics of a
+ * sparse Adam with the global step count in the bias corrections).  `row` is not read without `visible`.
+ * n_jobs = 0 and jobs with count = 0 are valid and launch nothing.  No LDS, no atomics, nothing waits for the device. */
+#define SR_ADAM_MAX_TENSORS 32
+typedef struct SrAdamJob {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    long long count;
+    int row;
+    float step_size, bias_correction2_sqrt, one_minus_beta1, one_minus_beta2, eps;
+} SrAdamJob;
+int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible_or_null, long long rows, void* hip_stream);
 
 /* Fused MLP chains of the SplatFields deform network's `GeneralMLP`s (reference utils/time_utils.py:123-191; SURVEY.md
  * section 8f row 4): n_points points are carried through a list of OPS in ONE kernel, the running state (<= 16 * hidden_tiles

@@ -3,3 +3,4 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, raste
 from .render import render  # noqa: F401
 from .losses import l1_loss, photometric_loss, ssim  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
+from .optim import SplatAdam  # noqa: F401

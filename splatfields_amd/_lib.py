@@ -58,10 +58,17 @@ class SrResFieldJob(C.Structure):
                 ("d_matrix_t", C.c_void_p), ("d_weights_t", C.c_void_p), ("count", C.c_int), ("rank", C.c_int), ("capacity", C.c_int)]
 
 
+class SrAdamJob(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("count", C.c_longlong), ("row", C.c_int), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float),
+                ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
+
+
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 MLP_MAX_GRAD_JOBS, MLP_MAX_GRAD_TASKS = 16, 128
 MLP_MAX_PACK_JOBS = 32
 MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatraster.h: SR_MORAN_MAX_TENSORS, SR_KNN_MAX_K
+ADAM_MAX_TENSORS = 32                                        # include/splatraster.h: SR_ADAM_MAX_TENSORS
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
 
 
@@ -119,6 +126,7 @@ SYMBOLS = {
                                          C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_photometric_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_adam_step": (C.c_int, [C.c_int, C.POINTER(SrAdamJob), C.c_void_p, C.c_longlong, C.c_void_p]),
     "sr_densify_workspace_bytes": (C.c_size_t, [C.c_int]),
     "sr_densify_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),

@@ -716,6 +716,29 @@ int sr_photometric_backward(int batch, int channels, int height, int width, cons
     return check_hip(hipGetLastError(), "photometric_backward");
 }
 
+int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, long long rows, void* hip_stream) {
+    if (n_jobs < 0 || n_jobs > SR_ADAM_MAX_TENSORS) return fail("bad arguments to sr_adam_step: n_jobs must be 0 .. SR_ADAM_MAX_TENSORS (32)");
+    if (n_jobs > 0 && !jobs) return fail("null pointer in sr_adam_step: jobs");
+    if (visible && rows < 0) return fail("bad arguments to sr_adam_step: negative row count");
+    bool work = false;
+    for (int i = 0; i < n_jobs; ++i) {
+        const SrAdamJob& j = jobs[i];
+        const std::string at = " (job " + std::to_string(i) + ")";
+        if (j.count < 0) return fail("bad arguments to sr_adam_step: negative element count" + at);
+        if (j.count > 0x7fffffffll) return fail("too many elements for sr_adam_step: at most 2^31 - 1 in one job" + at);
+        if (visible && (j.row <= 0 || j.count != rows * (long long)j.row))
+            return fail("sr_adam_step: with a row mask every job needs count == rows * row" + at);
+        if (j.count == 0) continue;
+        if (!j.param || !j.grad || !j.exp_avg || !j.exp_avg_sq) return fail("null pointer in sr_adam_step" + at);
+        if ((reinterpret_cast<uintptr_t>(j.param) | reinterpret_cast<uintptr_t>(j.grad) | reinterpret_cast<uintptr_t>(j.exp_avg) |
+             reinterpret_cast<uintptr_t>(j.exp_avg_sq)) & 3u) return fail("sr_adam_step: tensors must be 4-byte aligned" + at);
+        work = true;
+    }
+    if (!work) return 0;
+    sr::launch_adam(n_jobs, jobs, visible, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "adam_step");
+}
+
 size_t sr_densify_workspace_bytes(int n) { return sr::densify_workspace_bytes(n); }
 
 int sr_densify_plan(int n, const float* log_scales, int scale_cols, const float* opacity_logits, const float* grad_accum,

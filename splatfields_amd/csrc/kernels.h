@@ -113,6 +113,9 @@ void launch_loss_backward(int batch, int channels, int H, int W, const float* im
                           const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask, const float* g, int g_per_item,
                           float* dL_dimage, float* dL_dalpha, hipStream_t st);
 
+// adam.hip: the jobs are checked by the caller (sr_adam_step); jobs with count 0 are skipped
+void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st);
+
 // sh.hip
 void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
                        unsigned char* clamped, hipStream_t st);
