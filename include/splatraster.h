@@ -33,6 +33,11 @@
  *   sr_knn_graph + sr_moran_forward / sr_moran_backward, sr_moran_weights / sr_moran_weights_backward
  *        <- reference extract_geo.py:100-143 (`query_nn`, `morans_measure`, `morans_loss`) as train.py:203-215 calls them:
  *           [EXT] pytorch3d.ops.knn.knn_points and the [N,F,K,K] temporaries of the Moran's I regulariser.
+ *   sr_image_metrics
+ *        <- reference render.py:33-160 (`compute_psnr`, `compute_ssim`: the scipy evaluation `eval_all` runs per image on the
+ *           host) and utils/image_utils.py:19-21 (`psnr`, train.py:387-396), with the 8-bit quantisation of the image files
+ *           in between (torchvision `save_image`, render.py:282 `to8b`): a batch of views in one kernel plus a fixed-order
+ *           reduction.
  *   sr_adam_step
  *        <- reference train.py:314-322 (`gaussians.optimizer.step()`), the `torch.optim.Adam` of scene/gaussian_model.py:130-139:
  *           every tensor of the step in one launch.
@@ -264,6 +269,30 @@ int sr_photometric_forward(int batch, int channels, int height, int width, const
 int sr_photometric_backward(int batch, int channels, int height, int width, const float* image, const float* gt,
                             const float* alpha, const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask,
                             const float* upstream, int upstream_per_item, float* dL_dimage, float* dL_dalpha, void* hip_stream);
+
+/* Evaluation metrics of a batch of views (reference render.py:33-160 `compute_psnr` / `compute_ssim` with its defaults,
+ * utils/image_utils.py `psnr`), forward only.  pred, gt: `batch` RGB images of height x width float32, addressed by ELEMENT
+ * strides {item, channel, row, pixel}: [B,3,H,W] renders and [B,H,W,3] images both go in without a copy.  height, width >= 11.
+ * `quantize` is applied to both images first:
+ *   SR_QUANT_NONE  as given;
+ *   SR_QUANT_PNG   trunc(clamp(x 255 + 0.5, 0, 255)) / 255: torchvision `save_image`, then the `/255.` of `eval_imgs`;
+ *   SR_QUANT_TO8B  trunc(255 clamp(x, 0, 1)) / 255: `to8b` of render.py:282.
+ * `mask`: NULL, or float32 [height, width] per item, rows contiguous, `mask_item_stride` elements apart (0: one mask for
+ * every item), read as mask != 0.  It selects the reference's two-stage partial convolution (count-normalised per pass);
+ * a window without a mask pixel scores exactly 1 and is counted.  The squared error is never masked.
+ * Written, all to device memory:  psnr[b] = -10/ln10 ln(mse_b);  ssim[b] = mean of the (height-10) x (width-10) x 3 similarity
+ * map (11-tap "valid" window, sigma 1.5, float32 taps, clipped variances);  psnr_channels[b,c] = 20 log10(1/sqrt(mse_bc));
+ * `frames` (may be NULL; needs a quantisation): uint8 [batch, height, width, 3], the quantised prediction.
+ * Identical images give psnr = +inf.  `workspace`: sr_metrics_workspace_bytes(batch, height, width) bytes (0 for a shape
+ * out of range), the per-workgroup partial sums in double, which one workgroup adds in a fixed order: no floating-point
+ * atomics, results bit-identical from call to call.  The call only enqueues on `hip_stream`; nothing waits. */
+#define SR_QUANT_NONE 0
+#define SR_QUANT_PNG 1
+#define SR_QUANT_TO8B 2
+size_t sr_metrics_workspace_bytes(int batch, int height, int width);
+int sr_image_metrics(int batch, int height, int width, const float* pred, const long long* pred_strides4, const float* gt,
+                     const long long* gt_strides4, const float* mask, long long mask_item_stride, int quantize, void* workspace,
+                     float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, void* hip_stream);
 
 /* SH colour evaluation as a stand-alone stage (the SH part of the forward preprocess; reference utils/sh_utils.py:57-112,
  * extract_geo.py:40-44): colors[N,3] = max(sum_k basis_k(dir) shs[k] + 0.5, 0), clamped[N] bit c set where channel c was

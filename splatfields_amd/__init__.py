@@ -2,5 +2,6 @@
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 from .render import render  # noqa: F401
 from .losses import l1_loss, photometric_loss, ssim  # noqa: F401
+from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
 from .optim import SplatAdam  # noqa: F401

@@ -716,6 +716,27 @@ int sr_photometric_backward(int batch, int channels, int height, int width, cons
     return check_hip(hipGetLastError(), "photometric_backward");
 }
 
+size_t sr_metrics_workspace_bytes(int batch, int height, int width) { return sr::metrics_workspace_bytes(batch, height, width); }
+
+int sr_image_metrics(int batch, int height, int width, const float* pred, const long long* pred_strides4, const float* gt,
+                     const long long* gt_strides4, const float* mask, long long mask_item_stride, int quantize, void* workspace,
+                     float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, void* hip_stream) {
+    if (batch <= 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_image_metrics: sizes must be positive");
+    if (height < 11 || width < 11) return fail("bad arguments to sr_image_metrics: the 11-tap valid window needs height and width >= 11");
+    if (!sr::metrics_shape_ok(batch, height, width)) return fail("image too large for sr_image_metrics");
+    if (!pred || !gt || !pred_strides4 || !gt_strides4 || !workspace || !psnr || !ssim || !psnr_channels) return fail("null pointer in sr_image_metrics");
+    if (quantize != SR_QUANT_NONE && quantize != SR_QUANT_PNG && quantize != SR_QUANT_TO8B)
+        return fail("bad arguments to sr_image_metrics: unknown quantisation mode (SR_QUANT_NONE, SR_QUANT_PNG, SR_QUANT_TO8B)");
+    if (frames && quantize == SR_QUANT_NONE) return fail("sr_image_metrics: frames are the quantised prediction and need a quantisation mode");
+    for (int k = 0; k < 4; ++k)
+        if (pred_strides4[k] < 0 || gt_strides4[k] < 0) return fail("bad arguments to sr_image_metrics: negative stride");
+    if (mask && mask_item_stride != 0 && mask_item_stride < (long long)height * width)
+        return fail("bad arguments to sr_image_metrics: mask_item_stride must be 0 or at least height * width");
+    sr::launch_image_metrics(batch, height, width, pred, pred_strides4, gt, gt_strides4, mask, mask_item_stride, quantize, workspace, psnr,
+                             ssim, psnr_channels, frames, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "image_metrics");
+}
+
 int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, long long rows, void* hip_stream) {
     if (n_jobs < 0 || n_jobs > SR_ADAM_MAX_TENSORS) return fail("bad arguments to sr_adam_step: n_jobs must be 0 .. SR_ADAM_MAX_TENSORS (32)");
     if (n_jobs > 0 && !jobs) return fail("null pointer in sr_adam_step: jobs");

@@ -113,6 +113,13 @@ void launch_loss_backward(int batch, int channels, int H, int W, const float* im
                           const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask, const float* g, int g_per_item,
                           float* dL_dimage, float* dL_dalpha, hipStream_t st);
 
+// metrics.hip
+bool metrics_shape_ok(int batch, int H, int W);
+size_t metrics_workspace_bytes(int batch, int H, int W);   // 0 for a shape out of range
+void launch_image_metrics(int batch, int H, int W, const float* pred, const long long* pred_strides, const float* gt,
+                          const long long* gt_strides, const float* mask, long long mask_item_stride, int quantize, void* workspace,
+                          float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, hipStream_t st);
+
 // adam.hip: the jobs are checked by the caller (sr_adam_step); jobs with count 0 are skipped
 void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st);
 
