@@ -476,6 +476,20 @@ typedef struct SrMlpPackJob {
 } SrMlpPackJob;
 int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
 
+/* The same chains with bfloat16 matrix operands (opt-in; the fp32 pair above stays the default and is not affected).  With
+ * bf(.) = round to nearest even to bfloat16:
+ *   forward ops   acc = bias + bf(W) . bf(x)        backward ops   acc = bf(W^T) . bf(dZ)
+ * Products and accumulation are fp32 (v_mfma_f32_16x16x32_bf16); the bias is fp32 and the accumulator's initial value; the
+ * running state stays fp32 in registers and is rounded only where it becomes an MFMA operand; channels read from `src` are
+ * rounded as they are loaded.  Everything stored (saved activations, dZ, y, dL/dx0, accumulating stores), the epilogues and the
+ * sign bits are computed from the unrounded fp32 accumulators exactly as by sr_mlp_chain, and results are bit-identical from
+ * run to run.  Weight gradients come from sr_mlp_weight_grad on those stored fp32 values, unchanged.
+ * sr_mlp_pack_bf16 takes the job table of sr_mlp_pack: `dst` receives 16 * out_tiles * (mem_pad + reg_width) bfloat16 values
+ * (16-byte aligned; layout: csrc/mlp.hip), `bias_dst` stays fp32.  sr_mlp_chain_bf16 takes the op table of sr_mlp_chain with
+ * `w_packed` pointing at what sr_mlp_pack_bf16 wrote.  Arguments are validated as by the fp32 entry points. */
+int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
+int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream);
+
 /* Weight and bias gradients of the layers of a fused MLP: for every job
  *   dw[m * dw_row + dw_col0 + c] = sum over points p of dz[p * dz_row + m] * x[p * x_row + c],   m < job.m, c < job.k
  *   db[m]                        = sum over points p of dz[p * dz_row + m]                       (when db is set)

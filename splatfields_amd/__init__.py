@@ -5,3 +5,4 @@ from .losses import l1_loss, photometric_loss, ssim  # noqa: F401
 from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
 from .optim import SplatAdam  # noqa: F401
+from .fused_mlp import mlp_precision, set_mlp_precision  # noqa: F401

@@ -794,21 +794,37 @@ int sr_densify_gather(int n, int row_floats, const float* src, float* dst, const
     return check_hip(hipGetLastError(), "densify_gather");
 }
 
-int sr_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
-    if (n_points < 0 || !ops) return fail("bad arguments to sr_mlp_chain");
-    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain: negative_slope must be in [0, 1)");
-    if (sr::launch_mlp_chain(n_points, hidden_tiles, n_ops, ops, negative_slope, static_cast<hipStream_t>(hip_stream)))
-        return fail("sr_mlp_chain: unsupported op list (hidden_tiles 4 or 8, <= SR_MLP_MAX_OPS ops, even input tile counts, "
+static int mlp_chain_entry(const char* name, bool bf16, int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    if (n_points < 0 || !ops) return fail(std::string("bad arguments to ") + name);
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail(std::string(name) + ": negative_slope must be in [0, 1)");
+    if (sr::launch_mlp_chain(n_points, hidden_tiles, n_ops, ops, negative_slope, bf16, static_cast<hipStream_t>(hip_stream)))
+        return fail(std::string(name) + ": unsupported op list (hidden_tiles 4 or 8, <= SR_MLP_MAX_OPS ops, even input tile counts, "
                     "16-byte aligned rows wide enough for the tiles read)");
-    return check_hip(hipGetLastError(), "mlp_chain");
+    return check_hip(hipGetLastError(), bf16 ? "mlp_chain_bf16" : "mlp_chain");
+}
+
+static int mlp_pack_entry(const char* name, bool bf16, int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return fail(std::string("bad arguments to ") + name);
+    if (sr::launch_mlp_pack(n_jobs, jobs, bf16, static_cast<hipStream_t>(hip_stream)))
+        return fail(std::string(name) + ": unsupported job (<= SR_MLP_MAX_PACK_JOBS jobs; mem_pad multiple of 32, reg_width of 16, even tile "
+                    "count; counts within their padded sizes; 16-byte aligned destination)");
+    return check_hip(hipGetLastError(), bf16 ? "mlp_pack_bf16" : "mlp_pack");
+}
+
+int sr_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    return mlp_chain_entry("sr_mlp_chain", false, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+}
+
+int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    return mlp_chain_entry("sr_mlp_chain_bf16", true, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
 }
 
 int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
-    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return fail("bad arguments to sr_mlp_pack");
-    if (sr::launch_mlp_pack(n_jobs, jobs, static_cast<hipStream_t>(hip_stream)))
-        return fail("sr_mlp_pack: unsupported job (<= SR_MLP_MAX_PACK_JOBS jobs; mem_pad multiple of 32, reg_width of 16, even tile "
-                    "count; counts within their padded sizes; 16-byte aligned destination)");
-    return check_hip(hipGetLastError(), "mlp_pack");
+    return mlp_pack_entry("sr_mlp_pack", false, n_jobs, jobs, hip_stream);
+}
+
+int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    return mlp_pack_entry("sr_mlp_pack_bf16", true, n_jobs, jobs, hip_stream);
 }
 
 size_t sr_mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs) {

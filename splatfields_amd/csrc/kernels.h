@@ -57,8 +57,8 @@ void launch_densify_gather(int n, int row, const float* src, float* dst, const i
 // mlp.hip
 size_t mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs);
 int launch_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, void* workspace, size_t workspace_bytes, hipStream_t st);
-int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, hipStream_t st);
-int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, hipStream_t st);
+int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, bool bf16, hipStream_t st);
+int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, bool bf16, hipStream_t st);
 
 int launch_mlp_input_forward(int N, int L, int F, int TL, int row, const float* xyz, const float* feat, const float* time, float* x0, hipStream_t st);
 int launch_mlp_top_gradient(int N, int out, int row, const float* y, const float* dy, float slope, float* G, hipStream_t st);

@@ -1,5 +1,6 @@
 // Fused MLP kernels of the SplatFields deform network for gfx950: the layer chain (forward, and the
-// activation-gradient chain of the backward), the weight packer, and the weight-gradient kernel.
+// activation-gradient chain of the backward), the weight packer, and the weight-gradient kernel.  The chain and the packer exist
+// twice: exact fp32 (the default, described here) and, opt-in, with bf16 matrix operands (k_mlp_chain_bf16 below).
 //
 // What it replaces: reference utils/time_utils.py:123-191 (`GeneralMLP`: Linear -> activation for every layer, the
 // input concatenated back in front of the hidden state after the `skips` layers), which PyTorch-ROCm runs as one GEMM +
@@ -255,6 +256,170 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
     }
 }
 
+// ---- the same chains with bf16 matrix operands (opt-in: sr_mlp_chain_bf16) ------------------------------------------------
+// acc = bias + bf(W) . bf(x): both MFMA operands are rounded to bfloat16 (round to nearest even, v_cvt_pk_bf16_f32), products and
+// accumulation stay fp32 inside `v_mfma_f32_16x16x32_bf16`, and everything outside the MFMA is the fp32 kernel's: the bias as
+// the accumulator's initial value, the running state in fp32 registers (rounded only where it becomes an operand, once per op and
+// state tile), the epilogues, the sign bits and every store.  The fp32 MFMA issues at the vector rate on gfx950, 1/16 of the bf16
+// rate: a 32-channel chunk at HT = 8 is 16 MFMAs here instead of 128.
+//
+// Operand map of the 16x16x32 MFMA: lane (k = lane >> 4, m or n = lane & 15) holds K indices 8 k + j, j = 0..7, of row m of A and
+// of column n of B; the accumulator is the fp32 one (register i of lane (k, n) = row 4 k + i of column n).  A and B share the
+// lane -> K map, so WHICH channel sits at K index 8 k + j is free as long as packer and operand agree: element j stands for
+// channel 32 c + 16 (j >> 2) + 4 k + (j & 3) of chunk c, which makes the B operand of lane (k, n) the eight values
+// [prev[nt][2 c][0..3], prev[nt][2 c + 1][0..3]] it already holds -- the accumulator of one layer is still the operand of the next.
+// Packed matrix (k_mlp_pack_bf16), MT output tiles:
+//   bf16 index (((c * MT + mt) * 64 + lane) * 8 + j)  =  A[16 mt + (lane & 15)][32 c + 16 (j >> 2) + 4 (lane >> 4) + (j & 3)]
+// one ds_read_b128 per lane, output tile and chunk; a chunk is MT KiB in LDS.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#ifndef SR_MLP_BF16_WAVES8
+#define SR_MLP_BF16_WAVES8 2     // wavefronts per SIMD the 128-wide bf16 kernel is compiled for
+#endif
+
+__device__ __forceinline__ bf16x8 mlp_operand_bf16(const f32x4 lo, const f32x4 hi) {
+    return (bf16x8){(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+}
+
+// One 32-channel chunk against all output tiles: one MFMA per output tile and point tile.  `w` points at this lane's 16 bytes of
+// output tile 0 (consecutive output tiles are 64 x 16 bytes apart).  The 2 HT accumulators are independent: no dependent chains.
+template <int HT, bool FULL>
+__device__ __forceinline__ void mlp_chunk_bf16(f32x4 (&acc)[2][HT], const bf16x8* w, int out_tiles, const bf16x8 b0, const bf16x8 b1) {
+#pragma unroll
+    for (int mt = 0; mt < HT; ++mt) {
+        if (FULL || mt < out_tiles) {
+            const bf16x8 a = w[mt * 64];
+            acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b0, acc[0][mt], 0, 0, 0);
+            acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b1, acc[1][mt], 0, 0, 0);
+        }
+    }
+}
+
+template <int HT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_BF16_WAVES8 : 3, HT == 8 ? SR_MLP_BF16_WAVES8 : 3))) k_mlp_chain_bf16(const MlpK net, int n_points, float slope) {
+    __shared__ bf16x8 s_w[2][HT * 64];       // two chunks of a packed matrix: [mt][lane]
+    const int wave = wave_id(), lane = lane_id();
+    const int k = lane >> 4, n = lane & 15;
+    const int p0 = (blockIdx.x * 4 + wave) * 32;              // first point of this wavefront
+    int prow[2];                                              // this lane's point of each of the two point tiles (clamped)
+    bool pvalid[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) { prow[nt] = min(p0 + 16 * nt + n, n_points - 1); pvalid[nt] = p0 + 16 * nt + n < n_points; }
+
+    f32x4 prev[2][HT], acc[2][HT];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int t = 0; t < HT; ++t) prev[nt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    int buf = 0;
+    for (int l = 0; l < net.n_ops; ++l) {
+        const SrMlpOp L = net.op[l];
+        const bf16x8* w8 = reinterpret_cast<const bf16x8*>(L.w_packed);
+        const int chunk_v = L.out_tiles * 64;                  // 16-byte vectors per chunk: mt x 64
+        const int n_chunks = (L.mem_tiles + L.reg_tiles) / 2;
+        // LDS-direct staging as in k_mlp_chain: chunk c + 1 is requested under the MFMAs of chunk c and waited for at the top of
+        // the next chunk; a wavefront copies whole 64-lane pieces
+        auto stage = [&](int c, int into) {
+            const bf16x8* src = w8 + (size_t)c * chunk_v;
+            for (int j0 = 0; j0 < chunk_v; j0 += kBlock) {
+                if (j0 + 64 * wave < chunk_v)
+                    lds_copy16_async(src + j0 + (int)threadIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_address(&s_w[into][j0 + 64 * wave])));
+            }
+        };
+#pragma unroll
+        for (int mt = 0; mt < HT; ++mt) {                      // the bias stays fp32: the accumulators' initial value
+            f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+            if (L.bias && mt < L.out_tiles) { const float4 t4 = reinterpret_cast<const float4*>(L.bias)[4 * mt + k]; b4 = (f32x4){t4.x, t4.y, t4.z, t4.w}; }
+            acc[0][mt] = b4; acc[1][mt] = b4;
+        }
+        uint32_t mbits[2] = {0u, 0u};
+        if (L.mask_bits) { mbits[0] = L.mask_bits[(size_t)prow[0] * 4 + k]; mbits[1] = L.mask_bits[(size_t)prow[1] * 4 + k]; }
+        __syncthreads();          // everyone has left the previous op's last chunk
+        stage(0, buf);
+        int c = 0;
+        const bool full = L.out_tiles == HT;                   // wave-uniform
+        const bool store_vec = (L.store_row & 3) == 0 && (reinterpret_cast<uintptr_t>(L.store) & 15u) == 0;
+        // ---- input channels that come from memory: rounded as they are loaded ----
+        for (; c < L.mem_tiles / 2; ++c) {
+            bf16x8 bm[2];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const float* row = L.src + (size_t)prow[nt] * L.src_row + 32 * c + 4 * k;
+                const float4 lo = *reinterpret_cast<const float4*>(row), hi = *reinterpret_cast<const float4*>(row + 16);
+                bm[nt] = mlp_operand_bf16((f32x4){lo.x, lo.y, lo.z, lo.w}, (f32x4){hi.x, hi.y, hi.z, hi.w});
+            }
+            lds_copy_wait();      // this wavefront's pieces of chunk c have landed ...
+            __syncthreads();      // ... and everybody's; the other buffer is free
+            if (c + 1 < n_chunks) stage(c + 1, buf ^ 1);
+            if (full) mlp_chunk_bf16<HT, true>(acc, &s_w[buf][lane], L.out_tiles, bm[0], bm[1]);
+            else mlp_chunk_bf16<HT, false>(acc, &s_w[buf][lane], L.out_tiles, bm[0], bm[1]);
+            buf ^= 1;
+        }
+        // ---- input channels that are the register state: each state tile is rounded once per op, here ----
+#pragma unroll
+        for (int cr = 0; cr < HT / 2; ++cr) {
+            if (cr < L.reg_tiles / 2) {
+                const bf16x8 b0 = mlp_operand_bf16(prev[0][2 * cr], prev[0][2 * cr + 1]), b1 = mlp_operand_bf16(prev[1][2 * cr], prev[1][2 * cr + 1]);
+                lds_copy_wait();
+                __syncthreads();
+                if (c + 1 < n_chunks) stage(c + 1, buf ^ 1);
+                if (full) mlp_chunk_bf16<HT, true>(acc, &s_w[buf][lane], L.out_tiles, b0, b1);
+                else mlp_chunk_bf16<HT, false>(acc, &s_w[buf][lane], L.out_tiles, b0, b1);
+                buf ^= 1;
+                ++c;
+            }
+        }
+        // ---- epilogue: the fp32 kernel's, on unrounded fp32 accumulators ----
+        const bool plain = full && p0 + 32 <= n_points && !L.keep_state &&
+                           (L.epilogue == SR_MLP_LEAKY || (L.epilogue == SR_MLP_MASK && L.mask_bits)) &&
+                           (!L.store || (store_vec && L.store_channels == 16 * HT && !L.store_accumulate));   // wave-uniform
+        if (plain) { mlp_epilogue_plain<HT>(acc, prev, L, slope, mbits, p0, n, k); continue; }
+        // (k_mlp_chain's generic epilogue, repeated: as a function shared by the two kernels it costs ~600 spilled registers at HT = 4)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            uint32_t signs = 0u;                                // bit 4 mt + i: channel 16 mt + 4 k + i of this point is > 0
+#pragma unroll
+            for (int mt = 0; mt < HT; ++mt) {
+                f32x4 r = {0.f, 0.f, 0.f, 0.f};
+                if (mt < L.out_tiles) {
+                    r = acc[nt][mt];
+                    if (L.epilogue == SR_MLP_LEAKY) {            // activation of a forward layer (leaky ReLU, 0 <= slope < 1)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) r[i] = fmaxf(r[i], slope * r[i]);
+                    } else if (L.epilogue == SR_MLP_MASK) {      // backward: times leaky'(x), read off the saved activation's sign
+                        if (L.mask_bits) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) r[i] *= (mbits[nt] >> (4 * mt + i)) & 1u ? 1.0f : slope;
+                        } else {
+                            const float4 m4 = *reinterpret_cast<const float4*>(L.mask + (size_t)prow[nt] * L.mask_row + 16 * mt + 4 * k);
+                            r[0] *= m4.x > 0.f ? 1.0f : slope; r[1] *= m4.y > 0.f ? 1.0f : slope;
+                            r[2] *= m4.z > 0.f ? 1.0f : slope; r[3] *= m4.w > 0.f ? 1.0f : slope;
+                        }
+                    }
+                    if (L.sign_store) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) signs |= (r[i] > 0.f ? 1u : 0u) << (4 * mt + i);
+                    }
+                    if (L.store && pvalid[nt]) {
+                        float* dst = L.store + (size_t)(p0 + 16 * nt + n) * L.store_row + 16 * mt + 4 * k;
+                        if (store_vec && 16 * mt + 4 * k + 3 < L.store_channels) {       // whole float4 inside the row: one 16-byte access
+                            float4 v = make_float4(r[0], r[1], r[2], r[3]);
+                            if (L.store_accumulate) { const float4 o = *reinterpret_cast<const float4*>(dst); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+                            *reinterpret_cast<float4*>(dst) = v;
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                if (16 * mt + 4 * k + i < L.store_channels) dst[i] = L.store_accumulate ? dst[i] + r[i] : r[i];
+                        }
+                    }
+                }
+                if (!L.keep_state) prev[nt][mt] = r;
+            }
+            if (L.sign_store && pvalid[nt]) L.sign_store[(size_t)(p0 + 16 * nt + n) * 4 + k] = signs;
+        }
+    }
+}
+
 struct MlpPackK { SrMlpPackJob job[SR_MLP_MAX_PACK_JOBS]; };
 
 // One packed float per thread step: thread index = the destination index, decoded to (c, mt, tl, lane, i) -> (row, column).
@@ -274,6 +439,33 @@ __global__ void __launch_bounds__(kBlock) k_mlp_pack(const MlpPackK jobs) {
         float v = 0.0f;
         if (r < J.n_rows && col >= 0) v = J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
         J.dst[d] = v;
+    }
+    if (J.bias_dst && blockIdx.x == 0)
+        for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
+}
+
+// The matrix of a job rounded to bf16 in the layout k_mlp_chain_bf16 reads (above): two adjacent packed elements (j, j + 1 = two
+// adjacent columns of the same 4-column group) per thread step, one 4-byte store.  The bias is copied as fp32.
+__global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16(const MlpPackK jobs) {
+    const SrMlpPackJob J = jobs.job[blockIdx.y];
+    const int pairs = 8 * J.out_tiles * (J.mem_pad + J.reg_width);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(J.dst);
+    for (int d = blockIdx.x * kBlock + (int)threadIdx.x; d < pairs; d += gridDim.x * kBlock) {
+        const int j = 2 * (d & 3), lane = (d >> 2) & 63;
+        const int rest = d >> 8;                       // c * MT + mt
+        const int mt = rest % J.out_tiles, c = rest / J.out_tiles;
+        const int r = 16 * mt + (lane & 15);
+        const int cp = 32 * c + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
+        float v[2] = {0.0f, 0.0f};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            int col = -1;
+            if (cp + e < J.mem_pad) { if (cp + e < J.n_mem) col = J.mem_col0 + cp + e; }
+            else if (cp + e - J.mem_pad < J.n_reg) col = J.reg_col0 + cp + e - J.mem_pad;
+            if (r < J.n_rows && col >= 0) v[e] = J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
+        }
+        const __bf16 lo = (__bf16)v[0], hi = (__bf16)v[1];
+        dst[d] = (uint32_t)__builtin_bit_cast(unsigned short, lo) | ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
     }
     if (J.bias_dst && blockIdx.x == 0)
         for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
@@ -449,7 +641,7 @@ int launch_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, v
     return 0;
 }
 
-int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, hipStream_t st) {
+int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, bool bf16, hipStream_t st) {
     if (n_jobs < 0 || n_jobs > SR_MLP_MAX_PACK_JOBS) return 1;
     if (n_jobs == 0) return 0;
     MlpPackK k;
@@ -463,12 +655,17 @@ int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, hipStream_t st) {
         k.job[j] = s;
         most = max(most, 16 * s.out_tiles * (s.mem_pad + s.reg_width));
     }
+    if (bf16) {           // two elements per thread step
+        const int bx = min(64, (most / 2 + kBlock * 4 - 1) / (kBlock * 4));
+        hipLaunchKernelGGL(k_mlp_pack_bf16, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
+        return 0;
+    }
     const int bx = min(64, (most + kBlock * 4 - 1) / (kBlock * 4));
     hipLaunchKernelGGL(k_mlp_pack, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
     return 0;
 }
 
-int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, hipStream_t st) {
+int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, bool bf16, hipStream_t st) {
     if (n_ops < 1 || n_ops > kMlpMaxOps) return 1;
     MlpK net;
     net.n_ops = n_ops;
@@ -486,6 +683,12 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
     }
     if (n_points <= 0) return 0;
     const int blocks = (n_points + 127) / 128;
+    if (bf16) {
+        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_bf16<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
+        else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain_bf16<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
+        else return 1;
+        return 0;
+    }
     if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
     else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
     else return 1;

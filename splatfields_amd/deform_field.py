@@ -103,7 +103,9 @@ class FlowHead(nn.Module):
 
 
 class SplatFields(nn.Module):
-    def __init__(self, radius=None, n_frames: int = 0, encoder: Optional[nn.Module] = None, **kwargs):
+    def __init__(self, radius=None, n_frames: int = 0, encoder: Optional[nn.Module] = None, mlp_precision: Optional[str] = None, **kwargs):
+        """`mlp_precision`: "fp32", "bf16" or None (the process default, splatfields_amd.set_mlp_precision) for the fused layer
+        chains of every GeneralMLP built here."""
         super().__init__()
         rank = kwargs.get("composition_rank", 0)
         self.n_frames = n_frames
@@ -136,7 +138,8 @@ class SplatFields(nn.Module):
         def mlp(prefix, out, w, d, skips, multires, out_act, in_features=in_ch):
             return GeneralMLP(in_features=in_features, out_features=out, hidden_features=kwargs.get(prefix + "_w", w),
                               num_hidden_layers=kwargs.get(prefix + "_d", d), skips=kwargs.get(prefix + "_skips", skips),
-                              multires=multires, out_activation=out_act, act="leaky_relu", composition_rank=rank, n_frames=n_frames)
+                              multires=multires, out_activation=out_act, act="leaky_relu", composition_rank=rank, n_frames=n_frames,
+                              precision=mlp_precision)
 
         self.mlp_deform = mlp("deform", 3, 128, 6, [3], kwargs.get("deform_multires", 6), "none")
         self.use_view_dep_rgb = kwargs.get("use_view_dep_rgb", False)

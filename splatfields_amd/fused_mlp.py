@@ -10,10 +10,16 @@ chip (library GEMMs serialise this contraction: 2.7 of the 3.9 ms of a PyTorch-R
 layers' *effective* weights as ordinary autograd tensors: for ResField layers (reference utils/resfields.py:378-405) the
 caller composes `W + delta(frame)` first and autograd carries dW on to W and the delta factors.  `FusedGeneralMLP` is the
 module-style wrapper.  No CPU path.
+
+`precision="bf16"` (opt-in; `set_mlp_precision` / SPLATFIELDS_MLP_PRECISION set the process default, "fp32") runs the two layer
+chains on the bf16 MFMA: weights and the chains' inputs are rounded to bfloat16 where they enter a matrix product, products and
+sums, biases, the running state, the epilogues and everything stored stay fp32, and the weight gradients come from the fp32
+kernel on those stored values (include/splatraster.h: sr_mlp_chain_bf16).
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 from typing import List, Optional, Sequence, Tuple
 
@@ -21,6 +27,37 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+
+
+PRECISIONS = ("fp32", "bf16")
+
+
+def _checked_precision(name) -> str:
+    if name not in PRECISIONS:
+        raise ValueError(f"unknown MLP precision {name!r}: expected one of {PRECISIONS}")
+    return name
+
+
+# process default of the fused MLP chains, read once: SPLATFIELDS_MLP_PRECISION=bf16 turns the bf16 MFMA path on for every
+# network that does not name a precision itself
+_MLP_PRECISION = _checked_precision(os.environ.get("SPLATFIELDS_MLP_PRECISION") or "fp32")
+
+
+def set_mlp_precision(name: str) -> str:
+    """Process default of the fused MLP chains: "fp32" (exact fp32 MFMA) or "bf16" (bf16 operands, fp32 accumulation).
+    Returns the previous setting."""
+    global _MLP_PRECISION
+    prev, _MLP_PRECISION = _MLP_PRECISION, _checked_precision(name)
+    return prev
+
+
+def mlp_precision() -> str:
+    return _MLP_PRECISION
+
+
+def resolve_precision(precision: Optional[str]) -> str:
+    """`None` -> the process default, at call time."""
+    return _MLP_PRECISION if precision is None else _checked_precision(precision)
 
 
 def pack_layer_weight(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width: int, out_tiles: int) -> torch.Tensor:
@@ -38,6 +75,21 @@ def pack_layer_weight(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width: int,
     kt = (mem_pad + reg_width) // 16
     v = Wp.view(out_tiles, 16, kt // 2, 2, 4, 4)            # (mt, m, c, tl, k, i)
     return v.permute(2, 0, 3, 4, 1, 5).contiguous().reshape(-1)   # (c, mt, tl, k, m, i)
+
+
+def pack_layer_weight_bf16(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width: int, out_tiles: int) -> torch.Tensor:
+    """PyTorch statement of the bf16 packing (the device packer sr_mlp_pack_bf16 is tested against it): the same padded matrix W'
+    as `pack_layer_weight`, rounded to bfloat16, in the K order of the 16x16x32 MFMA (csrc/mlp.hip):
+    bf16 (((c MT + mt) 64 + 16 k + m) 8 + j) = W'[16 mt + m][32 c + 16 (j >> 2) + 4 k + (j & 3)]."""
+    M, K = W.shape
+    n_reg = K - n_mem
+    Wp = W.new_zeros(16 * out_tiles, mem_pad + reg_width)
+    if n_mem:
+        Wp[:M, :n_mem] = W[:, :n_mem]
+    if n_reg:
+        Wp[:M, mem_pad:mem_pad + n_reg] = W[:, n_mem:]
+    v = Wp.to(torch.bfloat16).view(out_tiles, 16, (mem_pad + reg_width) // 32, 2, 4, 4)     # (mt, m, c, j >> 2, k, j & 3)
+    return v.permute(2, 0, 4, 1, 3, 5).contiguous().reshape(-1)                          # (c, mt, k, m, j >> 2, j & 3)
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -89,7 +141,8 @@ class _Plan:
     = weights[j].data_ptr() + offset -- and are patched per call (building ~40 descriptor structs per network and step in
     Python cost ~0.6 ms of host time per network; patching ~60 pointers costs a few tens of microseconds)."""
 
-    def __init__(self):
+    def __init__(self, precision: str = "fp32"):
+        self.bf16 = _checked_precision(precision) == "bf16"      # packed matrices are bfloat16 (biases stay fp32)
         self.jobs: List[dict] = []
         self.ops: List[dict] = []
         self.sizes: List[Tuple[int, int]] = []
@@ -108,7 +161,8 @@ class _Plan:
         n = len(self.jobs)
         jobs = (_lib.SrMlpPackJob * n)()
         ops = (_lib.SrMlpOp * n)()
-        binds, at = [], 0     # (struct, field, symbol, index, byte offset)
+        binds, at = [], 0     # (struct, field, symbol, index, byte offset); `at`: bytes, every piece a multiple of 16
+        wsize = 2 if self.bf16 else 4
         for j, (job, op, (wf, bf)) in enumerate(zip(self.jobs, self.ops, self.sizes)):
             J, O = jobs[j], ops[j]
             J.ld, J.transposed, J.row0, J.n_rows = job["ld"], job["transposed"], job["row0"], job["n_rows"]
@@ -119,10 +173,10 @@ class _Plan:
             O.src_row, O.epilogue, O.mask_row = op.get("src_row", 0), op["epilogue"], op.get("mask_row", 0)
             O.store_row, O.store_channels = op.get("store_row", 0), op.get("store_channels", 0)
             O.store_accumulate, O.keep_state = op.get("store_accumulate", 0), op.get("keep_state", 0)
-            binds.append((J, "dst", "buf", 0, 4 * at)); binds.append((O, "w_packed", "buf", 0, 4 * at))
+            binds.append((J, "dst", "buf", 0, at)); binds.append((O, "w_packed", "buf", 0, at))
             if bf:
-                binds.append((J, "bias_dst", "buf", 0, 4 * (at + wf))); binds.append((O, "bias", "buf", 0, 4 * (at + wf)))
-            at += wf + bf
+                binds.append((J, "bias_dst", "buf", 0, at + wsize * wf)); binds.append((O, "bias", "buf", 0, at + wsize * wf))
+            at += wsize * wf + 4 * bf
             for f, key in (("w", "w"), ("bias_src", "bias")):
                 if job.get(key) is not None:
                     binds.append((J, f) + tuple(job[key]))
@@ -136,20 +190,21 @@ class _Plan:
             if self._arrays is None:
                 self._freeze()
             jobs, ops, binds, total = self._arrays
-            buf = torch.empty(total, dtype=torch.float32, device=device)
+            buf = torch.empty(total // 4, dtype=torch.float32, device=device)
             ptrs = dict(ptrs, buf=(buf.data_ptr(),))
             for obj, field, sym, idx, off in binds:
                 setattr(obj, field, ptrs[sym][idx] + off)
-            _lib.check(lib.sr_mlp_pack(len(jobs), jobs, C.c_void_p(stream)))
-            _lib.check(lib.sr_mlp_chain(n_points, ht, len(ops), ops, slope, C.c_void_p(stream)))
+            pack, chain = (lib.sr_mlp_pack_bf16, lib.sr_mlp_chain_bf16) if self.bf16 else (lib.sr_mlp_pack, lib.sr_mlp_chain)
+            _lib.check(pack(len(jobs), jobs, C.c_void_p(stream)))
+            _lib.check(chain(n_points, ht, len(ops), ops, slope, C.c_void_p(stream)))
         return buf      # alive until the caller drops it; the stream orders its reuse
 
 
-def _forward_plan(shape: _Shape, save: bool) -> _Plan:
-    key = ("fwd", save)
+def _forward_plan(shape: _Shape, save: bool, precision: str = "fp32") -> _Plan:
+    key = ("fwd", save, precision)
     if key not in shape.plans:
         H, L = shape.hidden, shape.n_layers
-        b = _Plan()
+        b = _Plan(precision)
         for j in range(L):
             last = j == L - 1
             rows, cols = shape.layer_dims[j]
@@ -167,7 +222,7 @@ def _forward_plan(shape: _Shape, save: bool) -> _Plan:
     return shape.plans[key]
 
 
-def _forward(shape: _Shape, x0: torch.Tensor, weights, biases, slope: float, save: bool):
+def _forward(shape: _Shape, x0: torch.Tensor, weights, biases, slope: float, save: bool, precision: str = "fp32"):
     """x0 [N, mem_pad] -> (y [N, out], acts [L-1, N, hidden] or None, signs [L-1, N, 4] int32 or None: one bit per activation,
     set where it is > 0, in the layout of SrMlpOp.sign_store)."""
     lib = _lib.load()
@@ -179,15 +234,15 @@ def _forward(shape: _Shape, x0: torch.Tensor, weights, biases, slope: float, sav
             "acts": [acts.data_ptr() + 4 * j * n * H for j in range(L - 1)] if save else (),
             "signs": [signs.data_ptr() + 16 * j * n for j in range(L - 1)] if save else ()}
     with torch.cuda.device(dev):
-        _forward_plan(shape, save).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
+        _forward_plan(shape, save, precision).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
     return y, acts, signs
 
 
-def _backward_plan(shape: _Shape, need_input: bool, bits: bool) -> _Plan:
-    key = ("bwd", need_input, bits)
+def _backward_plan(shape: _Shape, need_input: bool, bits: bool, precision: str = "fp32") -> _Plan:
+    key = ("bwd", need_input, bits, precision)
     if key not in shape.plans:
         H, L = shape.hidden, shape.n_layers
-        b = _Plan()
+        b = _Plan(precision)
         wrote_input = False        # dL/dx0 is not cleared beforehand: the first layer that feeds it (the topmost) stores, incl. zero padding
         for j in range(L - 1, -1, -1):
             ld = shape.layer_dims[j][1]
@@ -223,7 +278,7 @@ def _top_gradient(lib, shape: _Shape, y, dY, slope: float, G):
                                            slope, C.c_void_p(G.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
 
-def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input: bool, signs=None):
+def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input: bool, signs=None, precision: str = "fp32"):
     """-> (dL/dx0 [N, mem_pad] or None, G [N, out_pad] = dZ of the last layer (zero-padded), dz [L-1, N, hidden] = dZ of the others).
     leaky'(.) of the hidden layers is read off `signs` (16 bytes per point and layer) when given, else off `acts` (4 * hidden)."""
     lib = _lib.load()
@@ -236,7 +291,7 @@ def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input:
             "acts": [acts.data_ptr() + 4 * j * n * H for j in range(L - 1)], "dz": [dz.data_ptr() + 4 * j * n * H for j in range(L - 1)],
             "signs": [signs.data_ptr() + 16 * j * n for j in range(L - 1)] if signs is not None else ()}
     with torch.cuda.device(dev):
-        _backward_plan(shape, need_input, signs is not None).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
+        _backward_plan(shape, need_input, signs is not None, precision).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
     return dx0, G, dz
 
 
@@ -306,7 +361,7 @@ def _weight_grads(shape: _Shape, x0, acts, G, dz, weights):
 
 class _FusedMLPFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h_in, shape: _Shape, slope: float, grad_enabled: bool, *params):
+    def forward(ctx, h_in, shape: _Shape, slope: float, grad_enabled: bool, precision: str, *params):
         L = shape.n_layers
         weights = [_f32c(p) for p in params[:L]]
         biases = [_f32c(p) for p in params[L:]]
@@ -314,9 +369,9 @@ class _FusedMLPFn(torch.autograd.Function):
         # needs_input_grad reflects requires_grad of the inputs, not the grad mode (inside forward() grad mode is always off):
         # under torch.no_grad() nothing will run backward, so the [L-1, N, hidden] activation stack is neither allocated nor written
         need = grad_enabled and any(ctx.needs_input_grad)
-        y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need)
+        y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need, precision=precision)
         if need:
-            ctx.shape, ctx.slope = shape, slope
+            ctx.shape, ctx.slope, ctx.precision = shape, slope, precision      # the backward runs in the precision of its forward
             ctx.save_for_backward(x0, acts, signs, y, *weights)
         return y
 
@@ -327,13 +382,13 @@ class _FusedMLPFn(torch.autograd.Function):
         x0, acts, signs, y, *weights = ctx.saved_tensors
         L, d_in = shape.n_layers, shape.d_in
         need_input = ctx.needs_input_grad[0]
-        dx0, G, dz = _backward(shape, x0, acts, y, dY.to(torch.float32).contiguous(), weights, slope, need_input, signs)
+        dx0, G, dz = _backward(shape, x0, acts, y, dY.to(torch.float32).contiguous(), weights, slope, need_input, signs, ctx.precision)
         dWs, dbs = [None] * L, [None] * L
-        if any(ctx.needs_input_grad[4:]):
+        if any(ctx.needs_input_grad[5:]):
             dWs, dbs = _weight_grads(shape, x0, acts, G, dz, weights)
-            dWs = [g if ctx.needs_input_grad[4 + j] else None for j, g in enumerate(dWs)]
-            dbs = [g if ctx.needs_input_grad[4 + L + j] else None for j, g in enumerate(dbs)]
-        return (dx0[:, :d_in] if need_input else None, None, None, None, *dWs, *dbs)
+            dWs = [g if ctx.needs_input_grad[5 + j] else None for j, g in enumerate(dWs)]
+            dbs = [g if ctx.needs_input_grad[5 + L + j] else None for j, g in enumerate(dbs)]
+        return (dx0[:, :d_in] if need_input else None, None, None, None, None, *dWs, *dbs)
 
 
 class _FusedMLPPointsFn(torch.autograd.Function):
@@ -343,7 +398,8 @@ class _FusedMLPPointsFn(torch.autograd.Function):
     and step for the encoding, the concatenations, the padding and their backward."""
 
     @staticmethod
-    def forward(ctx, xyz, feat, time, shape: _Shape, slope: float, multires: int, time_multires: int, grad_enabled: bool, *params):
+    def forward(ctx, xyz, feat, time, shape: _Shape, slope: float, multires: int, time_multires: int, grad_enabled: bool, precision: str,
+                *params):
         lib = _lib.load()
         L = shape.n_layers
         weights = [_f32c(p) for p in params[:L]]
@@ -360,9 +416,9 @@ class _FusedMLPPointsFn(torch.autograd.Function):
                                                 C.c_void_p(t32.data_ptr()) if t32 is not None else None, C.c_void_p(x0.data_ptr()),
                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         need = grad_enabled and any(ctx.needs_input_grad)
-        y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need)
+        y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need, precision=precision)
         if need:
-            ctx.shape, ctx.slope, ctx.multires, ctx.n_feat = shape, slope, multires, n_feat
+            ctx.shape, ctx.slope, ctx.multires, ctx.n_feat, ctx.precision = shape, slope, multires, n_feat, precision
             ctx.save_for_backward(x32, x0, acts, signs, y, *weights)
         return y
 
@@ -374,7 +430,8 @@ class _FusedMLPPointsFn(torch.autograd.Function):
         x32, x0, acts, signs, y, *weights = ctx.saved_tensors
         L, dev, n = shape.n_layers, x0.device, x0.shape[0]
         need_xyz, need_feat = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.n_feat > 0
-        dx0, G, dz = _backward(shape, x0, acts, y, dY.to(torch.float32).contiguous(), weights, slope, need_xyz or need_feat, signs)
+        dx0, G, dz = _backward(shape, x0, acts, y, dY.to(torch.float32).contiguous(), weights, slope, need_xyz or need_feat, signs,
+                               ctx.precision)
         d_xyz = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_xyz else None
         d_feat = torch.empty(n, ctx.n_feat, dtype=torch.float32, device=dev) if need_feat else None
         if need_xyz or need_feat:
@@ -384,20 +441,22 @@ class _FusedMLPPointsFn(torch.autograd.Function):
                                                      C.c_void_p(d_feat.data_ptr()) if need_feat else None,
                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         dWs, dbs = [None] * L, [None] * L
-        if any(ctx.needs_input_grad[8:]):
+        if any(ctx.needs_input_grad[9:]):
             dWs, dbs = _weight_grads(shape, x0, acts, G, dz, weights)
-            dWs = [g if ctx.needs_input_grad[8 + j] else None for j, g in enumerate(dWs)]
-            dbs = [g if ctx.needs_input_grad[8 + L + j] else None for j, g in enumerate(dbs)]
-        return (d_xyz, d_feat, None, None, None, None, None, None, *dWs, *dbs)
+            dWs = [g if ctx.needs_input_grad[9 + j] else None for j, g in enumerate(dWs)]
+            dbs = [g if ctx.needs_input_grad[9 + L + j] else None for j, g in enumerate(dbs)]
+        return (d_xyz, d_feat, None, None, None, None, None, None, None, *dWs, *dbs)
 
 
 def fused_general_mlp_points(xyz: torch.Tensor, feat: Optional[torch.Tensor], multires: int, weights: Sequence[torch.Tensor],
                              biases: Sequence[torch.Tensor], skips: Sequence[int] = (), negative_slope: float = 0.01,
-                             _shape: Optional[_Shape] = None, time: Optional[torch.Tensor] = None, time_multires: int = 0) -> torch.Tensor:
+                             _shape: Optional[_Shape] = None, time: Optional[torch.Tensor] = None, time_multires: int = 0,
+                             precision: Optional[str] = None) -> torch.Tensor:
     """`fused_general_mlp(cat([positional_encoding(xyz, multires), feat, positional_encoding(time, time_multires)]), ...)` with the
     input matrix built on the device in one kernel: xyz [N, 3], feat [N, F] or None, time [N] / [N, 1] or None (one time per point,
-    no gradient), float32 on a HIP device."""
+    no gradient), float32 on a HIP device.  `precision`: "fp32", "bf16" or None (the process default, set_mlp_precision)."""
     _lib.load()
+    precision = resolve_precision(precision)
     if not xyz.is_cuda:
         raise RuntimeError("fused_general_mlp_points has no CPU path: tensors must be on a HIP ('cuda') device")
     n_feat = 0 if feat is None else feat.shape[1]
@@ -416,15 +475,17 @@ def fused_general_mlp_points(xyz: torch.Tensor, feat: Optional[torch.Tensor], mu
     if xyz.shape[0] == 0:
         return xyz.new_zeros(0, shape.out_features) + 0.0 * (xyz.sum() + sum(w.sum() for w in weights) + sum(b.sum() for b in biases))
     return _FusedMLPPointsFn.apply(xyz, feat, time, shape, float(negative_slope), int(max(multires, 0)), time_multires,
-                                   torch.is_grad_enabled(), *weights, *biases)
+                                   torch.is_grad_enabled(), precision, *weights, *biases)
 
 
 def fused_general_mlp(h_in: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], skips: Sequence[int] = (),
-                      negative_slope: float = 0.01, _shape: Optional[_Shape] = None) -> torch.Tensor:
+                      negative_slope: float = 0.01, _shape: Optional[_Shape] = None, precision: Optional[str] = None) -> torch.Tensor:
     """h_in [N, d_in] (positional encoding ++ features, as the reference builds it) -> [N, out_features]; differentiable with
     respect to h_in, the weights and the biases.  weights[j]: [out_j, in_j] on the device, biases[j]: [out_j]; in_0 = d_in,
-    in_j = hidden (+ d_in when j - 1 is in `skips`); hidden width 64 or 128."""
+    in_j = hidden (+ d_in when j - 1 is in `skips`); hidden width 64 or 128.  `precision`: "fp32" (exact fp32 MFMA), "bf16" (bf16
+    matrix operands, fp32 accumulation and fp32 everything else) or None: the process default (set_mlp_precision)."""
     _lib.load()
+    precision = resolve_precision(precision)
     if not h_in.is_cuda:
         raise RuntimeError("fused_general_mlp has no CPU path: tensors must be on a HIP ('cuda') device")
     shape = _shape or _Shape(weights, h_in.shape[1] if h_in.dim() == 2 else -1, skips)
@@ -444,7 +505,7 @@ def fused_general_mlp(h_in: torch.Tensor, weights: Sequence[torch.Tensor], biase
         raise ValueError("h_in must be float32 (the reference network runs in fp32)")
     if h_in.shape[0] == 0:      # nothing to launch; keep the graph connected so that parameters still receive (zero) gradients
         return h_in.new_zeros(0, shape.out_features) + 0.0 * (h_in.sum() + sum(w.sum() for w in weights) + sum(b.sum() for b in biases))
-    return _FusedMLPFn.apply(h_in, shape, float(negative_slope), torch.is_grad_enabled(), *weights, *biases)
+    return _FusedMLPFn.apply(h_in, shape, float(negative_slope), torch.is_grad_enabled(), precision, *weights, *biases)
 
 
 class _PointLinearFn(torch.autograd.Function):
@@ -520,11 +581,12 @@ class FusedGeneralMLP:
     swapped in through `weights` / `biases`) and the static shape."""
 
     def __init__(self, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], d_in: int, skips: Sequence[int] = (),
-                 negative_slope: float = 0.01):
+                 negative_slope: float = 0.01, precision: Optional[str] = None):
+        self.precision = None if precision is None else _checked_precision(precision)    # None: the process default at call time
         self.weights, self.biases = list(weights), list(biases)
         self.slope = float(negative_slope)
         self.shape = _Shape(self.weights, d_in, skips)
         self.d_in, self.hidden, self.out_features = self.shape.d_in, self.shape.hidden, self.shape.out_features
 
     def __call__(self, h_in: torch.Tensor) -> torch.Tensor:
-        return fused_general_mlp(h_in, self.weights, self.biases, negative_slope=self.slope, _shape=self.shape)
+        return fused_general_mlp(h_in, self.weights, self.biases, negative_slope=self.slope, _shape=self.shape, precision=self.precision)

@@ -27,7 +27,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .fused_mlp import _Shape, fused_general_mlp, fused_general_mlp_points
+from .fused_mlp import _Shape, _checked_precision, fused_general_mlp, fused_general_mlp_points
 
 
 def positional_encoding(x: torch.Tensor, multires: int) -> torch.Tensor:
@@ -194,8 +194,11 @@ _SLOPES = {"leaky_relu": 0.01, "relu": 0.0}
 class GeneralMLP(nn.Module):
     def __init__(self, in_features: int = 3, out_features: int = 3, hidden_features: int = 128, num_hidden_layers: int = 8,
                  skips: Sequence[int] = (4,), multires: int = 6, out_activation: str = "none", act: str = "relu",
-                 composition_rank: int = 0, n_frames: int = 100):
+                 composition_rank: int = 0, n_frames: int = 100, precision: Optional[str] = None):
         super().__init__()
+        # precision of the fused layer chains: "fp32", "bf16" or None = the process default at call time (set_mlp_precision);
+        # a plain attribute that may be set later, not part of the state dict
+        self.precision = None if precision is None else _checked_precision(precision)
         if act not in _SLOPES:
             raise NotImplementedError(f"act={act!r}: the fused kernels implement leaky_relu and relu")
         if out_activation not in _OUT_ACTIVATIONS:
@@ -230,15 +233,18 @@ class GeneralMLP(nn.Module):
         of the feature vector the reference passes in (utils/time_utils.py:455-456) -- inside the input kernel."""
         weights = compose_resfield_weights(list(self.net), frame_id)
         biases = [layer.bias for layer in self.net]
+        # a module without a precision of its own calls exactly as before the option existed: the fused op resolves the process
+        # default (set_mlp_precision) at call time
+        pk = {} if self.precision is None else {"precision": _checked_precision(self.precision)}
         if xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.dtype == torch.float32 and \
                 (xyz_feat is None or (xyz_feat.dtype == torch.float32 and xyz_feat.dim() == 2)):
             # the usual case: positions + features (+ time) -> the padded input matrix in one kernel
             h = fused_general_mlp_points(xyz, xyz_feat, self.multires, weights, biases, skips=self.skips, negative_slope=self.slope,
-                                         _shape=self._static_shape(), time=time, time_multires=time_multires)
+                                         _shape=self._static_shape(), time=time, time_multires=time_multires, **pk)
             return self.out_act(h)
         h_in = positional_encoding(xyz, self.multires)
         parts = [h_in] + ([xyz_feat] if xyz_feat is not None else []) + \
             ([positional_encoding(time.reshape(-1, 1), time_multires)] if time is not None else [])
         h_in = torch.cat(parts, dim=-1) if len(parts) > 1 else h_in
-        h = fused_general_mlp(h_in, weights, biases, skips=self.skips, negative_slope=self.slope, _shape=self._static_shape())
+        h = fused_general_mlp(h_in, weights, biases, skips=self.skips, negative_slope=self.slope, _shape=self._static_shape(), **pk)
         return self.out_act(h)
