@@ -558,7 +558,8 @@ int sr_resfield_backward(int n_jobs, const SrResFieldJob* jobs, const long long*
  * accumulated in 64-bit fixed point with integer atomics -- bit-reproducible, no floating-point atomics: the (point, plane)
  * pairs are binned by tile of the plane and every tile is summed in LDS by one workgroup; `workspace` holds
  * sr_triplane_backward_workspace(N, C, H, W) bytes (tile counters and the binned lists; needed only with dL_dplanes; 0 for
- * unsupported sizes: C a multiple of 4, <= 128). */
+ * unsupported sizes: C a multiple of 4, <= 128).  The limit of 128 channels is the plane gradient's (its LDS tile): the
+ * forward and a backward with dL_dpoints alone take any multiple of 4. */
 size_t sr_triplane_backward_workspace(int n_points, int channels, int height, int width);
 int sr_triplane_forward(int n_points, int channels, int height, int width, const float* planes, float* planes_texel_major,
                         const float* points, float* out, void* hip_stream);

@@ -893,11 +893,14 @@ int sr_triplane_forward(int n_points, int channels, int height, int width, const
 
 int sr_triplane_backward(int n_points, int channels, int height, int width, const float* planes_texel_major, const float* points,
                          const float* dL_dout, float* dL_dplanes, float* dL_dpoints, void* workspace, void* hip_stream) {
-    if (n_points < 0 || !planes_texel_major || (n_points > 0 && (!points || !dL_dout)) || (dL_dplanes && !workspace))
+    if (n_points < 0 || !planes_texel_major || (n_points > 0 && (!points || !dL_dout)))
         return fail("bad arguments to sr_triplane_backward");
+    // the size limits are checked before the workspace: a caller that sized it with sr_triplane_backward_workspace has none
+    // (0 bytes) exactly when the sizes are unsupported, and is told which limit it hit
     const int rc = sr::launch_triplane_backward(n_points, channels, height, width, planes_texel_major, points, dL_dout, dL_dplanes, dL_dpoints,
                                                 workspace, static_cast<hipStream_t>(hip_stream));
-    if (rc == 1) return fail("sr_triplane_backward: channels must be a multiple of 4 in 4..128, height * width <= 2^30, 12 n_points < 2^32");
+    if (rc == 1) return fail("sr_triplane_backward: channels must be a positive multiple of 4 (with dL_dplanes: in 4..128), height * width <= 2^30, 12 n_points < 2^32");
+    if (rc == 3) return fail("sr_triplane_backward: dL_dplanes needs a workspace of sr_triplane_backward_workspace bytes");
     if (rc) return fail("sr_triplane_backward: clearing the tile counters failed");
     return check_hip(hipGetLastError(), "triplane_backward");
 }

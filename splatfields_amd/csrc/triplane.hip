@@ -315,10 +315,14 @@ size_t triplane_backward_workspace(int N, int C, int H, int W) {
     return tp_carve(nullptr, N, C, H, W, nullptr);
 }
 
-// `workspace`: triplane_backward_workspace(N, C, H, W) bytes (tile counters, tile starts, the binned point lists, max |g|)
+// `workspace`: triplane_backward_workspace(N, C, H, W) bytes (tile counters, tile starts, the binned point lists, max |g|).
+// The tile limit (C <= 128) belongs to the plane gradient alone: the gather of dL/dpoints takes any C the forward takes.
+// Returns 1 for unsupported sizes, 3 for a plane gradient without a workspace (both before any launch), 2 if clearing fails.
 int launch_triplane_backward(int N, int C, int H, int W, const float* planes_hwc, const float* pts, const float* g, float* d_planes_chw,
                              float* d_pts, void* workspace, hipStream_t st) {
-    if (C <= 0 || (C & 3) || tp_tile(C) == 0 || H <= 0 || W <= 0 || (size_t)H * W > (1u << 30) || (long long)N * 12 > 0xffffffffll) return 1;
+    if (C <= 0 || (C & 3) || (d_planes_chw && tp_tile(C) == 0) || H <= 0 || W <= 0 || (size_t)H * W > (1u << 30) ||
+        (long long)N * 12 > 0xffffffffll) return 1;
+    if (d_planes_chw && !workspace) return 3;
     if (d_planes_chw) {
         TpBins b;
         tp_carve(workspace, N, C, H, W, &b);
