@@ -27,12 +27,18 @@ __device__ __forceinline__ uint32_t densify_decide(int i, const float* __restric
                                                    const float* __restrict__ denom, const float* __restrict__ max_radii2D,
                                                    const DensifyArgs a) {
     float ms = -__builtin_inff();
-    for (int c = 0; c < scale_cols; ++c) ms = fmaxf(ms, expf(log_scales[(size_t)i * scale_cols + c]));   // get_scaling.max(dim=1)
+    bool nan_scale = false;
+    for (int c = 0; c < scale_cols; ++c) {                  // get_scaling.max(dim=1)
+        const float e = expf(log_scales[(size_t)i * scale_cols + c]);
+        nan_scale |= e != e;
+        ms = fmaxf(ms, e);
+    }
+    if (nan_scale) ms = __builtin_nanf("");                 // torch.max propagates NaN (fmaxf drops it): no test on ms holds
     float grad = grad_accum[i] / denom[i];
     if (grad != grad) grad = 0.0f;                          // grads[grads.isnan()] = 0
-    const bool hot = grad >= a.grad_threshold;
-    const bool clone = hot && ms <= a.percent_dense * a.extent;
-    const bool split = hot && ms > a.percent_dense * a.extent;
+    // the clone pass tests torch.norm(grads, dim=-1), the split pass the signed value (:396, :360)
+    const bool clone = fabsf(grad) >= a.grad_threshold && ms <= a.percent_dense * a.extent;
+    const bool split = grad >= a.grad_threshold && ms > a.percent_dense * a.extent;
     const float opac = 1.0f / (1.0f + expf(-opacity_logit[i]));
     // the final prune: opacity, screen size (on max_radii2D as densification_postfix left it -- the caller passes what the
     // reference would test, see densify.py), world size

@@ -13,7 +13,9 @@ Semantics restated (file:line of the reference):
            xyz = build_rotation(q) @ normal(0, scale) + xyz, scale / 1.6, everything else copied; the parent is removed (:355-380)
   * prune  opacity < min_opacity, and -- if max_screen_size -- max_radii2D > max_screen_size or max(scale) > 0.1 extent (:418-423)
     (`densification_postfix` :349-353 has zeroed max_radii2D by then, so the screen-size test of the reference never fires;
-    `screen_test_on_accumulated_radii=True` tests the radii accumulated before the densification instead)
+    `screen_test_on_accumulated_radii=True` tests the radii accumulated before the densification instead: a row and its clone
+    on the row's radius; split children are new splats and start at radius 0, like every row the reference appends)
+  * a row with NaN in a log-scale is neither cloned nor split (torch.max propagates NaN: neither comparison holds)
   * statistics are reset for every row, Adam moments of new rows are zero                    (:317-320, :349-353)
 Row order of the result = the reference's: surviving originals, clones, first children, second children.
 The normal samples come from ``unit_normals`` [2, N, 3] (row k of splat i feeds its k-th child), default ``torch.randn``.
@@ -21,6 +23,7 @@ The normal samples come from ``unit_normals`` [2, N, 3] (row k of splat i feeds 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import torch
@@ -48,7 +51,7 @@ def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional
     dev, n = xyz.device, xyz.shape[0]
     f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
     src = {k: f32(params[k]) for k in PARAM_NAMES}
-    scale_cols = src["scaling"].reshape(n, -1).shape[1]
+    scale_cols = math.prod(src["scaling"].shape[1:])        # not reshape(n, -1): N may be 0
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if unit_normals is None:
@@ -66,8 +69,10 @@ def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional
         kept, clones, c1, c2, total = [int(c) for c in counts]
 
         def gather(t, mode):
-            row = t[0].numel() if n > 0 else int(torch.tensor(t.shape[1:]).prod().item()) if t.dim() > 1 else 1
+            row = math.prod(t.shape[1:])
             out = torch.empty((total,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
+            if n == 0 or total == 0:                         # nothing to write: the reference returns tensors of 0 rows
+                return out
             _lib.check(lib.sr_densify_gather(n, row, _ptr(t), _ptr(out), _ptr(dest), mode, _ptr(src["scaling"]), scale_cols,
                                              _ptr(src["rotation"]), _ptr(unit_normals), stream))
             return out
