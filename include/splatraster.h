@@ -38,6 +38,10 @@
  *           host) and utils/image_utils.py:19-21 (`psnr`, train.py:387-396), with the 8-bit quantisation of the image files
  *           in between (torchvision `save_image`, render.py:282 `to8b`): a batch of views in one kernel plus a fixed-order
  *           reduction.
+ *   sr_splat_reg_forward / sr_splat_reg_backward, sr_depth_l1_forward / sr_depth_l1_backward
+ *        <- reference train.py:195-201 (`lambda_norm`, `lambda_norm_mean`), :244-246 (`lambda_opacity`) and :224-229
+ *           (`lambda_depthl1`): the tail of the objective between `render()` and `loss.backward()`, each a streaming pass and a
+ *           fixed-order reduction forward and one kernel backward.
  *   sr_adam_step
  *        <- reference train.py:314-322 (`gaussians.optimizer.step()`), the `torch.optim.Adam` of scene/gaussian_model.py:130-139:
  *           every tensor of the step in one launch.
@@ -360,6 +364,47 @@ int sr_moran_weights(int n_points, int k, float eps, const float* points, const 
 int sr_moran_weights_backward(int n_points, int k, float eps, const float* points, const int* nn_ix, const unsigned* rev_start,
                               const unsigned* rev_edges, const float* dL_dweights, void* edges, float* dL_dpoints,
                               void* hip_stream);
+
+/* The splat regularisers of the training objective, for means3D [n,3] and the opacities [n] (the reference's [n,1] tensor):
+ *   norm        = mean_i |x_i|                                      reference train.py:195-197 (`lambda_norm`)
+ *   norm_mean   = mean_i |x_i - m|,  m = mean_i x_i, detached        reference train.py:198-201 (`lambda_norm_mean`); m is rounded
+ *                                                                   to float32 before the subtraction, as the float32 `mean` is
+ *   opacity_reg = mean_i (o_i - 1)^2                                reference train.py:244-246 (`lambda_opacity`)
+ *   loss        = lambda_norm norm + lambda_norm_mean norm_mean + lambda_opacity opacity_reg.
+ * A term whose weight is 0 is skipped: it is neither computed nor read (its tensor may be NULL) and is written as 0.
+ * sr_splat_reg_forward writes out[8] = loss | norm | norm_mean | opacity_reg | m (three floats) | 0 to device memory.
+ * `workspace`: sr_splat_reg_workspace_bytes(n) bytes (0 for n <= 0), the per-workgroup partial sums in double, which one
+ * workgroup adds in an order the shape alone fixes.  Launches: 2, or 3 with the centred norm (the mean comes before its pass).
+ * sr_splat_reg_backward, one launch, writes with g = *upstream read on the device and m = out[4..6] of the forward
+ *   dL_dmeans3D[i] (may be NULL) = g / n (lambda_norm x_i / |x_i| + lambda_norm_mean (x_i - m) / |x_i - m|),
+ *   dL_dopacity[i] (may be NULL) = g lambda_opacity 2 (o_i - 1) / n;
+ * a vector of length 0 contributes exactly 0 (torch's `norm` backward).  `out` may be NULL when lambda_norm_mean = 0.
+ * Every row is evaluated in double from its float32 inputs with the IEEE square root and division and rounded to float32 once
+ * where it is stored.  All tensors are contiguous and 4-byte aligned; means3D moves as 16-byte vectors over the flat array for
+ * any such base (a slice with a storage offset included), the opacities and a gradient where their address agrees with the
+ * rows' modulo 16, element by element where not.  n = 0 is valid and launches nothing.  No floating-point atomics, nothing
+ * waits for the device: identical bits from call to call. */
+size_t sr_splat_reg_workspace_bytes(int n_splats);
+int sr_splat_reg_forward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                         double lambda_opacity, void* workspace, float* out, void* hip_stream);
+int sr_splat_reg_backward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                          double lambda_opacity, const float* out, const float* upstream, float* dL_dmeans3D, float* dL_dopacity,
+                          void* hip_stream);
+
+/* Depth L1 (reference train.py:224-229, `lambda_depthl1`): for depth, gt_depth [batch, height, width] float32, contiguous,
+ *   valid = gt_depth > 0,   depth_l1 = mean over ALL batch height width elements of |depth valid - gt_depth valid|
+ * (`F.l1_loss` divides by every element, the masked ones included).  Inputs are assumed finite.
+ * sr_depth_l1_forward writes out[1 + batch] = the mean over everything | the mean over each item.  `workspace`:
+ * sr_depth_l1_workspace_bytes(batch, height, width) bytes (0 for a shape out of range or an empty batch).  2 launches.
+ * sr_depth_l1_backward, one launch, writes dL_ddepth = g sign(depth - gt_depth) valid / (batch height width), sign(0) = 0,
+ * g = upstream[0]; with upstream_per_item, g = upstream[b] and the divisor is height width: the gradient of sum_b g_b item_b.
+ * batch = 0 is valid and launches nothing; a non-positive image size is an error.  4-byte aligned bases; 16-byte vectors
+ * wherever the tensors agree modulo 16.  No floating-point atomics, nothing waits for the device. */
+size_t sr_depth_l1_workspace_bytes(int batch, int height, int width);
+int sr_depth_l1_forward(int batch, int height, int width, const float* depth, const float* gt_depth, void* workspace, float* out,
+                        void* hip_stream);
+int sr_depth_l1_backward(int batch, int height, int width, const float* depth, const float* gt_depth, const float* upstream,
+                         int upstream_per_item, float* dL_ddepth, void* hip_stream);
 
 /* Densification / pruning of the splat set on the device: reference scene/gaussian_model.py:411-425 (`densify_and_prune`) with
  * :394-409 (`densify_and_clone`), :355-380 (`densify_and_split`, N = 2), :306-353 (`densification_postfix`) and :272-304

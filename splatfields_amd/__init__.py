@@ -1,7 +1,8 @@
 """MI355X-native differentiable Gaussian-splat rasterizer behind SplatFields' render() boundary."""
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 from .render import render  # noqa: F401
-from .losses import l1_loss, photometric_loss, ssim  # noqa: F401
+from .losses import (centered_position_norm, depth_l1_loss, l1_loss, opacity_regularizer, photometric_loss, position_norm,  # noqa: F401
+                     splat_regularizers, ssim, training_objective)
 from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
 from .optim import SplatAdam  # noqa: F401

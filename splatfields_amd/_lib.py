@@ -132,6 +132,13 @@ SYMBOLS = {
                                    C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "sr_adam_step": (C.c_int, [C.c_int, C.POINTER(SrAdamJob), C.c_void_p, C.c_longlong, C.c_void_p]),
+    "sr_splat_reg_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "sr_splat_reg_forward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_splat_reg_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "sr_depth_l1_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sr_depth_l1_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_depth_l1_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sr_densify_workspace_bytes": (C.c_size_t, [C.c_int]),
     "sr_densify_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),

@@ -760,6 +760,67 @@ int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible
     return check_hip(hipGetLastError(), "adam_step");
 }
 
+size_t sr_splat_reg_workspace_bytes(int n_splats) { return sr::splat_reg_workspace_bytes(n_splats); }
+
+int sr_splat_reg_forward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                         double lambda_opacity, void* workspace, float* out, void* hip_stream) {
+    if (n_splats < 0) return fail("bad arguments to sr_splat_reg_forward: negative splat count");
+    if (!(lambda_norm == lambda_norm) || !(lambda_norm_mean == lambda_norm_mean) || !(lambda_opacity == lambda_opacity))
+        return fail("bad arguments to sr_splat_reg_forward: a weight is NaN");
+    if (n_splats == 0) return 0;
+    if (!workspace || !out) return fail("null pointer in sr_splat_reg_forward");
+    if ((lambda_norm != 0.0 || lambda_norm_mean != 0.0) && !means3D) return fail("null pointer in sr_splat_reg_forward: means3D is read by the norm terms");
+    if (lambda_opacity != 0.0 && !opacity) return fail("null pointer in sr_splat_reg_forward: opacity is read by the opacity term");
+    if ((reinterpret_cast<uintptr_t>(means3D) | reinterpret_cast<uintptr_t>(opacity)) & 3u) return fail("sr_splat_reg_forward: tensors must be 4-byte aligned");
+    sr::launch_splat_reg_forward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, workspace, out,
+                                 static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "splat_reg_forward");
+}
+
+int sr_splat_reg_backward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                          double lambda_opacity, const float* out, const float* upstream, float* dL_dmeans3D, float* dL_dopacity,
+                          void* hip_stream) {
+    if (n_splats < 0) return fail("bad arguments to sr_splat_reg_backward: negative splat count");
+    if (!(lambda_norm == lambda_norm) || !(lambda_norm_mean == lambda_norm_mean) || !(lambda_opacity == lambda_opacity))
+        return fail("bad arguments to sr_splat_reg_backward: a weight is NaN");
+    if (n_splats == 0 || (!dL_dmeans3D && !dL_dopacity)) return 0;
+    if (!upstream) return fail("null pointer in sr_splat_reg_backward");
+    if (dL_dmeans3D && !means3D) return fail("null pointer in sr_splat_reg_backward: dL_dmeans3D without means3D");
+    if (dL_dopacity && !opacity) return fail("null pointer in sr_splat_reg_backward: dL_dopacity without opacity");
+    if (dL_dmeans3D && lambda_norm_mean != 0.0 && !out) return fail("null pointer in sr_splat_reg_backward: the centred norm needs the mean in `out` of the forward");
+    if ((reinterpret_cast<uintptr_t>(means3D) | reinterpret_cast<uintptr_t>(opacity) | reinterpret_cast<uintptr_t>(dL_dmeans3D) |
+         reinterpret_cast<uintptr_t>(dL_dopacity)) & 3u) return fail("sr_splat_reg_backward: tensors must be 4-byte aligned");
+    sr::launch_splat_reg_backward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, out, upstream, dL_dmeans3D,
+                                  dL_dopacity, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "splat_reg_backward");
+}
+
+size_t sr_depth_l1_workspace_bytes(int batch, int height, int width) { return sr::depth_l1_workspace_bytes(batch, height, width); }
+
+int sr_depth_l1_forward(int batch, int height, int width, const float* depth, const float* gt_depth, void* workspace, float* out,
+                        void* hip_stream) {
+    if (batch < 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_depth_l1_forward: the image size must be positive and the batch not negative");
+    if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_forward");
+    if (batch == 0) return 0;
+    if (!depth || !gt_depth || !workspace || !out) return fail("null pointer in sr_depth_l1_forward");
+    if ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(gt_depth)) & 3u) return fail("sr_depth_l1_forward: tensors must be 4-byte aligned");
+    sr::launch_depth_l1_forward(batch, height, width, depth, gt_depth, workspace, out, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "depth_l1_forward");
+}
+
+int sr_depth_l1_backward(int batch, int height, int width, const float* depth, const float* gt_depth, const float* upstream,
+                         int upstream_per_item, float* dL_ddepth, void* hip_stream) {
+    if (batch < 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_depth_l1_backward: the image size must be positive and the batch not negative");
+    if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_backward");
+    if (batch == 0) return 0;
+    if (!depth || !gt_depth || !upstream || !dL_ddepth) return fail("null pointer in sr_depth_l1_backward");
+    if ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(gt_depth) | reinterpret_cast<uintptr_t>(dL_ddepth)) & 3u)
+        return fail("sr_depth_l1_backward: tensors must be 4-byte aligned");
+    sr::launch_depth_l1_backward(batch, height, width, depth, gt_depth, upstream, upstream_per_item != 0, dL_ddepth,
+                                 static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "depth_l1_backward");
+}
+
 size_t sr_densify_workspace_bytes(int n) { return sr::densify_workspace_bytes(n); }
 
 int sr_densify_plan(int n, const float* log_scales, int scale_cols, const float* opacity_logits, const float* grad_accum,

@@ -120,6 +120,19 @@ void launch_image_metrics(int batch, int H, int W, const float* pred, const long
                           const long long* gt_strides, const float* mask, long long mask_item_stride, int quantize, void* workspace,
                           float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, hipStream_t st);
 
+// objective.hip: arguments are checked by the caller (sr_splat_reg_*, sr_depth_l1_*); n > 0, batch > 0
+size_t splat_reg_workspace_bytes(long long n);
+void launch_splat_reg_forward(long long n, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                              double lambda_opacity, void* workspace, float* out, hipStream_t st);
+void launch_splat_reg_backward(long long n, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                               double lambda_opacity, const float* out, const float* upstream, float* d_means3D, float* d_opacity,
+                               hipStream_t st);
+bool depth_l1_shape_ok(int batch, int H, int W);
+size_t depth_l1_workspace_bytes(int batch, int H, int W);   // 0 for a shape out of range or an empty batch
+void launch_depth_l1_forward(int batch, int H, int W, const float* depth, const float* gt, void* workspace, float* out, hipStream_t st);
+void launch_depth_l1_backward(int batch, int H, int W, const float* depth, const float* gt, const float* upstream, bool per_item,
+                              float* grad, hipStream_t st);
+
 // adam.hip: the jobs are checked by the caller (sr_adam_step); jobs with count 0 are skipped
 void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st);
 

@@ -186,3 +186,351 @@ def photometric_loss(image: torch.Tensor, gt_image: torch.Tensor, lambda_dssim: 
         return loss, l1, {"ssim": ssim_items.mean() if shape[0] > 1 else ssim_items.reshape(()),
                           "mask": mask_l1 if opacity is not None else None}
     return loss, l1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The tail of the objective (reference train.py:195-201, :224-229, :244-246) and the objective of a step (:165-250):
+# sr_splat_reg_* and sr_depth_l1_* (csrc/objective.hip).  A streaming pass and a fixed-order reduction forward, one kernel
+# backward; no host synchronisation, no floating-point atomics, bit-identical results from call to call.  No CPU path.
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _empty_in_phase(t: torch.Tensor) -> torch.Tensor:
+    """An uninitialised float32 tensor of t's shape whose address agrees with t's modulo 16 (t: float32, contiguous): the
+    kernels then store a gradient in the same 16-byte vectors they load its input in, whatever t's storage offset."""
+    lead = (t.data_ptr() >> 2) & 3
+    if lead == 0:
+        return torch.empty_like(t)
+    return torch.empty(t.numel() + lead, dtype=torch.float32, device=t.device)[lead:].view(t.shape)
+
+
+def _nan_like_graph(t: torch.Tensor) -> torch.Tensor:
+    """The mean of an empty tensor, as the reference's expressions give it: NaN, still a function of t."""
+    return t.sum() * float("nan")
+
+
+def _run_splat_reg(x, o, weights):
+    """Enqueues sr_splat_reg_forward on the current stream: float32 contiguous tensors (or None) in, out[8] on the device =
+    loss | norm | norm_mean | opacity_reg | mean (3) | 0."""
+    lib = _lib.load()
+    first = x if x is not None else o
+    n, dev = first.shape[0], first.device
+    with torch.cuda.device(dev):
+        work = torch.empty(lib.sr_splat_reg_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        out = torch.empty(8, dtype=torch.float32, device=dev)
+        _lib.check(lib.sr_splat_reg_forward(n, _ptr(x), _ptr(o), *weights, _ptr(work), _ptr(out), _stream(dev)))
+    return out
+
+
+class _SplatReg(torch.autograd.Function):
+    """loss = lambda_norm * norm + lambda_norm_mean * norm_mean + lambda_opacity * opacity_reg, differentiable, and the three
+    terms, detached.  Gradients flow to `means3D` and `opacity`."""
+
+    @staticmethod
+    def forward(ctx, means3D, opacity, weights):
+        x = None if means3D is None else _f32(means3D)
+        o = None if opacity is None else _f32(opacity)
+        out = _run_splat_reg(x, o, weights)
+        n = (x if x is not None else o).shape[0]
+        ctx.save_for_backward(x, o, out)
+        ctx.set_materialize_grads(False)
+        ctx.weights, ctx.n = weights, n
+        ctx.x_meta = None if means3D is None else (means3D.shape, means3D.dtype)
+        ctx.o_meta = None if opacity is None else (opacity.shape, opacity.dtype)
+        dt = (means3D if x is not None else opacity).dtype
+        outs = [out[0].to(dt), out[1].to(dt), out[2].to(dt), out[3].to(dt)]
+        ctx.mark_non_differentiable(*outs[1:])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_loss, g_norm, g_norm_mean, g_opacity):
+        if g_loss is None:
+            return None, None, None
+        lib = _lib.load()
+        x, o, out = ctx.saved_tensors
+        lam_n, lam_nm, lam_o = ctx.weights
+        want_x = x is not None and ctx.needs_input_grad[0]
+        want_o = o is not None and ctx.needs_input_grad[1]
+        if not want_x and not want_o:
+            return None, None, None
+        g = _f32(g_loss)
+        dev = out.device
+        with torch.cuda.device(dev):
+            d_x = _empty_in_phase(x) if want_x else None
+            d_o = _empty_in_phase(o) if want_o else None
+            _lib.check(lib.sr_splat_reg_backward(ctx.n, _ptr(x), _ptr(o), lam_n, lam_nm, lam_o, _ptr(out), _ptr(g), _ptr(d_x), _ptr(d_o),
+                                                 _stream(dev)))
+        if want_x:
+            shape, dt = ctx.x_meta
+            d_x = d_x.reshape(shape).to(dt)
+        if want_o:
+            shape, dt = ctx.o_meta
+            d_o = d_o.reshape(shape).to(dt)
+        return d_x, d_o, None
+
+
+def _check_splats(name, means3D, opacity):
+    for what, t in (("means3D", means3D), ("opacity", opacity)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} takes tensors")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} has no CPU path: {what} must be on a HIP ('cuda') device")
+        if not t.is_floating_point():
+            raise RuntimeError(f"{name}: {what} must be a floating-point tensor")
+    if means3D is not None and (means3D.dim() != 2 or means3D.shape[1] != 3):
+        raise RuntimeError(f"{name}: means3D must be [N,3], got {tuple(means3D.shape)}")
+    if opacity is not None and not (opacity.dim() == 1 or (opacity.dim() == 2 and opacity.shape[1] == 1)):
+        raise RuntimeError(f"{name}: opacity must be [N] or [N,1], got {tuple(opacity.shape)}")
+    if means3D is not None and opacity is not None:
+        if opacity.shape[0] != means3D.shape[0]:
+            raise RuntimeError(f"{name}: {means3D.shape[0]} rows of means3D and {opacity.shape[0]} opacities")
+        if opacity.device != means3D.device:
+            raise RuntimeError(f"{name}: means3D and opacity must be on the same device")
+
+
+def splat_regularizers(means3D: Optional[torch.Tensor], opacity: Optional[torch.Tensor] = None, lambda_norm: float = 0.0,
+                       lambda_norm_mean: float = 0.0, lambda_opacity: float = 0.0):
+    """The splat terms of the reference's objective in one fused forward and one backward launch:
+
+        loss = lambda_norm * means3D.norm(dim=1).mean()                                               # train.py:195-197
+             + lambda_norm_mean * (means3D - means3D.detach().mean(0, keepdim=True)).norm(dim=1).mean()   # train.py:198-201
+             + lambda_opacity * ((opacity - 1.0) ** 2).mean()                                          # train.py:244-246
+
+    Returns ``(loss, terms)``: ``terms`` holds the detached device scalars ``norm``, ``norm_mean`` and ``opacity`` of the terms
+    that were asked for.  A term with weight 0 is skipped, not computed.  Gradients flow to ``means3D`` and ``opacity``."""
+    weights = (float(lambda_norm), float(lambda_norm_mean), float(lambda_opacity))
+    need_x, need_o = weights[0] != 0.0 or weights[1] != 0.0, weights[2] != 0.0
+    if need_x and means3D is None:
+        raise RuntimeError("splat_regularizers: lambda_norm / lambda_norm_mean without means3D")
+    if need_o and opacity is None:
+        raise RuntimeError("splat_regularizers: lambda_opacity without opacity")
+    if not need_x and not need_o:
+        raise RuntimeError("splat_regularizers: every weight is 0, there is nothing to compute")
+    _check_splats("splat_regularizers", means3D if need_x else None, opacity if need_o else None)
+    first = means3D if need_x else opacity
+    names = [k for k, on in (("norm", weights[0] != 0.0), ("norm_mean", weights[1] != 0.0), ("opacity", weights[2] != 0.0)) if on]
+    if first.shape[0] == 0:      # the mean of nothing
+        loss = _nan_like_graph(first)
+        return loss, {k: loss.detach() for k in names}
+    x, o = (means3D if need_x else None), (opacity if need_o else None)
+    if torch.is_grad_enabled() and ((x is not None and x.requires_grad) or (o is not None and o.requires_grad)):
+        loss, norm, norm_mean, opacity_reg = _SplatReg.apply(x, o, weights)
+    else:       # nothing to differentiate: nothing is kept
+        out = _run_splat_reg(None if x is None else _f32(x), None if o is None else _f32(o), weights).to(first.dtype)
+        loss, norm, norm_mean, opacity_reg = out[0], out[1], out[2], out[3]
+    values = {"norm": norm, "norm_mean": norm_mean, "opacity": opacity_reg}
+    return loss, {k: values[k] for k in names}
+
+
+def position_norm(means3D: torch.Tensor) -> torch.Tensor:
+    """``means3D.norm(dim=1).mean()`` (reference train.py:196), differentiable."""
+    return splat_regularizers(means3D, lambda_norm=1.0)[0]
+
+
+def centered_position_norm(means3D: torch.Tensor) -> torch.Tensor:
+    """``(means3D - means3D.detach().mean(dim=0, keepdim=True)).norm(dim=1).mean()`` (reference train.py:199-200)."""
+    return splat_regularizers(means3D, lambda_norm_mean=1.0)[0]
+
+
+def opacity_regularizer(opacity: torch.Tensor) -> torch.Tensor:
+    """``((opacity - 1.0) ** 2).mean()`` (reference train.py:245) for the [N,1] (or [N]) opacities."""
+    return splat_regularizers(None, opacity, lambda_opacity=1.0)[0]
+
+
+def _run_depth_l1(d, g, shape):
+    """Enqueues sr_depth_l1_forward on the current stream: float32 contiguous tensors in, out[1 + batch] on the device = the
+    mean over everything | the mean per item."""
+    lib = _lib.load()
+    batch, h, w = shape
+    dev = d.device
+    with torch.cuda.device(dev):
+        work = torch.empty(lib.sr_depth_l1_workspace_bytes(batch, h, w), dtype=torch.uint8, device=dev)
+        out = torch.empty(1 + batch, dtype=torch.float32, device=dev)
+        _lib.check(lib.sr_depth_l1_forward(batch, h, w, _ptr(d), _ptr(g), _ptr(work), _ptr(out), _stream(dev)))
+    return out
+
+
+class _DepthL1(torch.autograd.Function):
+    """(mean over everything, mean per item): `per_item` selects the differentiable one.  Gradients flow to `depth`."""
+
+    @staticmethod
+    def forward(ctx, depth, gt, shape, per_item):
+        d, g = _f32(depth), _f32(gt)       # each converted to float32 on its own: a half-precision render does not round the target
+        out = _run_depth_l1(d, g, shape)
+        ctx.save_for_backward(d, g)
+        ctx.set_materialize_grads(False)
+        ctx.shape, ctx.per_item, ctx.meta = shape, per_item, (depth.shape, depth.dtype)
+        outs = (out[0].to(depth.dtype), out[1:].to(depth.dtype))
+        ctx.mark_non_differentiable(outs[0 if per_item else 1])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_all, g_items):
+        up = g_items if ctx.per_item else g_all
+        if up is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        lib = _lib.load()
+        d, g = ctx.saved_tensors
+        batch, h, w = ctx.shape
+        up = _f32(up)
+        dev = d.device
+        with torch.cuda.device(dev):
+            grad = _empty_in_phase(d)
+            _lib.check(lib.sr_depth_l1_backward(batch, h, w, _ptr(d), _ptr(g), _ptr(up), int(ctx.per_item), _ptr(grad), _stream(dev)))
+        shape, dt = ctx.meta
+        return grad.reshape(shape).to(dt), None, None, None
+
+
+def depth_l1_loss(depth: torch.Tensor, gt_depth: torch.Tensor, size_average: bool = True) -> torch.Tensor:
+    """Lines 224-229 of the reference's train.py:
+
+        _dmask = gt_depth > 0
+        F.l1_loss(depth * _dmask, gt_depth * _dmask)          # the mean over ALL elements, the masked ones included
+
+    for depth maps [H,W], [1,H,W] or [B,H,W] (``gt_depth`` in any of these shapes with as many elements).  A 0-dim tensor, or
+    the [B] per-item means with ``size_average=False``.  Differentiable in ``depth``; inputs are assumed finite."""
+    if not isinstance(depth, torch.Tensor) or not isinstance(gt_depth, torch.Tensor):
+        raise TypeError("depth_l1_loss takes tensors")
+    if not depth.is_cuda or not gt_depth.is_cuda:
+        raise RuntimeError("depth_l1_loss has no CPU path: tensors must be on a HIP ('cuda') device")
+    if gt_depth.device != depth.device:
+        raise RuntimeError("depth_l1_loss: the two depth maps must be on the same device")
+    if depth.dim() not in (2, 3) or not depth.is_floating_point():
+        raise RuntimeError(f"depth_l1_loss: expected a floating-point [H,W], [1,H,W] or [B,H,W] depth map, got {tuple(depth.shape)}")
+    if gt_depth.numel() != depth.numel() or gt_depth.shape[-2:] != depth.shape[-2:]:
+        raise RuntimeError(f"depth_l1_loss: the two depth maps must have the same size, got {tuple(depth.shape)} and {tuple(gt_depth.shape)}")
+    if gt_depth.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("depth_l1_loss: the target requires grad, and no gradient is computed for it (detach it)")
+    shape = (depth.shape[0] if depth.dim() == 3 else 1, depth.shape[-2], depth.shape[-1])
+    if depth.numel() == 0:       # the mean of nothing
+        nan = _nan_like_graph(depth)
+        return nan if size_average else nan.expand(shape[0])
+    if torch.is_grad_enabled() and depth.requires_grad:
+        everything, items = _DepthL1.apply(depth, gt_depth, shape, not size_average)
+        return everything if size_average else items
+    out = _run_depth_l1(_f32(depth), _f32(gt_depth), shape).to(depth.dtype)      # nothing to differentiate: nothing is kept
+    return out[0] if size_average else out[1:]
+
+
+def _as_views(name, arg, n_views=None):
+    """A per-view argument as (list of per-view tensors, the stacked tensor or None): a list / tuple of V tensors, or a tensor
+    whose first dimension is V."""
+    if arg is None:
+        return None, None
+    if isinstance(arg, torch.Tensor):
+        if arg.dim() < 3:
+            raise RuntimeError(f"training_objective: {name} must be a list of per-view tensors or stacked along a first view dimension, got {tuple(arg.shape)}")
+        views, stacked = list(arg.unbind(0)), arg
+    else:
+        views, stacked = list(arg), None
+        if not all(isinstance(v, torch.Tensor) for v in views):
+            raise TypeError(f"training_objective: {name} takes tensors")
+    if n_views is not None and len(views) != n_views:
+        raise RuntimeError(f"training_objective: {len(views)} {name} for {n_views} views")
+    return views, stacked
+
+
+def _batch(views, stacked, index, tail_dims):
+    """The views `index` as one batch [len(index), *tail]: the stacked tensor itself when it is all of them."""
+    if stacked is not None and len(index) == len(views):
+        return stacked.reshape((len(index),) + tuple(tail_dims))
+    return torch.stack([views[i].reshape(tuple(tail_dims)) for i in index])
+
+
+def training_objective(images, gt_images, *, opacities=None, gt_masks=None, depths=None, gt_depths=None, means3D=None,
+                       gaussian_opacity=None, gradient_error=None, extra=None, lambda_dssim: float, lambda_mask: float = 0.0,
+                       lambda_norm: float = 0.0, lambda_norm_mean: float = 0.0, lambda_opacity: float = 0.0,
+                       lambda_depthl1: float = 0.0, lambda_gradient: float = 0.0):
+    """The objective of the reference's train.py:165-250 for the V views of a step, rendered from one ``gaussian_dict``:
+
+        per view   (1 - lambda_dssim) * Ll1 + lambda_dssim * (1 - ssim)  + lambda_mask * mask  + lambda_depthl1 * depthl1
+        once       lambda_norm * norm + lambda_norm_mean * norm_mean + lambda_opacity * opacity
+                   + lambda_gradient * gradient_error + extra
+
+    the view terms summed and divided by V.  The reference adds the two norm terms to every view's loss before it divides the
+    sum by V, which is the same value; they are evaluated once here.  As in the reference, a term is on when its weight is
+    > 0 (and, for ``gradient_error``, when it is given).  ``extra`` is the caller's ``lambda_corr * moran_loss(...)``.
+
+    ``images`` / ``gt_images``: a list of V [3,H,W] tensors or one stacked [V,3,H,W]; ``opacities`` / ``gt_masks`` /
+    ``depths`` / ``gt_depths`` likewise, one value per pixel.  Views of equal shape go through ONE batched ``photometric_loss``
+    and one batched depth L1; views of differing shapes are grouped by shape and the groups' means combined with the weights
+    (views in the group) / V.  Returns ``(loss, log)``; ``log`` carries ``Ll1`` and the reference's ``loss_dict`` entries these
+    terms feed -- ``mask``, ``depthl1``, ``opacity``, ``loss_gradient`` -- as detached device tensors (0 for a term that is off).
+    Nothing is read back to the host."""
+    views, stacked = _as_views("images", images)
+    n_views = len(views)
+    if n_views == 0:
+        raise RuntimeError("training_objective: at least one view is required")
+    gts, gts_stacked = _as_views("gt_images", gt_images, n_views)
+    use_mask, use_depth = lambda_mask > 0.0, lambda_depthl1 > 0.0
+    if use_mask and (opacities is None or gt_masks is None):
+        raise RuntimeError("training_objective: lambda_mask needs opacities and gt_masks")
+    if use_depth and (depths is None or gt_depths is None):
+        raise RuntimeError("training_objective: lambda_depthl1 needs depths and gt_depths")
+    alphas, alphas_stacked = _as_views("opacities", opacities, n_views) if use_mask else (None, None)
+    masks, masks_stacked = _as_views("gt_masks", gt_masks, n_views) if use_mask else (None, None)
+    rendered, rendered_stacked = _as_views("depths", depths, n_views) if use_depth else (None, None)
+    targets, targets_stacked = _as_views("gt_depths", gt_depths, n_views) if use_depth else (None, None)
+
+    groups = {}                                    # shape -> view indices, in order of first appearance
+    for i, v in enumerate(views):
+        if v.dim() != 3:
+            raise RuntimeError(f"training_objective: a view is [C,H,W], got {tuple(v.shape)}")
+        groups.setdefault(tuple(v.shape), []).append(i)
+
+    def combine(total, term, count):
+        term = term if count == n_views else term * (count / n_views)
+        return term if total is None else total + term
+
+    loss = l1 = mask_term = depth_term = None
+    for shape, index in groups.items():
+        c, h, w = shape
+        image = _batch(views, stacked, index, shape)
+        gt = _batch(gts, gts_stacked, index, shape)
+        alpha = _batch(alphas, alphas_stacked, index, (h, w)) if use_mask else None
+        mask = _batch(masks, masks_stacked, index, (h, w)) if use_mask else None
+        group_loss, group_l1, terms = photometric_loss(image, gt, lambda_dssim, alpha, mask, lambda_mask if use_mask else 0.0,
+                                                       return_terms=True)
+        loss, l1 = combine(loss, group_loss, len(index)), combine(l1, group_l1, len(index))
+        if use_mask:
+            mask_term = combine(mask_term, terms["mask"], len(index))
+        if use_depth:
+            value = depth_l1_loss(_batch(rendered, rendered_stacked, index, (h, w)), _batch(targets, targets_stacked, index, (h, w)))
+            depth_term = combine(depth_term, value, len(index))
+    if use_depth:
+        loss = loss + lambda_depthl1 * depth_term
+
+    lam_n, lam_nm, lam_o = (max(float(v), 0.0) for v in (lambda_norm, lambda_norm_mean, lambda_opacity))
+    if (lam_n or lam_nm) and means3D is None:
+        raise RuntimeError("training_objective: lambda_norm / lambda_norm_mean need means3D")
+    if lam_o and gaussian_opacity is None:
+        raise RuntimeError("training_objective: lambda_opacity needs gaussian_opacity")
+    opacity_term = None
+    if lam_n or lam_nm or lam_o:
+        reg, terms = splat_regularizers(means3D if (lam_n or lam_nm) else None, gaussian_opacity if lam_o else None, lam_n, lam_nm, lam_o)
+        loss = loss + reg.to(loss.dtype)
+        opacity_term = terms.get("opacity")
+    gradient_term = None
+    if lambda_gradient > 0.0 and gradient_error is not None:
+        gradient_term = gradient_error
+        loss = loss + lambda_gradient * gradient_term
+    if extra is not None:
+        loss = loss + extra
+
+    zero = None
+
+    def logged(t):
+        nonlocal zero
+        if t is not None:
+            return t.detach()
+        if zero is None:
+            zero = torch.zeros((), dtype=loss.dtype, device=loss.device)
+        return zero
+
+    log = {"Ll1": l1.detach(), "mask": logged(mask_term), "depthl1": logged(depth_term), "opacity": logged(opacity_term),
+           "loss_gradient": logged(gradient_term)}
+    return loss, log
