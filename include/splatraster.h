@@ -45,6 +45,9 @@
  *   sr_adam_step
  *        <- reference train.py:314-322 (`gaussians.optimizer.step()`), the `torch.optim.Adam` of scene/gaussian_model.py:130-139:
  *           every tensor of the step in one launch.
+ *   sr_groupnorm_stats, sr_conv3x3_forward / _backward_data / _weight_grad, sr_groupnorm_silu_backward
+ *        <- reference scene/time_decoders.py (`TimeVAEDecoder`) behind scene/tripFields.py:176-204 (`Tensorial2D`): the plane
+ *           generator's GroupNorm -> SiLU -> [nearest x2] -> conv 3x3 -> [+ residual] layers, all planes per launch.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -610,6 +613,83 @@ int sr_triplane_forward(int n_points, int channels, int height, int width, const
                         const float* points, float* out, void* hip_stream);
 int sr_triplane_backward(int n_points, int channels, int height, int width, const float* planes_texel_major, const float* points,
                          const float* dL_dout, float* dL_dplanes, float* dL_dpoints, void* workspace, void* hip_stream);
+
+/* Plane generator -- the other half of the reference's VarTriPlaneEncoder: the CNN decoder that turns a fixed noise map into a
+ * plane on every step (`Tensorial2D` around `TimeVAEDecoder`, scene/tripFields.py:176-204, scene/time_decoders.py).  Its
+ * convolution stack is GroupNorm -> SiLU -> [nearest x2] -> 3x3 convolution -> [+ residual]; every layer of it is one
+ * sr_conv3x3_forward, and every plane of the encoder goes through the SAME launch: the entry points take a job table with one
+ * row per plane (shapes are shared, pointers are per plane).  All tensors are fp32 NCHW without the batch dimension, contiguous.
+ * Matrix products run on v_mfma_f32_16x16x4_f32; there are no floating-point atomics, every sum across workgroups goes
+ * through partials in the caller's workspace that are added in a fixed order (bit-identical from call to call); nothing waits
+ * on the host.  sr_profile_collect counts the launches of the forward entries under stage 0 and of the backward entries
+ * under stage 6 (one record per kernel launch).
+ *
+ * Channel counts of a convolution: multiples of 8 in 8..64.  GroupNorm: any `groups` dividing the channel count, channels
+ * 1..64.  height * width of the convolution's OUTPUT below 2^24.  Anything else returns nonzero before any launch.
+ *
+ * One row serves all five entry points; each reads the fields named in its description and ignores the others. */
+#define SR_PLANE_MAX_JOBS 8
+#define SR_CONV_PROLOGUE 1 /* the convolution's input is SiLU(gamma (x - mean) rstd + beta), recomputed from x and `stats`        */
+#define SR_CONV_UPSAMPLE 2 /* ... then upsampled nearest x2: the convolution runs at [2 h_in, 2 w_in]                             */
+#define SR_CONV_RESIDUAL 4 /* `residual` [cout, h_out, w_out] is added to the result                                               */
+#define SR_CONV_SILU_OUT 8 /* out = SiLU(z), z = convolution + bias + residual; the forward also writes z to `pre`                 */
+typedef struct SrPlaneJob {
+    const float* x;        /* layer input [cin, h_in, w_in] (for sr_groupnorm_*: [channels, h, w])                               */
+    const float* weight;   /* [cout, cin, 3, 3]                                                                                   */
+    const float* bias;     /* [cout] or NULL                                                                                      */
+    const float* gamma;    /* [cin] GroupNorm weight (SR_CONV_PROLOGUE, sr_groupnorm_silu_backward)                               */
+    const float* beta;     /* [cin] GroupNorm bias                                                                                */
+    float* stats;          /* [groups, 4]: mean, 1 / sqrt(var + eps), mean_lo (the double mean = mean + mean_lo), 0;
+                              written by sr_groupnorm_stats, read by the others                                                   */
+    const float* residual; /* [cout, h_out, w_out] (SR_CONV_RESIDUAL)                                                              */
+    float* out;            /* [cout, h_out, w_out]                                                                                */
+    float* pre;            /* [cout, h_out, w_out] (SR_CONV_SILU_OUT): written by the forward, read by the two backward entries   */
+    const float* dy;       /* [cout, h_out, w_out] gradient at `out`                                                              */
+    float* dx;             /* sr_conv3x3_backward_data: [cin, h_in, w_in], gradient at the ACTIVATED (not yet upsampled) input;
+                              sr_groupnorm_silu_backward reads it as the gradient at the activated tensor                         */
+    float* dweight;        /* [cout, cin, 3, 3]                                                                                   */
+    float* dbias;          /* [cout] or NULL                                                                                      */
+    float* dgamma;         /* [channels]                                                                                          */
+    float* dbeta;          /* [channels]                                                                                          */
+    float* d_residual;     /* sr_conv3x3_weight_grad with SR_CONV_SILU_OUT: [cout, h_out, w_out] gradient at z (which is the
+                              residual's gradient), or NULL                                                                       */
+    const float* add;      /* sr_groupnorm_silu_backward: [channels, h, w] added to the result (a residual branch), or NULL       */
+    float* dx_out;         /* sr_groupnorm_silu_backward: [channels, h, w] gradient at x                                          */
+} SrPlaneJob;
+
+/* stats[g] = (mean, 1 / sqrt(biased variance + eps), mean_lo, 0) over channels / groups * h * w values of x, summed in double.
+ * Two launches: per-chunk (mean, M2) partials, then their fixed-order combination.  The workspace is 8-byte aligned.
+ * Fields: x, stats. */
+size_t sr_groupnorm_stats_workspace(int n_planes, int channels, int groups, int height, int width);   /* 0: unsupported */
+int sr_groupnorm_stats(int n_planes, const SrPlaneJob* jobs, int channels, int groups, int height, int width, float eps,
+                       void* workspace, void* hip_stream);
+
+/* One fused layer, one launch.  `flags`: SR_CONV_* bits.  The zero padding applies to the activated, upsampled tensor (a border
+ * tap contributes 0).  Fields: x, weight, bias, residual, out; gamma, beta, stats with SR_CONV_PROLOGUE; pre with
+ * SR_CONV_SILU_OUT. */
+int sr_conv3x3_forward(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags,
+                       void* hip_stream);
+
+/* dx = gradient at the activated input of the convolution (before the upsample: the 2x2 blocks are summed in a fixed order).
+ * With SR_CONV_SILU_OUT dy is first taken through SiLU'(pre).  One launch.  Fields: dy, weight, dx; pre. */
+int sr_conv3x3_backward_data(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int flags, void* hip_stream);
+
+/* dx_out = gradient at x of a = SiLU(gamma (x - mean) rstd + beta) given dx = gradient at a, (+ add); dgamma, dbeta.  Two
+ * launches: per-channel partial sums, then their fixed-order combination and the element-wise pass.
+ * A group of at most 1024 values is taken through double arithmetic from x on (mean and variance included, hence `eps`): with
+ * few values per group the result is a difference of relative size eps rstd^2 that float statistics do not resolve.
+ * The workspace is 8-byte aligned.
+ * Fields: dx, x, gamma, beta, stats, add, dx_out, dgamma, dbeta. */
+size_t sr_groupnorm_silu_backward_workspace(int n_planes, int channels, int height, int width);
+int sr_groupnorm_silu_backward(int n_planes, const SrPlaneJob* jobs, int channels, int groups, int height, int width, float eps,
+                               void* workspace, void* hip_stream);
+
+/* dweight, dbias of the layer sr_conv3x3_forward ran with the same shapes and flags; the activated input is recomputed.  Two
+ * launches: partials per tile of pixels, then their fixed-order sum.
+ * Fields: dy, x, dweight, dbias; gamma, beta, stats with SR_CONV_PROLOGUE; pre, d_residual with SR_CONV_SILU_OUT. */
+size_t sr_conv3x3_weight_grad_workspace(int n_planes, int cin, int cout, int h_in, int w_in, int flags);
+int sr_conv3x3_weight_grad(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags,
+                           void* workspace, void* hip_stream);
 
 /* Diagnostics for the parity tests: byte offsets of four arrays inside the opaque buffers of a view with these sizes
  * (`instances` = the capacity the binning buffer was carved for):

@@ -64,7 +64,15 @@ class SrAdamJob(C.Structure):
                 ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
 
 
+class SrPlaneJob(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in (
+        "x", "weight", "bias", "gamma", "beta", "stats", "residual", "out", "pre", "dy", "dx", "dweight", "dbias", "dgamma", "dbeta",
+        "d_residual", "add", "dx_out")]
+
+
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
+PLANE_MAX_JOBS = 8                                           # include/splatraster.h: SR_PLANE_MAX_JOBS
+CONV_PROLOGUE, CONV_UPSAMPLE, CONV_RESIDUAL, CONV_SILU_OUT = 1, 2, 4, 8   # include/splatraster.h: SR_CONV_*
 MLP_MAX_GRAD_JOBS, MLP_MAX_GRAD_TASKS = 16, 128
 MLP_MAX_PACK_JOBS = 32
 MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatraster.h: SR_MORAN_MAX_TENSORS, SR_KNN_MAX_K
@@ -160,6 +168,16 @@ SYMBOLS = {
     "sr_triplane_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_triplane_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "sr_groupnorm_stats_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sr_groupnorm_stats": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "sr_conv3x3_forward": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sr_conv3x3_backward_data": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sr_groupnorm_silu_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sr_groupnorm_silu_backward": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                             C.c_void_p]),
+    "sr_conv3x3_weight_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sr_conv3x3_weight_grad": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
     "sr_debug_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_size_t)]),
     "sr_debug_backward_stats": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "sr_profile_enable": (C.c_int, [C.c_int]),

@@ -136,6 +136,22 @@ void launch_depth_l1_backward(int batch, int H, int W, const float* depth, const
 // adam.hip: the jobs are checked by the caller (sr_adam_step); jobs with count 0 are skipped
 void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st);
 
+// planegen.hip: shapes are checked by the caller (plane_*_ok); every function is exactly one kernel launch
+bool plane_channels_ok(int c);
+bool plane_conv_shape_ok(int cin, int cout, int hin, int win, int flags);
+bool plane_gn_shape_ok(int channels, int groups, int h, int w);
+size_t gn_stats_workspace(int n_planes, int channels, int groups, int h, int w);
+void launch_gn_stats_partial(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, void* ws, hipStream_t st);
+void launch_gn_stats_final(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, const void* ws, hipStream_t st);
+void launch_conv3x3_forward(int n, const SrPlaneJob* jobs, int cin, int cout, int hin, int win, int groups, int flags, hipStream_t st);
+void launch_conv3x3_backward_data(int n, const SrPlaneJob* jobs, int cin, int cout, int hin, int win, int flags, hipStream_t st);
+size_t conv3x3_weight_grad_workspace(int n_planes, int cin, int cout, int hin, int win, int flags);
+void launch_conv3x3_wgrad_partial(int n, const SrPlaneJob* jobs, int cin, int cout, int hin, int win, int groups, int flags, void* ws, hipStream_t st);
+void launch_conv3x3_wgrad_reduce(int n, const SrPlaneJob* jobs, int cin, int cout, int hin, int win, int flags, const void* ws, hipStream_t st);
+size_t gn_silu_backward_workspace(int n_planes, int channels, int h, int w);
+void launch_gn_silu_backward_partial(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, void* ws, hipStream_t st);
+void launch_gn_silu_backward_apply(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, const void* ws, hipStream_t st);
+
 // sh.hip
 void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
                        unsigned char* clamped, hipStream_t st);

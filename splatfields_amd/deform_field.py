@@ -3,19 +3,21 @@ kernels (splatfields_amd/general_mlp.py).
 
 Same constructor keywords, same `forward(xyz_in, t)` -> dict(scales, opacity, rotations, rgb | rgb_fnc, flow, means3D), same
 parameter names (`mlp_deform.net.<i>...`, `mlp_refine_feat.<i>...`, `mlp_flow_head.branch_w...`), so the MLP / flow-head part of a
-`deform.pth` checkpoint (reference scene/deform_model.py:36-47) loads with `load_state_dict`.  NOT drop-in for the reference's
-DEFAULT encoder: its checkpoints carry the plane generator's weights (`encoder.subs.*`), which only load when the caller supplies
-that generator (below); `load_state_dict` says so instead of failing on missing / unexpected keys.
+`deform.pth` checkpoint (reference scene/deform_model.py:36-47) loads with `load_state_dict`.  A default-config checkpoint also
+carries the plane generator's weights (`encoder.subs.*`): they load, `strict=True`, when the network is built with the generator
+-- `SplatFields(encoder_args={"generator": "decoder"})` (splatfields_amd/plane_generator.py) -- and `load_state_dict` says so
+instead of failing on missing / unexpected keys when it was not.
 
 The tri-plane feature encoder (reference scene/tripFields.py:383-436) is `splatfields_amd.triplane.TriPlaneSampler`: the
 per-point lookup (three `grid_sample`s + cat) runs on HIP kernels, forward and backward.  With the reference's default
 `encoder_type='VarTriPlaneEncoder'` and no `encoder=` argument the sampler owns its planes [3, out_ch, 16 noise_res,
-16 noise_res] as a learnable parameter (a decoder-free tri-plane).  The reference GENERATES the planes with a diffusers / mmgen
-VAE decoder (`Tensorial2D`, :176-204; those packages exist neither in its checkout nor in this image): pass such a generator
-as `TriPlaneSampler(plane_source=...)`, or any module with the encoder's interface (`encoder(x[None]) -> [1, N, out_dim]`,
+16 noise_res] as a learnable parameter (a decoder-free tri-plane).  The reference GENERATES the planes with three CNN decoders
+(`Tensorial2D`, :176-204): opt in with `encoder_args={"generator": "decoder", in_ch, out_ch, noise_res, fuse_mode}` (the
+generator on HIP kernels, configured from `n_frames` / `layer_strategy` as utils/time_utils.py:316-327 does, and told the frame
+of the step), pass a generator as `TriPlaneSampler(plane_source=...)`, or any module with the encoder's interface (`encoder(x[None]) -> [1, N, out_dim]`,
 attribute `out_dim`, e.g. the reference's own `VarTriPlaneEncoder` instance) as `encoder=`.  An `encoder_type` outside the
 reference's list runs without plane features (`feat_dim = 0`, utils/time_utils.py:333-334).  State-dict keys of the
-decoder-free sampler are `encoder.planes`; a reference checkpoint's `encoder.subs.*` keys need the reference's generator.
+decoder-free sampler are `encoder.planes`; a reference checkpoint's `encoder.subs.*` keys need the generator opt-in.
 
 `FlowHead` (utils/time_utils.py:194-303): 'offset', 'se3' (default) and 'dct'; the SE(3) exponential is written out per point
 (no 4x4 batched matmuls), following the reference's formulas including its `w / theta + 1e-5` convention.
@@ -110,6 +112,16 @@ class SplatFields(nn.Module):
         rank = kwargs.get("composition_rank", 0)
         self.n_frames = n_frames
         self.encoder_type = kwargs.get("encoder_type", "VarTriPlaneEncoder")
+        if encoder is None and self.encoder_type in ["VarTriPlaneEncoder"] and (kwargs.get("encoder_args") or {}).get("generator") == "decoder":
+            # opt-in: the reference's encoder with its plane generator (splatfields_amd/plane_generator.py), configured as the
+            # reference does it (utils/time_utils.py:316-328)
+            from .plane_generator import VarTriPlaneEncoder
+            ea = kwargs["encoder_args"]
+            unknown = sorted(k for k in ea if k not in ("generator", "in_ch", "out_ch", "noise_res", "fuse_mode"))
+            if unknown:
+                raise ValueError("SplatFields: encoder_args %s are not arguments of the plane generator (in_ch, out_ch, noise_res, fuse_mode)" % unknown)
+            encoder = VarTriPlaneEncoder({**{k: v for k, v in ea.items() if k != "generator"},
+                                          "layer_kwargs": {"n_frames": n_frames, "strategy": kwargs.get("layer_strategy", "none")}})
         if encoder is None and self.encoder_type in ["VarTriPlaneEncoder"]:
             from .triplane import TriPlaneSampler
             ea = kwargs.get("encoder_args", {}) or {}
@@ -175,9 +187,17 @@ class SplatFields(nn.Module):
     def _time2frame_id(self, t):
         return torch.round(t * (self.n_frames - 1))
 
+    def _encode(self, x, frame_id):
+        """encoder features [N, feat_dim]; an encoder that generates its planes (plane_generator.VarTriPlaneEncoder) is told the
+        frame: its per-frame convolution weights are the time conditioning of the planes"""
+        if getattr(self.encoder, "takes_frame_id", False):
+            return self.encoder(x[None], frame_id=frame_id).squeeze(0)
+        return self.encoder(x[None]).squeeze(0)
+
     def extract_features(self, x, t):
         t_feat = positional_encoding(t, self.time_multires) if self.n_frames > 0 else None
-        x_feat = self.mlp_refine_feat(self.encoder(x[None]).squeeze(0)) if self.feat_dim > 0 else None
+        frame_id = self._time2frame_id(t.view(-1)[0]).long() if self.n_frames > 0 and torch.is_tensor(t) else None
+        x_feat = self.mlp_refine_feat(self._encode(x, frame_id)) if self.feat_dim > 0 else None
         parts = [f for f in (x_feat, t_feat) if f is not None]
         return torch.cat(parts, dim=-1) if parts else None
 
@@ -193,7 +213,7 @@ class SplatFields(nn.Module):
         fuse_time = self.n_frames > 0 and torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and not t.requires_grad and \
             t.numel() == xyz_in.shape[0] and not self.geo_model_disable_pts
         if fuse_time:
-            feat = self.mlp_refine_feat(self.encoder(xyz_in[None]).squeeze(0)) if self.feat_dim > 0 else None
+            feat = self.mlp_refine_feat(self._encode(xyz_in, frame_id)) if self.feat_dim > 0 else None
             tk = dict(time=t.reshape(-1), time_multires=self.time_multires)
         else:
             feat, tk = self.extract_features(xyz_in, t), {}

@@ -2,13 +2,13 @@
 (scene/tripFields.py:383-436) on HIP kernels (csrc/triplane.hip).
 
 The reference encoder has two halves: a plane GENERATOR per axis pair (`Tensorial2D`, :176-204: a diffusers-style
-`TimeVAEDecoder` that turns a fixed 8 x 20 x 20 noise map into a 16 x 320 x 320 plane) and the LOOKUP every point does
+`TimeVAEDecoder` that turns a fixed 8 x 20 x 20 noise map into a 16 x 160 x 160 plane) and the LOOKUP every point does
 (`forward`, :430-436: `F.grid_sample` of the three planes at the xy / yz / zx projections of the point + `cat`).  The lookup
 is what the hot path of a 4-D training step runs per splat; it is built here, forward and backward, with the interface
-`SplatFields` expects of its encoder (`out_dim`; `encoder(x[None]) -> [1, N, out_dim]`).  The generator stays a
-caller-supplied module (`plane_source`): the reference builds it from diffusers / mmgen blocks that exist neither in its
-checkout nor in this image.  Without one, the planes are a learnable parameter of the sampler itself (a decoder-free
-tri-plane of the same shape), which is what the default `SplatFields()` constructs.
+`SplatFields` expects of its encoder (`out_dim`; `encoder(x[None]) -> [1, N, out_dim]`).  The generator is a module of its
+own (`plane_source`): splatfields_amd/plane_generator.py builds the reference's, `VarTriPlaneEncoder` there is this sampler
+around it.  Without one, the planes are a learnable parameter of the sampler itself (a decoder-free tri-plane), which is what
+the default `SplatFields()` constructs.
 """
 from __future__ import annotations
 
