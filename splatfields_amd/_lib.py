@@ -8,6 +8,8 @@ from pathlib import Path
 
 import os
 
+import torch
+
 # SPLATRASTER_LIB selects an alternative build of the same ABI (A/B experiments); default: the in-tree library.
 LIB_PATH = Path(os.environ.get("SPLATRASTER_LIB") or (Path(__file__).resolve().parent / "libsplatraster.so"))
 
@@ -240,3 +242,23 @@ class use_library:
 def check(status: int) -> None:
     if status != 0:
         raise RuntimeError("libsplatraster: " + load().sr_last_error().decode("utf-8", "replace"))
+
+
+# ---- what every caller of the library hands it: a data pointer, the stream, float32 contiguous memory ----
+
+def ptr(t):
+    """the data pointer of a tensor as a void* argument; None (NULL) for None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """the current stream of `device` as the void* every launch takes last"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def f32c(t):
+    """detached, float32, contiguous: the tensor's own memory when it already is both"""
+    t = t.detach()
+    if t.dtype is not torch.float32 or not t.is_contiguous():
+        t = t.to(torch.float32).contiguous()
+    return t

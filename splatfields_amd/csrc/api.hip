@@ -23,6 +23,10 @@ int check_hip(hipError_t e, const char* what) {
     return fail(std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// any of these pointers (NULL counts as aligned) off a 4-byte boundary
+template <typename... P>
+bool any_unaligned4(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 3u) != 0; }
+
 #define SR_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
 // ---- optional per-stage timing (HIP events on the launch stream) ----
@@ -751,8 +755,7 @@ int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible
             return fail("sr_adam_step: with a row mask every job needs count == rows * row" + at);
         if (j.count == 0) continue;
         if (!j.param || !j.grad || !j.exp_avg || !j.exp_avg_sq) return fail("null pointer in sr_adam_step" + at);
-        if ((reinterpret_cast<uintptr_t>(j.param) | reinterpret_cast<uintptr_t>(j.grad) | reinterpret_cast<uintptr_t>(j.exp_avg) |
-             reinterpret_cast<uintptr_t>(j.exp_avg_sq)) & 3u) return fail("sr_adam_step: tensors must be 4-byte aligned" + at);
+        if (any_unaligned4(j.param, j.grad, j.exp_avg, j.exp_avg_sq)) return fail("sr_adam_step: tensors must be 4-byte aligned" + at);
         work = true;
     }
     if (!work) return 0;
@@ -771,7 +774,7 @@ int sr_splat_reg_forward(int n_splats, const float* means3D, const float* opacit
     if (!workspace || !out) return fail("null pointer in sr_splat_reg_forward");
     if ((lambda_norm != 0.0 || lambda_norm_mean != 0.0) && !means3D) return fail("null pointer in sr_splat_reg_forward: means3D is read by the norm terms");
     if (lambda_opacity != 0.0 && !opacity) return fail("null pointer in sr_splat_reg_forward: opacity is read by the opacity term");
-    if ((reinterpret_cast<uintptr_t>(means3D) | reinterpret_cast<uintptr_t>(opacity)) & 3u) return fail("sr_splat_reg_forward: tensors must be 4-byte aligned");
+    if (any_unaligned4(means3D, opacity)) return fail("sr_splat_reg_forward: tensors must be 4-byte aligned");
     sr::launch_splat_reg_forward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, workspace, out,
                                  static_cast<hipStream_t>(hip_stream));
     return check_hip(hipGetLastError(), "splat_reg_forward");
@@ -788,8 +791,7 @@ int sr_splat_reg_backward(int n_splats, const float* means3D, const float* opaci
     if (dL_dmeans3D && !means3D) return fail("null pointer in sr_splat_reg_backward: dL_dmeans3D without means3D");
     if (dL_dopacity && !opacity) return fail("null pointer in sr_splat_reg_backward: dL_dopacity without opacity");
     if (dL_dmeans3D && lambda_norm_mean != 0.0 && !out) return fail("null pointer in sr_splat_reg_backward: the centred norm needs the mean in `out` of the forward");
-    if ((reinterpret_cast<uintptr_t>(means3D) | reinterpret_cast<uintptr_t>(opacity) | reinterpret_cast<uintptr_t>(dL_dmeans3D) |
-         reinterpret_cast<uintptr_t>(dL_dopacity)) & 3u) return fail("sr_splat_reg_backward: tensors must be 4-byte aligned");
+    if (any_unaligned4(means3D, opacity, dL_dmeans3D, dL_dopacity)) return fail("sr_splat_reg_backward: tensors must be 4-byte aligned");
     sr::launch_splat_reg_backward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, out, upstream, dL_dmeans3D,
                                   dL_dopacity, static_cast<hipStream_t>(hip_stream));
     return check_hip(hipGetLastError(), "splat_reg_backward");
@@ -803,7 +805,7 @@ int sr_depth_l1_forward(int batch, int height, int width, const float* depth, co
     if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_forward");
     if (batch == 0) return 0;
     if (!depth || !gt_depth || !workspace || !out) return fail("null pointer in sr_depth_l1_forward");
-    if ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(gt_depth)) & 3u) return fail("sr_depth_l1_forward: tensors must be 4-byte aligned");
+    if (any_unaligned4(depth, gt_depth)) return fail("sr_depth_l1_forward: tensors must be 4-byte aligned");
     sr::launch_depth_l1_forward(batch, height, width, depth, gt_depth, workspace, out, static_cast<hipStream_t>(hip_stream));
     return check_hip(hipGetLastError(), "depth_l1_forward");
 }
@@ -814,8 +816,7 @@ int sr_depth_l1_backward(int batch, int height, int width, const float* depth, c
     if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_backward");
     if (batch == 0) return 0;
     if (!depth || !gt_depth || !upstream || !dL_ddepth) return fail("null pointer in sr_depth_l1_backward");
-    if ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(gt_depth) | reinterpret_cast<uintptr_t>(dL_ddepth)) & 3u)
-        return fail("sr_depth_l1_backward: tensors must be 4-byte aligned");
+    if (any_unaligned4(depth, gt_depth, dL_ddepth)) return fail("sr_depth_l1_backward: tensors must be 4-byte aligned");
     sr::launch_depth_l1_backward(batch, height, width, depth, gt_depth, upstream, upstream_per_item != 0, dL_ddepth,
                                  static_cast<hipStream_t>(hip_stream));
     return check_hip(hipGetLastError(), "depth_l1_backward");

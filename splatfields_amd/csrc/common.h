@@ -117,6 +117,7 @@ struct Image {
 };
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // NULL counts as aligned
 
 struct Carver {
     char* base; size_t off;

@@ -22,17 +22,13 @@
 //
 // No floating-point atomics anywhere: values and gradients are bit-identical from call to call.
 #include "kernels.h"
+#include "reduce.h"
+#include "window11.h"
 
 namespace sr {
 
 namespace {
 
-constexpr int kLossTile = 32;                        // output tile edge
-constexpr int kLossHalo = 5;                         // window_size / 2
-constexpr int kLossRaw = kLossTile + 2 * kLossHalo;  // 42: tile + halo
-constexpr int kLossRawStride = 44;                   // LDS row stride of the haloed tile: 16-byte rows for the ds_read_b128 of the row pass
-constexpr int kLossQuads = kLossTile / 4;            // a thread filters 4 neighbouring columns
-constexpr int kLossTaps = 2 * kLossHalo + 1;
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 
 // float32(exp(-(i-5)^2 / 4.5)) / float32 sum, as torch evaluates the reference's gaussian(11, 1.5)
@@ -46,68 +42,22 @@ struct LossDims {
     int vec;   // W % 4 == 0 and every base pointer 16-byte aligned: centre loads and stores are float4
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-    return v;
-}
-
-// sum over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ float block_sum(float v, float* s_red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    float r = 0.0f;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) r += s_red[w];
-    }
-    __syncthreads();
-    return r;
-}
-
 // the haloed tile of one plane -> LDS, zero outside the image (the reference's zero padding)
 __device__ __forceinline__ void load_haloed(const float* __restrict__ plane, int H, int W, int x0, int y0, float* __restrict__ s) {
-    for (int i = threadIdx.x; i < kLossRaw * kLossRaw; i += kBlock) {
-        const int r = i / kLossRaw, c = i - r * kLossRaw;
-        const int gy = y0 + r - kLossHalo, gx = x0 + c - kLossHalo;
+    for (int i = threadIdx.x; i < kWinRaw * kWinRaw; i += kBlock) {
+        const int r = i / kWinRaw, c = i - r * kWinRaw;
+        const int gy = y0 + r - kWinHalo, gx = x0 + c - kWinHalo;
         const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        s[r * kLossRawStride + c] = in ? plane[(size_t)gy * W + gx] : 0.0f;
+        s[r * kWinRawStride + c] = in ? plane[(size_t)gy * W + gx] : 0.0f;
     }
 }
 
-// 14 neighbouring values of LDS row `row`, from column 4 * quad (two columns more are read and not used)
-__device__ __forceinline__ void read_span(const float* __restrict__ s, int row, int quad, float (&v)[16]) {
-    const float4* p = reinterpret_cast<const float4*>(s + row * kLossRawStride + 4 * quad);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 q = p[j];
-        v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
-    }
-}
-
-// 4 neighbouring outputs of the 11-tap filter over a span
-__device__ __forceinline__ float4 filter_span(const float (&v)[16]) {
-    const float w[kLossTaps] = SR_LOSS_TAPS;
-    float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int t = 0; t < kLossTaps; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaf(w[t], v[j + t], o[j]);
-    return make_float4(o[0], o[1], o[2], o[3]);
-}
-
-// column pass: 4 neighbouring outputs of row `row` from the row-filtered planes [kLossRaw][kLossTile].  A wavefront reads
-// 8 quads x 8 rows = 1 KiB of consecutive LDS per tap: no bank conflict.
-__device__ __forceinline__ float4 filter_column(const float* __restrict__ s, int row, int quad) {
-    const float w[kLossTaps] = SR_LOSS_TAPS;
-    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-    for (int t = 0; t < kLossTaps; ++t) {
-        const float4 q = *reinterpret_cast<const float4*>(s + (row + t) * kLossTile + 4 * quad);
-        o.x = fmaf(w[t], q.x, o.x); o.y = fmaf(w[t], q.y, o.y); o.z = fmaf(w[t], q.z, o.z); o.w = fmaf(w[t], q.w, o.w);
-    }
-    return o;
+// row pass: the 4 filtered outputs of a span -> their 16-byte slot of a row-filtered plane (`dst` without __restrict__: with it
+// the backward filters its three maps one after another instead of interleaved)
+__device__ __forceinline__ void filter_span_to(const float (&w)[kWinTaps], const float (&v)[16], float* dst) {
+    float o[4];
+    win_filter_span(w, v, o);
+    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
 __device__ __forceinline__ void load4(const float* __restrict__ p, int n_valid, int vec, float (&v)[4]) {
@@ -138,7 +88,7 @@ __device__ __forceinline__ TilePos tile_of_block(const LossDims& d) {
     const unsigned per_plane = (unsigned)d.tiles_x * (unsigned)d.tiles_y;
     const unsigned plane = b / per_plane, t = b - plane * per_plane;
     const unsigned ty = t / (unsigned)d.tiles_x, tx = t - ty * (unsigned)d.tiles_x;
-    return {(int)plane, (int)tx * kLossTile, (int)ty * kLossTile};
+    return {(int)plane, (int)tx * kWinTile, (int)ty * kWinTile};
 }
 
 // partial: [3][blocks] = sum S | sum |x - y| | sum |clamp(a) - m| of each workgroup's tile.  maps (may be NULL):
@@ -146,48 +96,50 @@ __device__ __forceinline__ TilePos tile_of_block(const LossDims& d) {
 __global__ void __launch_bounds__(kBlock) k_loss_forward(const LossDims d, const float* __restrict__ image, const float* __restrict__ gt,
                                                          const float* __restrict__ alpha, const float* __restrict__ gt_mask, int do_ssim,
                                                          float* __restrict__ maps, float* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) float s_raw[2][kLossRaw * kLossRawStride];
-    __shared__ __attribute__((aligned(16))) float s_row[5][kLossRaw * kLossTile];
+    __shared__ __attribute__((aligned(16))) float s_raw[2][kWinRaw * kWinRawStride];
+    __shared__ __attribute__((aligned(16))) float s_row[5][kWinRaw * kWinTile];
     __shared__ float s_red[kBlock / kWave];
     const TilePos tp = tile_of_block(d);
     const int H = d.H, W = d.W;
     const size_t plane_px = (size_t)H * W;
     const float* px = image + (size_t)tp.plane * plane_px;
     const float* py = gt + (size_t)tp.plane * plane_px;
-    const int row = threadIdx.x / kLossQuads, quad = threadIdx.x % kLossQuads;   // this thread's 4 pixels in the column pass
+    const int row = threadIdx.x / kWinQuads, quad = threadIdx.x % kWinQuads;   // this thread's 4 pixels in the column pass
     const int gy = tp.y0 + row, gx = tp.x0 + 4 * quad;
     const int n_valid = gy < H ? min(4, W - gx) : 0;                              // <= 0: none
 
     float sum_s = 0.0f, sum_l1 = 0.0f, sum_mask = 0.0f;
     if (do_ssim) {
+        const float taps[kWinTaps] = SR_LOSS_TAPS;
         load_haloed(px, H, W, tp.x0, tp.y0, s_raw[0]);
         load_haloed(py, H, W, tp.x0, tp.y0, s_raw[1]);
         __syncthreads();
-        for (int item = threadIdx.x; item < kLossRaw * kLossQuads; item += kBlock) {   // rows
-            const int r = item / kLossQuads, q = item % kLossQuads;
+        for (int item = threadIdx.x; item < kWinRaw * kWinQuads; item += kBlock) {   // rows
+            const int r = item / kWinQuads, q = item % kWinQuads;
             float x[16], y[16], p[16];
-            read_span(s_raw[0], r, q, x);
-            read_span(s_raw[1], r, q, y);
-            float4* out = reinterpret_cast<float4*>(&s_row[0][r * kLossTile + 4 * q]);
-            constexpr int kPlaneF4 = kLossRaw * kLossTile / 4;
-            out[0] = filter_span(x);
-            out[kPlaneF4] = filter_span(y);
+            win_read_span(s_raw[0], r, q, x);
+            win_read_span(s_raw[1], r, q, y);
+            float* out = &s_row[0][r * kWinTile + 4 * q];
+            constexpr int kPlane = kWinRaw * kWinTile;
+            filter_span_to(taps, x, out);
+            filter_span_to(taps, y, out + kPlane);
 #pragma unroll
             for (int j = 0; j < 14; ++j) p[j] = x[j] * x[j];
-            out[2 * kPlaneF4] = filter_span(p);
+            filter_span_to(taps, p, out + 2 * kPlane);
 #pragma unroll
             for (int j = 0; j < 14; ++j) p[j] = y[j] * y[j];
-            out[3 * kPlaneF4] = filter_span(p);
+            filter_span_to(taps, p, out + 3 * kPlane);
 #pragma unroll
             for (int j = 0; j < 14; ++j) p[j] = x[j] * y[j];
-            out[4 * kPlaneF4] = filter_span(p);
+            filter_span_to(taps, p, out + 4 * kPlane);
         }
         __syncthreads();
-        const float4 m1 = filter_column(s_row[0], row, quad), m2 = filter_column(s_row[1], row, quad);   // columns
-        const float4 e11 = filter_column(s_row[2], row, quad), e22 = filter_column(s_row[3], row, quad);
-        const float4 e12 = filter_column(s_row[4], row, quad);
-        const float mu1[4] = {m1.x, m1.y, m1.z, m1.w}, mu2[4] = {m2.x, m2.y, m2.z, m2.w};
-        const float xx[4] = {e11.x, e11.y, e11.z, e11.w}, yy[4] = {e22.x, e22.y, e22.z, e22.w}, xy[4] = {e12.x, e12.y, e12.z, e12.w};
+        float mu1[4], mu2[4], xx[4], yy[4], xy[4];   // columns
+        win_filter_column(taps, s_row[0], row, quad, mu1);
+        win_filter_column(taps, s_row[1], row, quad, mu2);
+        win_filter_column(taps, s_row[2], row, quad, xx);
+        win_filter_column(taps, s_row[3], row, quad, yy);
+        win_filter_column(taps, s_row[4], row, quad, xy);
         float p_mu[4], p_a[4], p_c[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -208,8 +160,8 @@ __global__ void __launch_bounds__(kBlock) k_loss_forward(const LossDims d, const
             store4(maps + 2 * all + off, n_valid, d.vec, p_c);
         }
         if (n_valid > 0) {   // |x - y| of the same pixels, from the tile in LDS
-            const float* cx = &s_raw[0][(row + kLossHalo) * kLossRawStride + 4 * quad + kLossHalo];
-            const float* cy = &s_raw[1][(row + kLossHalo) * kLossRawStride + 4 * quad + kLossHalo];
+            const float* cx = &s_raw[0][(row + kWinHalo) * kWinRawStride + 4 * quad + kWinHalo];
+            const float* cy = &s_raw[1][(row + kWinHalo) * kWinRawStride + 4 * quad + kWinHalo];
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (j < n_valid) sum_l1 += fabsf(cx[j] - cy[j]);
         }
@@ -244,15 +196,7 @@ constexpr int kReduceBlock = 1024;
 __device__ __forceinline__ double reduce_range(const float* __restrict__ v, size_t n, double* s) {
     double acc = 0.0;
     for (size_t i = threadIdx.x; i < n; i += kReduceBlock) acc += (double)v[i];
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int d = kReduceBlock / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
+    return block_tree_sum<double, kReduceBlock>(acc, s);
 }
 
 __global__ void __launch_bounds__(kReduceBlock) k_loss_reduce(size_t blocks, int batch, size_t blocks_per_item, double px_per_item,
@@ -286,36 +230,36 @@ __global__ void __launch_bounds__(kBlock) k_loss_backward(const LossDims d, cons
                                                           const float* __restrict__ maps, float c_l1, float c_ssim, float c_mask,
                                                           const float* __restrict__ g, int g_per_item, float* __restrict__ dL_dimage,
                                                           float* __restrict__ dL_dalpha) {
-    __shared__ __attribute__((aligned(16))) float s_raw[3][kLossRaw * kLossRawStride];
-    __shared__ __attribute__((aligned(16))) float s_row[3][kLossRaw * kLossTile];
+    __shared__ __attribute__((aligned(16))) float s_raw[3][kWinRaw * kWinRawStride];
+    __shared__ __attribute__((aligned(16))) float s_row[3][kWinRaw * kWinTile];
     const TilePos tp = tile_of_block(d);
     const int H = d.H, W = d.W;
     const size_t plane_px = (size_t)H * W, all = (size_t)d.planes * plane_px;
     const int item_idx = tp.plane / d.channels;
     const float gv = g[g_per_item ? item_idx : 0];
-    const int row = threadIdx.x / kLossQuads, quad = threadIdx.x % kLossQuads;
+    const int row = threadIdx.x / kWinQuads, quad = threadIdx.x % kWinQuads;
     const int gy = tp.y0 + row, gx = tp.x0 + 4 * quad;
     const int n_valid = gy < H ? min(4, W - gx) : 0;
 
     float conv_mu[4] = {0.0f, 0.0f, 0.0f, 0.0f}, conv_a[4] = {0.0f, 0.0f, 0.0f, 0.0f}, conv_c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (maps) {
+        const float taps[kWinTaps] = SR_LOSS_TAPS;
 #pragma unroll
         for (int m = 0; m < 3; ++m) load_haloed(maps + m * all + (size_t)tp.plane * plane_px, H, W, tp.x0, tp.y0, s_raw[m]);
         __syncthreads();
-        for (int item = threadIdx.x; item < kLossRaw * kLossQuads; item += kBlock) {
-            const int r = item / kLossQuads, q = item % kLossQuads;
+        for (int item = threadIdx.x; item < kWinRaw * kWinQuads; item += kBlock) {
+            const int r = item / kWinQuads, q = item % kWinQuads;
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 float v[16];
-                read_span(s_raw[m], r, q, v);
-                *reinterpret_cast<float4*>(&s_row[m][r * kLossTile + 4 * q]) = filter_span(v);
+                win_read_span(s_raw[m], r, q, v);
+                filter_span_to(taps, v, &s_row[m][r * kWinTile + 4 * q]);
             }
         }
         __syncthreads();
-        const float4 a = filter_column(s_row[0], row, quad), b = filter_column(s_row[1], row, quad), c = filter_column(s_row[2], row, quad);
-        conv_mu[0] = a.x; conv_mu[1] = a.y; conv_mu[2] = a.z; conv_mu[3] = a.w;
-        conv_a[0] = b.x; conv_a[1] = b.y; conv_a[2] = b.z; conv_a[3] = b.w;
-        conv_c[0] = c.x; conv_c[1] = c.y; conv_c[2] = c.z; conv_c[3] = c.w;
+        win_filter_column(taps, s_row[0], row, quad, conv_mu);
+        win_filter_column(taps, s_row[1], row, quad, conv_a);
+        win_filter_column(taps, s_row[2], row, quad, conv_c);
     }
     if (n_valid <= 0) return;
     const size_t px_off = (size_t)gy * W + gx;
@@ -350,19 +294,17 @@ __global__ void __launch_bounds__(kBlock) k_loss_backward(const LossDims d, cons
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // 0 when the tile count does not fit a grid
 size_t loss_blocks(int planes, int H, int W) {
     if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t n = (size_t)planes * (size_t)((H + kLossTile - 1) / kLossTile) * (size_t)((W + kLossTile - 1) / kLossTile);
+    const size_t n = (size_t)planes * (size_t)((H + kWinTile - 1) / kWinTile) * (size_t)((W + kWinTile - 1) / kWinTile);
     return n <= 0x7fffffffull ? n : 0;
 }
 
 LossDims loss_dims(int batch, int channels, int H, int W) {
     LossDims d;
     d.planes = batch * channels; d.channels = channels; d.H = H; d.W = W;
-    d.tiles_x = (W + kLossTile - 1) / kLossTile; d.tiles_y = (H + kLossTile - 1) / kLossTile;
+    d.tiles_x = (W + kWinTile - 1) / kWinTile; d.tiles_y = (H + kWinTile - 1) / kWinTile;
     d.vec = (W % 4) == 0;
     return d;
 }

@@ -24,17 +24,14 @@
 //
 // No floating-point atomics and no host wait: results are bit-identical from call to call.
 #include "kernels.h"
+#include "reduce.h"
+#include "window11.h"
 
 namespace sr {
 
 namespace {
 
-constexpr int kMetTile = 32;                       // output tile edge
-constexpr int kMetTaps = 11;
-constexpr int kMetRaw = kMetTile + kMetTaps - 1;   // 42: the input region of a tile
-constexpr int kMetRawStride = 44;                  // LDS row stride of the region: 16-byte rows for the ds_read_b128 of the row pass
-constexpr int kMetGroups = kMetRawStride / 4;      // a row is staged as 11 groups of 4 columns
-constexpr int kMetQuads = kMetTile / 4;            // a thread filters 4 neighbouring columns
+constexpr int kMetGroups = kWinRawStride / 4;      // a row of the region is staged as 11 groups of 4 columns
 constexpr float kMetC1 = (float)(0.01 * 0.01), kMetC2 = (float)(0.03 * 0.03);   // Python doubles, rounded where they meet float32
 
 // float32(exp(-0.5 ((i-5)/1.5)^2)) / float32 sum, as torch evaluates the filter of the reference's compute_ssim
@@ -68,60 +65,6 @@ __device__ __forceinline__ float quantise(float x, float& level) {
     return x;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-    return v;
-}
-
-// sum over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) r += s_red[w];
-    }
-    __syncthreads();
-    return r;
-}
-
-// 14 neighbouring values of LDS row `row`, from column 4 * quad (two columns more are read and not used)
-__device__ __forceinline__ void met_read_span(const float* __restrict__ s, int row, int quad, float (&v)[16]) {
-    const float4* p = reinterpret_cast<const float4*>(s + row * kMetRawStride + 4 * quad);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 q = p[j];
-        v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
-    }
-}
-
-// 4 neighbouring outputs of the 11-tap valid filter over a span
-__device__ __forceinline__ void met_filter_span(const float (&v)[16], float (&o)[4]) {
-    const float w[kMetTaps] = SR_METRIC_TAPS;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < kMetTaps; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaf(w[t], v[j + t], o[j]);
-}
-
-// column pass: 4 neighbouring outputs of row `row` from a row-filtered plane [kMetRaw][kMetTile].  A wavefront reads
-// 8 quads x 8 rows = 1 KiB of consecutive LDS per tap: no bank conflict.
-__device__ __forceinline__ void met_filter_column(const float* __restrict__ s, int row, int quad, float (&o)[4]) {
-    const float w[kMetTaps] = SR_METRIC_TAPS;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < kMetTaps; ++t) {
-        const float4 q = *reinterpret_cast<const float4*>(s + (row + t) * kMetTile + 4 * quad);
-        o[0] = fmaf(w[t], q.x, o[0]); o[1] = fmaf(w[t], q.y, o[1]); o[2] = fmaf(w[t], q.z, o[2]); o[3] = fmaf(w[t], q.w, o[3]);
-    }
-}
-
 // the partial convolution's normalisation: n of the 11 window pixels are inside the mask
 __device__ __forceinline__ float met_normalise(float r, int n) { return n != 0 ? __fdiv_rn(r * 11.0f, (float)n) : 0.0f; }
 
@@ -131,18 +74,18 @@ template <bool kMasked, int kQuant>
 __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const float* __restrict__ pred, const float* __restrict__ gt,
                                                     const float* __restrict__ mask, unsigned char* __restrict__ frames,
                                                     double* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) float s_raw[2][kMetRaw * kMetRawStride];
-    __shared__ __attribute__((aligned(16))) float s_row[5][kMetRaw * kMetTile];
+    __shared__ __attribute__((aligned(16))) float s_raw[2][kWinRaw * kWinRawStride];
+    __shared__ __attribute__((aligned(16))) float s_row[5][kWinRaw * kWinTile];
     // the mask and the first pass's mask as bytes (0 / 1): the masked kernel keeps three workgroups on a compute unit
-    __shared__ __attribute__((aligned(16))) unsigned char s_mask[kMasked ? kMetRaw * kMetRawStride : 16];
-    __shared__ __attribute__((aligned(16))) unsigned char s_m1[kMasked ? kMetRaw * kMetTile : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char s_mask[kMasked ? kWinRaw * kWinRawStride : 16];
+    __shared__ __attribute__((aligned(16))) unsigned char s_m1[kMasked ? kWinRaw * kWinTile : 16];
     __shared__ double s_red[kBlock / kWave];
 
     const unsigned per_plane = (unsigned)d.tiles_x * (unsigned)d.tiles_y;
     const unsigned plane = blockIdx.x / per_plane, t_in = blockIdx.x - plane * per_plane;
     const int ty = (int)(t_in / (unsigned)d.tiles_x), tx = (int)(t_in - (unsigned)ty * (unsigned)d.tiles_x);
     const int item = (int)(plane / 3u), ch = (int)(plane - 3u * (unsigned)item);
-    const int x0 = tx * kMetTile, y0 = ty * kMetTile;
+    const int x0 = tx * kWinTile, y0 = ty * kWinTile;
     const int H = d.H, W = d.W;
     const bool last_x = tx == d.tiles_x - 1, last_y = ty == d.tiles_y - 1;
     const float* pp = pred + (long long)item * d.ps[0] + (long long)ch * d.ps[1];
@@ -151,7 +94,7 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
 
     // ---- stage the 42 x 42 region: quantise, add up the squared error of the owned pixels, mask ----
     double sum_se = 0.0;
-    for (int i = threadIdx.x; i < kMetRaw * kMetGroups; i += kBlock) {
+    for (int i = threadIdx.x; i < kWinRaw * kMetGroups; i += kBlock) {
         const int r = i / kMetGroups, g = i - r * kMetGroups;
         const int gy = y0 + r, gx0 = x0 + 4 * g;
         float xv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, yv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -180,7 +123,7 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
                     }
                 }
             }
-            const bool own_row = r < kMetTile || last_y;
+            const bool own_row = r < kWinTile || last_y;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j < n) {
@@ -189,7 +132,7 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
                     xv[j] = quantise<kQuant>(xv[j], level);
                     float unused;
                     yv[j] = quantise<kQuant>(yv[j], unused);
-                    if (own_row && (c < kMetTile || (last_x && c < kMetRaw))) {
+                    if (own_row && (c < kWinTile || (last_x && c < kWinRaw))) {
                         const double diff = (double)(xv[j] - yv[j]);
                         sum_se += diff * diff;
                         if (kQuant != SR_QUANT_NONE && frames)
@@ -204,31 +147,33 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
                 }
             }
         }
-        *reinterpret_cast<float4*>(&s_raw[0][r * kMetRawStride + 4 * g]) = make_float4(xv[0], xv[1], xv[2], xv[3]);
-        *reinterpret_cast<float4*>(&s_raw[1][r * kMetRawStride + 4 * g]) = make_float4(yv[0], yv[1], yv[2], yv[3]);
-        if (kMasked) *reinterpret_cast<unsigned*>(&s_mask[r * kMetRawStride + 4 * g]) = mbytes;
+        *reinterpret_cast<float4*>(&s_raw[0][r * kWinRawStride + 4 * g]) = make_float4(xv[0], xv[1], xv[2], xv[3]);
+        *reinterpret_cast<float4*>(&s_raw[1][r * kWinRawStride + 4 * g]) = make_float4(yv[0], yv[1], yv[2], yv[3]);
+        if (kMasked) *reinterpret_cast<unsigned*>(&s_mask[r * kWinRawStride + 4 * g]) = mbytes;
     }
     __syncthreads();
 
+    const float taps[kWinTaps] = SR_METRIC_TAPS;
+
     // ---- rows: five quantities along W ----
-    for (int it = threadIdx.x; it < kMetRaw * kMetQuads; it += kBlock) {
-        const int r = it / kMetQuads, q = it % kMetQuads;
+    for (int it = threadIdx.x; it < kWinRaw * kWinQuads; it += kBlock) {
+        const int r = it / kWinQuads, q = it % kWinQuads;
         float x[16], y[16], p[16], o[5][4];
-        met_read_span(s_raw[0], r, q, x);
-        met_read_span(s_raw[1], r, q, y);
-        met_filter_span(x, o[0]);
-        met_filter_span(y, o[1]);
+        win_read_span(s_raw[0], r, q, x);
+        win_read_span(s_raw[1], r, q, y);
+        win_filter_span(taps, x, o[0]);
+        win_filter_span(taps, y, o[1]);
 #pragma unroll
         for (int j = 0; j < 14; ++j) p[j] = x[j] * x[j];
-        met_filter_span(p, o[2]);
+        win_filter_span(taps, p, o[2]);
 #pragma unroll
         for (int j = 0; j < 14; ++j) p[j] = y[j] * y[j];
-        met_filter_span(p, o[3]);
+        win_filter_span(taps, p, o[3]);
 #pragma unroll
         for (int j = 0; j < 14; ++j) p[j] = x[j] * y[j];
-        met_filter_span(p, o[4]);
+        win_filter_span(taps, p, o[4]);
         if (kMasked) {
-            const unsigned* mw = reinterpret_cast<const unsigned*>(&s_mask[r * kMetRawStride + 4 * q]);
+            const unsigned* mw = reinterpret_cast<const unsigned*>(&s_mask[r * kWinRawStride + 4 * q]);
             int b[16];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -239,9 +184,9 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
             int n[4];
             n[0] = 0;
 #pragma unroll
-            for (int t = 0; t < kMetTaps; ++t) n[0] += b[t];
+            for (int t = 0; t < kWinTaps; ++t) n[0] += b[t];
 #pragma unroll
-            for (int j = 1; j < 4; ++j) n[j] = n[j - 1] - b[j - 1] + b[j + kMetTaps - 1];
+            for (int j = 1; j < 4; ++j) n[j] = n[j - 1] - b[j - 1] + b[j + kWinTaps - 1];
             unsigned m1 = 0u;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -249,23 +194,23 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
 #pragma unroll
                 for (int k = 0; k < 5; ++k) o[k][j] = met_normalise(o[k][j], n[j]);
             }
-            *reinterpret_cast<unsigned*>(&s_m1[r * kMetTile + 4 * q]) = m1;
+            *reinterpret_cast<unsigned*>(&s_m1[r * kWinTile + 4 * q]) = m1;
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k)
-            *reinterpret_cast<float4*>(&s_row[k][r * kMetTile + 4 * q]) = make_float4(o[k][0], o[k][1], o[k][2], o[k][3]);
+            *reinterpret_cast<float4*>(&s_row[k][r * kWinTile + 4 * q]) = make_float4(o[k][0], o[k][1], o[k][2], o[k][3]);
     }
     __syncthreads();
 
     // ---- columns: the same along H, then the similarity of this thread's 4 outputs ----
-    const int row = threadIdx.x / kMetQuads, quad = threadIdx.x % kMetQuads;
+    const int row = threadIdx.x / kWinQuads, quad = threadIdx.x % kWinQuads;
     float o[5][4];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) met_filter_column(s_row[k], row, quad, o[k]);
+    for (int k = 0; k < 5; ++k) win_filter_column(taps, s_row[k], row, quad, o[k]);
     if (kMasked) {
         unsigned packed = 0u;   // four byte counters, at most 11 each
 #pragma unroll
-        for (int t = 0; t < kMetTaps; ++t) packed += *reinterpret_cast<const unsigned*>(&s_m1[(row + t) * kMetTile + 4 * quad]);
+        for (int t = 0; t < kWinTaps; ++t) packed += *reinterpret_cast<const unsigned*>(&s_m1[(row + t) * kWinTile + 4 * quad]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int n = (int)((packed >> (8 * j)) & 0xffu);
@@ -288,7 +233,7 @@ __global__ void __launch_bounds__(kBlock) k_metrics(const MetricDims d, const fl
         const float v = __fdiv_rn(numer, denom);
         if (j < n_valid) sum_s += v;
     }
-    const double bs = block_sum_f64((double)sum_s, s_red), be = block_sum_f64(sum_se, s_red);
+    const double bs = block_sum((double)sum_s, s_red), be = block_sum(sum_se, s_red);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = bs;
         partial[(size_t)gridDim.x + blockIdx.x] = be;
@@ -315,9 +260,9 @@ __global__ void __launch_bounds__(kMetReduceBlock) k_metrics_reduce(int batch, u
                 acc_e[c] += partial[blocks + first + t];
             }
         }
-        acc_s = wave_sum_f64(acc_s);
+        acc_s = wave_sum(acc_s);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc_e[c] = wave_sum_f64(acc_e[c]);
+        for (int c = 0; c < 3; ++c) acc_e[c] = wave_sum(acc_e[c]);
         if (lane == 0) {
             ssim[b] = (float)(acc_s / out_per_item);
             const double mse = ((acc_e[0] + acc_e[1]) + acc_e[2]) / (3.0 * px_per_plane);
@@ -332,15 +277,13 @@ __global__ void __launch_bounds__(kMetReduceBlock) k_metrics_reduce(int batch, u
 // takes fewer than 2^32 threads, so at most (2^32 - 1) / 256 workgroups
 constexpr size_t kMetMaxBlocks = 0xffffffffull / kBlock;
 size_t metric_blocks(int batch, int H, int W) {
-    if (batch <= 0 || H < kMetTaps || W < kMetTaps) return 0;
-    const size_t ty = (size_t)(H - kMetTaps + 1 + kMetTile - 1) / kMetTile, tx = (size_t)(W - kMetTaps + 1 + kMetTile - 1) / kMetTile;
+    if (batch <= 0 || H < kWinTaps || W < kWinTaps) return 0;
+    const size_t ty = (size_t)(H - kWinTaps + 1 + kWinTile - 1) / kWinTile, tx = (size_t)(W - kWinTaps + 1 + kWinTile - 1) / kWinTile;
     const size_t per_plane = ty * tx;   // < 2^52
     if (per_plane > kMetMaxBlocks || (size_t)batch > kMetMaxBlocks / 3u) return 0;
     const size_t n = (size_t)batch * 3u * per_plane;
     return n <= kMetMaxBlocks ? n : 0;
 }
-
-bool met_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <bool kMasked>
 void launch_metrics_quant(int quantize, unsigned nb, hipStream_t st, const MetricDims& d, const float* pred, const float* gt,
@@ -367,10 +310,10 @@ void launch_image_metrics(int batch, int H, int W, const float* pred, const long
                           float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, hipStream_t st) {
     MetricDims d;
     d.batch = batch; d.H = H; d.W = W;
-    d.out_h = H - kMetTaps + 1; d.out_w = W - kMetTaps + 1;
-    d.tiles_x = (d.out_w + kMetTile - 1) / kMetTile; d.tiles_y = (d.out_h + kMetTile - 1) / kMetTile;
+    d.out_h = H - kWinTaps + 1; d.out_w = W - kWinTaps + 1;
+    d.tiles_x = (d.out_w + kWinTile - 1) / kWinTile; d.tiles_y = (d.out_h + kWinTile - 1) / kWinTile;
     d.mask_item = mask_item_stride;
-    bool vec = (W % 4) == 0 && met_aligned16(pred) && met_aligned16(gt) && met_aligned16(mask) && (mask_item_stride % 4) == 0;
+    bool vec = (W % 4) == 0 && aligned16(pred) && aligned16(gt) && aligned16(mask) && (mask_item_stride % 4) == 0;
     for (int k = 0; k < 4; ++k) {
         d.ps[k] = pred_strides[k]; d.gs[k] = gt_strides[k];
         if (k < 3) vec = vec && (pred_strides[k] % 4) == 0 && (gt_strides[k] % 4) == 0;

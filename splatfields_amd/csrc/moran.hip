@@ -25,6 +25,7 @@
 //
 // No floating-point atomics anywhere: values and gradients are bit-identical from call to call.
 #include "kernels.h"
+#include "reduce.h"
 #include <type_traits>
 
 namespace sr {
@@ -99,21 +100,6 @@ __device__ __forceinline__ void moran_channel(const float (&c)[K][K], const floa
     }
 }
 
-// sum over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ float moran_block_sum(float v, float* s_red) {
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    float r = 0.0f;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) r += s_red[w];
-    }
-    __syncthreads();
-    return r;
-}
-
 __device__ __forceinline__ int moran_item_of_slot(const MoranSource& s, int slot) { return s.order ? (int)s.order[slot] : slot; }
 
 // partial: [tensors][blocks]
@@ -145,7 +131,7 @@ __global__ void __launch_bounds__(kBlock) k_moran_forward(const MoranSource s, c
 #pragma unroll
     for (int t = 0; t < kMoranMaxTensors; ++t) {
         if (t >= T.count) break;
-        const float v = moran_block_sum(acc[t], s_red);
+        const float v = block_sum(acc[t], s_red);
         if (threadIdx.x == 0) partial[(size_t)t * gridDim.x + blockIdx.x] = v;
     }
 }
@@ -158,6 +144,7 @@ __global__ void __launch_bounds__(kMoranReduceBlock) k_moran_reduce(size_t block
     for (int t = 0; t < T.count; ++t) {
         double acc = 0.0;
         for (size_t i = threadIdx.x; i < blocks; i += kMoranReduceBlock) acc += (double)partial[(size_t)t * blocks + i];
+        // block_tree_sum (reduce.h) written out: the division sits in front of the last barrier, where the helper would put it behind
         sh[threadIdx.x] = acc;
         __syncthreads();
         for (int d = kMoranReduceBlock / 2; d > 0; d >>= 1) {

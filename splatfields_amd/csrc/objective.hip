@@ -26,6 +26,7 @@
 // same order, which saves the launch a separate mean kernel would take.  Forward: 2 launches, 3 with the centred norm; depth
 // L1: 2.  Backward: 1 each.  No floating-point atomics, no host wait: identical bits from call to call.
 #include "kernels.h"
+#include "reduce.h"
 
 namespace sr {
 
@@ -33,26 +34,6 @@ namespace {
 
 constexpr int kObjMaxBlocks = 512;       // partial sums per quantity: the second stage and the mean are sums over at most these
 constexpr int kObjDepthItemBlocks = 256; // workgroups (= partial sums) per depth item at most
-
-__device__ __forceinline__ double obj_wave_sum(double v) {
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
-    return v;
-}
-
-// sum over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ double obj_block_sum(double v, double* s_red) {
-    v = obj_wave_sum(v);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) r += s_red[w];
-    }
-    __syncthreads();
-    return r;
-}
 
 // float lanes between the 16-byte boundary at or below p and p
 inline int obj_lead(const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u); }
@@ -113,7 +94,7 @@ __device__ __forceinline__ void reg_mean(const RegDims& d, const double* __restr
     if (wave < 3) {
         double acc = 0.0;
         for (int b = lane; b < d.blocks; b += kWave) acc += partial[(size_t)(kSumX + wave) * kObjMaxBlocks + b];
-        acc = obj_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) s_mean[wave] = (double)(float)(acc / (double)d.n);     // the reference's mean is a float32 tensor
     }
     __syncthreads();
@@ -165,12 +146,12 @@ __global__ void __launch_bounds__(kBlock) k_splat_reg_partial(const RegDims d, c
         if (opacity) { const double e = (double)o[edge] - 1.0; a_o += e * e; }
     }
     if (kCentred) {
-        const double s = obj_block_sum(a_len, s_red);
+        const double s = block_sum(a_len, s_red);
         if (threadIdx.x == 0) partial[(size_t)kSumCentred * kObjMaxBlocks + blockIdx.x] = s;
         return;
     }
-    const double s_len = obj_block_sum(a_len, s_red), s_x = obj_block_sum(a_x, s_red), s_y = obj_block_sum(a_y, s_red);
-    const double s_z = obj_block_sum(a_z, s_red), s_o = obj_block_sum(a_o, s_red);
+    const double s_len = block_sum(a_len, s_red), s_x = block_sum(a_x, s_red), s_y = block_sum(a_y, s_red);
+    const double s_z = block_sum(a_z, s_red), s_o = block_sum(a_o, s_red);
     if (threadIdx.x == 0) {
         partial[(size_t)kSumNorm * kObjMaxBlocks + blockIdx.x] = s_len;
         partial[(size_t)kSumX * kObjMaxBlocks + blockIdx.x] = s_x;
@@ -194,7 +175,7 @@ __global__ void __launch_bounds__(kBlock) k_splat_reg_final(const RegDims d, dou
         const bool used = q == kSumNorm ? d.want_norm != 0 : (q == kSumOpacity ? d.want_opacity != 0 : d.want_mean != 0);
         if (used)
             for (int b = threadIdx.x; b < d.blocks; b += kBlock) acc += partial[(size_t)q * kObjMaxBlocks + b];
-        total[q] = obj_block_sum(acc, s_red);
+        total[q] = block_sum(acc, s_red);
     }
     if (threadIdx.x == 0) {
         const double n = (double)d.n;
@@ -339,7 +320,7 @@ __global__ void __launch_bounds__(kBlock) k_depth_l1_partial(const DepthDims d, 
                 if (i >= lead && i < end) acc += depth_term(pd[i], pg[i]);
         }
     }
-    const double s = obj_block_sum(acc, s_red);
+    const double s = block_sum(acc, s_red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -350,13 +331,13 @@ __global__ void __launch_bounds__(kBlock) k_depth_l1_final(const DepthDims d, co
     for (int b = wave; b < d.batch; b += kBlock / kWave) {
         double acc = 0.0;
         for (int k = lane; k < d.item_blocks; k += kWave) acc += partial[(size_t)b * d.item_blocks + k];
-        acc = obj_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) out[1 + b] = (float)(acc / (double)d.pixels);
     }
     double acc = 0.0;
     const long long count = (long long)d.batch * d.item_blocks;
     for (long long i = threadIdx.x; i < count; i += kBlock) acc += partial[i];
-    const double total = obj_block_sum(acc, s_red);
+    const double total = block_sum(acc, s_red);
     if (threadIdx.x == 0) out[0] = (float)(total / ((double)d.batch * (double)d.pixels));
 }
 

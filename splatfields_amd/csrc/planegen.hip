@@ -18,6 +18,7 @@
 // zero AFTER the activation (the padding belongs to the activated, upsampled tensor).
 // No floating-point atomics; reductions are LDS trees and fixed-order loops over partials.
 #include "kernels.h"
+#include "reduce.h"
 
 namespace sr {
 
@@ -41,39 +42,10 @@ __device__ __forceinline__ float dsilu(float y) {
     return s * (1.f + y * (1.f - s));
 }
 
-// sum over the workgroup in a fixed tree; `red` holds kBlock floats
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // ---- GroupNorm statistics ---------------------------------------------------------------------------------------------------
 // The sums are doubles, and the mean is handed on as a float pair (mean, mean_lo): where a group holds few, nearly equal values
 // rstd is large and the rounding of a float mean (half an ulp of |x|) would come out of (x - mean) rstd amplified.
 constexpr int kStat = 4;      // floats per group in `stats`: mean, rstd, mean_lo, unused
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 // grid (chunks, groups, planes): (mean, M2) of one chunk of a group's contiguous values
 __global__ __launch_bounds__(kBlock) void k_gn_stats_partial(const PlaneTable t, int group_elems, int nchunks, double* __restrict__ ws) {
@@ -88,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_gn_stats_partial(const PlaneTable t,
         v[i] = idx < hi ? x[idx] : 0.f;
         s += (double)v[i];
     }
-    const double mean = block_sum_d(s, red) / (double)(hi - lo);
+    const double mean = block_tree_sum<double, kBlock>(s, red) / (double)(hi - lo);
     double q = 0.0;
 #pragma unroll
     for (int i = 0; i < kGnChunk / kBlock; ++i) {
@@ -96,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void k_gn_stats_partial(const PlaneTable t,
         const double d = (double)v[i] - mean;
         q += idx < hi ? d * d : 0.0;
     }
-    const double m2 = block_sum_d(q, red);
+    const double m2 = block_tree_sum<double, kBlock>(q, red);
     if (threadIdx.x == 0) {
         double* o = ws + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nchunks + blockIdx.x) * 2;
         o[0] = mean; o[1] = m2;
@@ -388,10 +360,10 @@ constexpr int kGnSmall = 1024;
 __device__ __forceinline__ void group_stats_d(const float* __restrict__ xg, int n, double eps, double* red, double* mean, double* rstd) {
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) s += (double)xg[i];
-    const double m = block_sum_d(s, red) / (double)n;
+    const double m = block_tree_sum<double, kBlock>(s, red) / (double)n;
     double q = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) { const double d = (double)xg[i] - m; q += d * d; }
-    const double var = block_sum_d(q, red) / (double)n;
+    const double var = block_tree_sum<double, kBlock>(q, red) / (double)n;
     *mean = m;
     *rstd = 1.0 / sqrt(var + eps);
 }
@@ -440,8 +412,8 @@ __global__ __launch_bounds__(kBlock) void k_gn_bwd_partial(const PlaneTable t, c
         }
         s1 = f1; s2 = f2;
     }
-    s1 = block_sum_d(s1, red);
-    s2 = block_sum_d(s2, red);
+    s1 = block_tree_sum<double, kBlock>(s1, red);
+    s2 = block_tree_sum<double, kBlock>(s2, red);
     if (threadIdx.x == 0) {
         double* o = ws + (((size_t)blockIdx.z * a.channels + c) * a.nchunks + blockIdx.x) * 2;
         o[0] = s1; o[1] = s2;

@@ -29,12 +29,9 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 PARAM_NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")   # the reference's optimizer group names
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional[Dict[str, tuple]], grad_accum: torch.Tensor,
@@ -53,7 +50,7 @@ def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional
     src = {k: f32(params[k]) for k in PARAM_NAMES}
     scale_cols = math.prod(src["scaling"].shape[1:])        # not reshape(n, -1): N may be 0
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         if unit_normals is None:
             unit_normals = torch.randn(2, n, 3, device=dev, dtype=torch.float32, generator=generator)
         unit_normals = f32(unit_normals)
@@ -63,9 +60,9 @@ def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional
         dest = torch.empty(4, max(n, 1), dtype=torch.int32, device=dev)
         counts = (C.c_longlong * 5)()
         radii = f32(max_radii2D).reshape(-1) if (screen_test_on_accumulated_radii and max_radii2D is not None) else None
-        _lib.check(lib.sr_densify_plan(n, _ptr(src["scaling"]), scale_cols, _ptr(src["opacity"]), _ptr(f32(grad_accum).reshape(-1)),
-                                       _ptr(f32(denom).reshape(-1)), _ptr(radii), float(max_grad), float(min_opacity), float(extent),
-                                       float(percent_dense), float(max_screen_size or 0.0), _ptr(ws), _ptr(dest), counts, stream))
+        _lib.check(lib.sr_densify_plan(n, ptr(src["scaling"]), scale_cols, ptr(src["opacity"]), ptr(f32(grad_accum).reshape(-1)),
+                                       ptr(f32(denom).reshape(-1)), ptr(radii), float(max_grad), float(min_opacity), float(extent),
+                                       float(percent_dense), float(max_screen_size or 0.0), ptr(ws), ptr(dest), counts, stream))
         kept, clones, c1, c2, total = [int(c) for c in counts]
 
         def gather(t, mode):
@@ -73,8 +70,8 @@ def densify_and_prune_tensors(params: Dict[str, torch.Tensor], moments: Optional
             out = torch.empty((total,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)
             if n == 0 or total == 0:                         # nothing to write: the reference returns tensors of 0 rows
                 return out
-            _lib.check(lib.sr_densify_gather(n, row, _ptr(t), _ptr(out), _ptr(dest), mode, _ptr(src["scaling"]), scale_cols,
-                                             _ptr(src["rotation"]), _ptr(unit_normals), stream))
+            _lib.check(lib.sr_densify_gather(n, row, ptr(t), ptr(out), ptr(dest), mode, ptr(src["scaling"]), scale_cols,
+                                             ptr(src["rotation"]), ptr(unit_normals), stream))
             return out
 
         mode_of = {"xyz": 2, "scaling": 3}

@@ -12,12 +12,12 @@ plus about ten small kernels per iteration.  ``densification_stats`` does the sa
 ``sr_densification_stats`` and no synchronisation."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 
 from . import _lib
+from ._lib import ptr as p
 
 
 def densification_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, xyz_gradient_accum: Optional[torch.Tensor],
@@ -39,7 +39,5 @@ def densification_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, xyz_g
     for name, t in (("xyz_gradient_accum", xyz_gradient_accum), ("denom", denom), ("max_radii2D", max_radii2D)):
         if t is not None and (t.dtype is not torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != dev):
             raise RuntimeError(f"{name} must be a contiguous float32 tensor with N elements on the same device (updated in place)")
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     with torch.cuda.device(dev):
-        _lib.check(lib.sr_densification_stats(n, p(g), p(r), p(xyz_gradient_accum), p(denom), p(max_radii2D),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(lib.sr_densification_stats(n, p(g), p(r), p(xyz_gradient_accum), p(denom), p(max_radii2D), _lib.stream(dev)))

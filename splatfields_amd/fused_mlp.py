@@ -94,7 +94,8 @@ def pack_layer_weight_bf16(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width:
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     """the tensor as contiguous float32 -- itself when it already is (the usual case: one attribute
-    test instead of three tensor methods; ~50 of these per network and step are host time the GPU waits for)"""
+    test instead of three tensor methods; ~50 of these per network and step are host time the GPU waits for).
+    Not _lib.f32c, which detaches first: one tensor method more on that usual case."""
     if t.dtype is torch.float32 and t.is_contiguous():
         return t          # only its data pointer is used; autograd.Function inputs may be saved as they are
     return t.detach().to(torch.float32).contiguous()
@@ -195,8 +196,8 @@ class _Plan:
             for obj, field, sym, idx, off in binds:
                 setattr(obj, field, ptrs[sym][idx] + off)
             pack, chain = (lib.sr_mlp_pack_bf16, lib.sr_mlp_chain_bf16) if self.bf16 else (lib.sr_mlp_pack, lib.sr_mlp_chain)
-            _lib.check(pack(len(jobs), jobs, C.c_void_p(stream)))
-            _lib.check(chain(n_points, ht, len(ops), ops, slope, C.c_void_p(stream)))
+            _lib.check(pack(len(jobs), jobs, stream))
+            _lib.check(chain(n_points, ht, len(ops), ops, slope, stream))
         return buf      # alive until the caller drops it; the stream orders its reuse
 
 
@@ -234,7 +235,7 @@ def _forward(shape: _Shape, x0: torch.Tensor, weights, biases, slope: float, sav
             "acts": [acts.data_ptr() + 4 * j * n * H for j in range(L - 1)] if save else (),
             "signs": [signs.data_ptr() + 16 * j * n for j in range(L - 1)] if save else ()}
     with torch.cuda.device(dev):
-        _forward_plan(shape, save, precision).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
+        _forward_plan(shape, save, precision).run(lib, ptrs, dev, n, shape.ht, slope, _lib.stream(dev))
     return y, acts, signs
 
 
@@ -275,7 +276,7 @@ def _top_gradient(lib, shape: _Shape, y, dY, slope: float, G):
     dev = y.device
     with torch.cuda.device(dev):
         _lib.check(lib.sr_mlp_top_gradient(y.shape[0], shape.out_features, shape.out_pad, C.c_void_p(y.data_ptr()), C.c_void_p(dY.data_ptr()),
-                                           slope, C.c_void_p(G.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                           slope, C.c_void_p(G.data_ptr()), _lib.stream(dev)))
 
 
 def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input: bool, signs=None, precision: str = "fp32"):
@@ -291,7 +292,7 @@ def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input:
             "acts": [acts.data_ptr() + 4 * j * n * H for j in range(L - 1)], "dz": [dz.data_ptr() + 4 * j * n * H for j in range(L - 1)],
             "signs": [signs.data_ptr() + 16 * j * n for j in range(L - 1)] if signs is not None else ()}
     with torch.cuda.device(dev):
-        _backward_plan(shape, need_input, signs is not None, precision).run(lib, ptrs, dev, n, shape.ht, slope, torch.cuda.current_stream(dev).cuda_stream)
+        _backward_plan(shape, need_input, signs is not None, precision).run(lib, ptrs, dev, n, shape.ht, slope, _lib.stream(dev))
     return dx0, G, dz
 
 
@@ -347,8 +348,7 @@ def _weight_grads(shape: _Shape, x0, acts, G, dz, weights):
                 raise ValueError("unsupported weight-gradient job list: " + lib.sr_last_error().decode("utf-8", "replace"))
             ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.sr_mlp_weight_grad(cnt, len(jobs), arr, C.c_void_p(ws.data_ptr()), ws_bytes,
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                _lib.check(lib.sr_mlp_weight_grad(cnt, len(jobs), arr, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
         if total_W is None:
             total_W, total_b = dWs, dbs
         else:      # fixed chunk order: still deterministic
@@ -413,8 +413,7 @@ class _FusedMLPPointsFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(lib.sr_mlp_input_forward(n, multires, n_feat, time_multires, shape.mem_pad, C.c_void_p(x32.data_ptr()),
                                                 C.c_void_p(f32.data_ptr()) if f32 is not None else None,
-                                                C.c_void_p(t32.data_ptr()) if t32 is not None else None, C.c_void_p(x0.data_ptr()),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                C.c_void_p(t32.data_ptr()) if t32 is not None else None, C.c_void_p(x0.data_ptr()), _lib.stream(dev)))
         need = grad_enabled and any(ctx.needs_input_grad)
         y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need, precision=precision)
         if need:
@@ -438,8 +437,7 @@ class _FusedMLPPointsFn(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.check(lib.sr_mlp_input_backward(n, ctx.multires, ctx.n_feat, shape.mem_pad, C.c_void_p(x32.data_ptr()),
                                                      C.c_void_p(dx0.data_ptr()), C.c_void_p(d_xyz.data_ptr()) if need_xyz else None,
-                                                     C.c_void_p(d_feat.data_ptr()) if need_feat else None,
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                     C.c_void_p(d_feat.data_ptr()) if need_feat else None, _lib.stream(dev)))
         dWs, dbs = [None] * L, [None] * L
         if any(ctx.needs_input_grad[9:]):
             dWs, dbs = _weight_grads(shape, x0, acts, G, dz, weights)
@@ -550,8 +548,7 @@ class _PointLinearFn(torch.autograd.Function):
                     raise ValueError("unsupported weight-gradient job: " + lib.sr_last_error().decode("utf-8", "replace"))
                 ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
                 with torch.cuda.device(dev):
-                    _lib.check(lib.sr_mlp_weight_grad(cnt, 1, job, C.c_void_p(ws.data_ptr()), ws_bytes,
-                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                    _lib.check(lib.sr_mlp_weight_grad(cnt, 1, job, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
                 if lo:
                     dW.add_(pW)
                     db.add_(pb)

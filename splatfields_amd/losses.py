@@ -13,27 +13,16 @@ backward (``sr_photometric_backward``): no host synchronisation, no floating-poi
 to call.  There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 
 from . import _lib
+from ._lib import f32c, ptr
 
 WINDOW_SIZE = 11   # the kernels are built for the reference's window: 11 taps, sigma 1.5
 
 _FUSED, _L1, _SSIM = 0, 1, 2
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    if t.dtype is not torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
-    return t
 
 
 def _run_forward(x, y, a, m, shape, lambda_dssim, lambda_mask, with_ssim, with_maps):
@@ -47,10 +36,9 @@ def _run_forward(x, y, a, m, shape, lambda_dssim, lambda_mask, with_ssim, with_m
         out = torch.empty(3 + batch, dtype=torch.float32, device=dev)   # loss | l1 | mask_l1 (written with a mask only) | ssim [batch]
         maps = torch.empty((3,) + tuple(x.shape), dtype=torch.float32, device=dev) if with_maps else None
         ssim_out = out[3:] if with_ssim else None
-        _lib.check(lib.sr_photometric_forward(batch, channels, h, w, _ptr(x), _ptr(y), _ptr(a), _ptr(m), float(lambda_dssim),
-                                              float(lambda_mask), _ptr(work), _ptr(maps), _ptr(out[0:1]), _ptr(out[1:2]),
-                                              _ptr(ssim_out), _ptr(out[2:3]) if a is not None else None,
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(lib.sr_photometric_forward(batch, channels, h, w, ptr(x), ptr(y), ptr(a), ptr(m), float(lambda_dssim),
+                                              float(lambda_mask), ptr(work), ptr(maps), ptr(out[0:1]), ptr(out[1:2]),
+                                              ptr(ssim_out), ptr(out[2:3]) if a is not None else None, _lib.stream(dev)))
     return out[0], out[1], out[3:], out[2], maps
 
 
@@ -60,9 +48,9 @@ class _Photometric(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, gt, opacity, gt_mask, mode, shape, lambda_dssim, lambda_mask):
-        x, y = _f32(image), _f32(gt)
-        a = None if opacity is None else _f32(opacity)
-        m = None if gt_mask is None else _f32(gt_mask)
+        x, y = f32c(image), f32c(gt)
+        a = None if opacity is None else f32c(opacity)
+        m = None if gt_mask is None else f32c(gt_mask)
         with_ssim = mode != _L1
         loss, l1, ssim_items, mask_l1, maps = _run_forward(x, y, a, m, shape, lambda_dssim, lambda_mask, with_ssim, with_maps=with_ssim)
         ctx.save_for_backward(x, y, a, m, maps)
@@ -84,7 +72,7 @@ class _Photometric(torch.autograd.Function):
         g = {_FUSED: g_loss, _L1: g_l1, _SSIM: g_ssim}[ctx.mode]
         if g is None:
             return (None,) * 8
-        g = _f32(g)
+        g = f32c(g)
         per_item = ctx.mode == _SSIM
         dev = x.device
         want_alpha = a is not None and ctx.needs_input_grad[2]
@@ -92,9 +80,8 @@ class _Photometric(torch.autograd.Function):
             d_image = torch.empty_like(x)
             d_alpha = torch.empty_like(a) if want_alpha else None
             w_l1, w_ssim, w_mask = ctx.weights
-            _lib.check(lib.sr_photometric_backward(batch, channels, h, w, _ptr(x), _ptr(y), _ptr(a), _ptr(m), _ptr(maps), w_l1, w_ssim,
-                                                   w_mask, _ptr(g), int(per_item), _ptr(d_image), _ptr(d_alpha),
-                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(lib.sr_photometric_backward(batch, channels, h, w, ptr(x), ptr(y), ptr(a), ptr(m), ptr(maps), w_l1, w_ssim,
+                                                   w_mask, ptr(g), int(per_item), ptr(d_image), ptr(d_alpha), _lib.stream(dev)))
         shape, dt = ctx.image_meta
         d_image = d_image.reshape(shape).to(dt) if ctx.needs_input_grad[0] else None
         if want_alpha:
@@ -123,8 +110,8 @@ def _call(image, gt, opacity, gt_mask, mode, shape, lambda_dssim, lambda_mask):
     if tracked:
         return _Photometric.apply(image, gt, opacity, gt_mask, mode, shape, lambda_dssim, lambda_mask)
     # nothing to differentiate: no derivative maps are written and nothing is kept
-    loss, l1, ssim_items, mask_l1, _ = _run_forward(_f32(image), _f32(gt), None if opacity is None else _f32(opacity),
-                                                    None if gt_mask is None else _f32(gt_mask), shape, lambda_dssim, lambda_mask,
+    loss, l1, ssim_items, mask_l1, _ = _run_forward(f32c(image), f32c(gt), None if opacity is None else f32c(opacity),
+                                                    None if gt_mask is None else f32c(gt_mask), shape, lambda_dssim, lambda_mask,
                                                     with_ssim=mode != _L1, with_maps=False)
     dt = image.dtype
     return loss.to(dt), l1.to(dt), ssim_items.to(dt), mask_l1.to(dt)
@@ -193,10 +180,6 @@ def photometric_loss(image: torch.Tensor, gt_image: torch.Tensor, lambda_dssim: 
 # sr_splat_reg_* and sr_depth_l1_* (csrc/objective.hip).  A streaming pass and a fixed-order reduction forward, one kernel
 # backward; no host synchronisation, no floating-point atomics, bit-identical results from call to call.  No CPU path.
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _empty_in_phase(t: torch.Tensor) -> torch.Tensor:
     """An uninitialised float32 tensor of t's shape whose address agrees with t's modulo 16 (t: float32, contiguous): the
     kernels then store a gradient in the same 16-byte vectors they load its input in, whatever t's storage offset."""
@@ -220,7 +203,7 @@ def _run_splat_reg(x, o, weights):
     with torch.cuda.device(dev):
         work = torch.empty(lib.sr_splat_reg_workspace_bytes(n), dtype=torch.uint8, device=dev)
         out = torch.empty(8, dtype=torch.float32, device=dev)
-        _lib.check(lib.sr_splat_reg_forward(n, _ptr(x), _ptr(o), *weights, _ptr(work), _ptr(out), _stream(dev)))
+        _lib.check(lib.sr_splat_reg_forward(n, ptr(x), ptr(o), *weights, ptr(work), ptr(out), _lib.stream(dev)))
     return out
 
 
@@ -230,8 +213,8 @@ class _SplatReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, opacity, weights):
-        x = None if means3D is None else _f32(means3D)
-        o = None if opacity is None else _f32(opacity)
+        x = None if means3D is None else f32c(means3D)
+        o = None if opacity is None else f32c(opacity)
         out = _run_splat_reg(x, o, weights)
         n = (x if x is not None else o).shape[0]
         ctx.save_for_backward(x, o, out)
@@ -255,13 +238,12 @@ class _SplatReg(torch.autograd.Function):
         want_o = o is not None and ctx.needs_input_grad[1]
         if not want_x and not want_o:
             return None, None, None
-        g = _f32(g_loss)
+        g = f32c(g_loss)
         dev = out.device
         with torch.cuda.device(dev):
             d_x = _empty_in_phase(x) if want_x else None
             d_o = _empty_in_phase(o) if want_o else None
-            _lib.check(lib.sr_splat_reg_backward(ctx.n, _ptr(x), _ptr(o), lam_n, lam_nm, lam_o, _ptr(out), _ptr(g), _ptr(d_x), _ptr(d_o),
-                                                 _stream(dev)))
+            _lib.check(lib.sr_splat_reg_backward(ctx.n, ptr(x), ptr(o), lam_n, lam_nm, lam_o, ptr(out), ptr(g), ptr(d_x), ptr(d_o), _lib.stream(dev)))
         if want_x:
             shape, dt = ctx.x_meta
             d_x = d_x.reshape(shape).to(dt)
@@ -320,7 +302,7 @@ def splat_regularizers(means3D: Optional[torch.Tensor], opacity: Optional[torch.
     if torch.is_grad_enabled() and ((x is not None and x.requires_grad) or (o is not None and o.requires_grad)):
         loss, norm, norm_mean, opacity_reg = _SplatReg.apply(x, o, weights)
     else:       # nothing to differentiate: nothing is kept
-        out = _run_splat_reg(None if x is None else _f32(x), None if o is None else _f32(o), weights).to(first.dtype)
+        out = _run_splat_reg(None if x is None else f32c(x), None if o is None else f32c(o), weights).to(first.dtype)
         loss, norm, norm_mean, opacity_reg = out[0], out[1], out[2], out[3]
     values = {"norm": norm, "norm_mean": norm_mean, "opacity": opacity_reg}
     return loss, {k: values[k] for k in names}
@@ -350,7 +332,7 @@ def _run_depth_l1(d, g, shape):
     with torch.cuda.device(dev):
         work = torch.empty(lib.sr_depth_l1_workspace_bytes(batch, h, w), dtype=torch.uint8, device=dev)
         out = torch.empty(1 + batch, dtype=torch.float32, device=dev)
-        _lib.check(lib.sr_depth_l1_forward(batch, h, w, _ptr(d), _ptr(g), _ptr(work), _ptr(out), _stream(dev)))
+        _lib.check(lib.sr_depth_l1_forward(batch, h, w, ptr(d), ptr(g), ptr(work), ptr(out), _lib.stream(dev)))
     return out
 
 
@@ -359,7 +341,7 @@ class _DepthL1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, depth, gt, shape, per_item):
-        d, g = _f32(depth), _f32(gt)       # each converted to float32 on its own: a half-precision render does not round the target
+        d, g = f32c(depth), f32c(gt)       # each converted to float32 on its own: a half-precision render does not round the target
         out = _run_depth_l1(d, g, shape)
         ctx.save_for_backward(d, g)
         ctx.set_materialize_grads(False)
@@ -376,11 +358,11 @@ class _DepthL1(torch.autograd.Function):
         lib = _lib.load()
         d, g = ctx.saved_tensors
         batch, h, w = ctx.shape
-        up = _f32(up)
+        up = f32c(up)
         dev = d.device
         with torch.cuda.device(dev):
             grad = _empty_in_phase(d)
-            _lib.check(lib.sr_depth_l1_backward(batch, h, w, _ptr(d), _ptr(g), _ptr(up), int(ctx.per_item), _ptr(grad), _stream(dev)))
+            _lib.check(lib.sr_depth_l1_backward(batch, h, w, ptr(d), ptr(g), ptr(up), int(ctx.per_item), ptr(grad), _lib.stream(dev)))
         shape, dt = ctx.meta
         return grad.reshape(shape).to(dt), None, None, None
 
@@ -412,7 +394,7 @@ def depth_l1_loss(depth: torch.Tensor, gt_depth: torch.Tensor, size_average: boo
     if torch.is_grad_enabled() and depth.requires_grad:
         everything, items = _DepthL1.apply(depth, gt_depth, shape, not size_average)
         return everything if size_average else items
-    out = _run_depth_l1(_f32(depth), _f32(gt_depth), shape).to(depth.dtype)      # nothing to differentiate: nothing is kept
+    out = _run_depth_l1(f32c(depth), f32c(gt_depth), shape).to(depth.dtype)      # nothing to differentiate: nothing is kept
     return out[0] if size_average else out[1:]
 
 

@@ -16,18 +16,16 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 FILTER_SIZE = 11   # the kernel is built for the reference's defaults: 11 taps, sigma 1.5, k1 0.01, k2 0.03, max_val 1
 _DEFAULTS = {"max_val": 1.0, "filter_size": FILTER_SIZE, "filter_sigma": 1.5, "k1": 0.01, "k2": 0.03}
 _QUANT = {None: _lib.QUANT_NONE, "png": _lib.QUANT_PNG, "to8b": _lib.QUANT_TO8B}
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _f32(t: torch.Tensor) -> torch.Tensor:
-    """float32; any strides are kept (the kernel addresses by strides), only another dtype costs a copy"""
+    """float32; any strides are kept (the kernel addresses by strides), only another dtype costs a copy.  Not _lib.f32c, which
+    would make it contiguous."""
     t = t.detach()
     return t if t.dtype is torch.float32 else t.to(torch.float32)
 
@@ -106,9 +104,9 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
         work = torch.empty(lib.sr_metrics_workspace_bytes(batch, h, w), dtype=torch.uint8, device=dev)
         out = torch.empty(5 * batch, dtype=torch.float32, device=dev)   # psnr [B] | ssim [B] | psnr_channels [B,3]
         frames = torch.empty((batch, h, w, 3), dtype=torch.uint8, device=dev) if return_frames else None
-        _lib.check(lib.sr_image_metrics(batch, h, w, _ptr(x), _strides4(x, layout), _ptr(y), _strides4(y, layout), _ptr(m), mask_item,
-                                        _QUANT[quantize], _ptr(work), _ptr(out[:batch]), _ptr(out[batch:2 * batch]),
-                                        _ptr(out[2 * batch:]), _ptr(frames), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(lib.sr_image_metrics(batch, h, w, ptr(x), _strides4(x, layout), ptr(y), _strides4(y, layout), ptr(m), mask_item,
+                                        _QUANT[quantize], ptr(work), ptr(out[:batch]), ptr(out[batch:2 * batch]),
+                                        ptr(out[2 * batch:]), ptr(frames), _lib.stream(dev)))
     res = {"psnr": out[:batch], "ssim": out[batch:2 * batch], "psnr_channels": out[2 * batch:].reshape(batch, 3)}
     if return_frames:
         res["frames"] = frames

@@ -19,24 +19,10 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 
 from . import _lib
+from ._lib import f32c, ptr
 
 MAX_NEIGHBORS = _lib.KNN_MAX_K
 MAX_TENSORS = _lib.MORAN_MAX_TENSORS
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    if t.dtype is not torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
-    return t
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _pointer_array(tensors):
@@ -66,7 +52,7 @@ def knn_graph(points: torch.Tensor, n_neighbors: int = 5) -> KnnGraph:
     """Exact k-nearest-neighbour graph of ``points`` [N, 3] (``sr_knn_graph``); pass it to ``moran_loss`` to reuse the search."""
     _check_points("knn_graph", points, n_neighbors)
     lib = _lib.load()
-    pts = _f32(points)
+    pts = f32c(points)
     n, k, dev = pts.shape[0], int(n_neighbors), pts.device
     with torch.cuda.device(dev):
         work = torch.empty(lib.sr_knn_graph_workspace_bytes(n, k), dtype=torch.uint8, device=dev)
@@ -74,7 +60,7 @@ def knn_graph(points: torch.Tensor, n_neighbors: int = 5) -> KnnGraph:
         order = torch.empty(n, dtype=torch.int32, device=dev)
         rev_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
         rev_edges = torch.empty(n * k, dtype=torch.int32, device=dev)
-        _lib.check(lib.sr_knn_graph(n, k, _ptr(pts), _ptr(nn_ix), _ptr(order), _ptr(rev_start), _ptr(rev_edges), _ptr(work), _stream(dev)))
+        _lib.check(lib.sr_knn_graph(n, k, ptr(pts), ptr(nn_ix), ptr(order), ptr(rev_start), ptr(rev_edges), ptr(work), _lib.stream(dev)))
     return KnnGraph(nn_ix, order, rev_start, rev_edges)
 
 
@@ -86,9 +72,9 @@ def _run_forward(n, k, eps, pts, weight, graph, feats):
     with torch.cuda.device(dev):
         work = torch.empty(lib.sr_moran_workspace_bytes(n, len(feats)), dtype=torch.uint8, device=dev)
         out = torch.empty(1 + 2 * len(feats), dtype=torch.float32, device=dev)
-        _lib.check(lib.sr_moran_forward(n, k, eps, _ptr(pts), _ptr(weight), _ptr(graph.nn_ix) if graph else None,
-                                        _ptr(graph.order) if graph else None, len(feats), _pointer_array(feats), widths, _ptr(work),
-                                        _ptr(out), _stream(dev)))
+        _lib.check(lib.sr_moran_forward(n, k, eps, ptr(pts), ptr(weight), ptr(graph.nn_ix) if graph else None,
+                                        ptr(graph.order) if graph else None, len(feats), _pointer_array(feats), widths, ptr(work),
+                                        ptr(out), _lib.stream(dev)))
     return out
 
 
@@ -101,10 +87,10 @@ class _Moran(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, source, graph, eps, which, *features):
-        src = _f32(source)
+        src = f32c(source)
         k = graph.nn_ix.shape[1] if graph is not None else src.shape[-1]
         n = src.shape[0]
-        feats = [_f32(f).reshape(-1, f.shape[-1]) if graph is None else _f32(f).reshape(n, -1) for f in features]
+        feats = [f32c(f).reshape(-1, f.shape[-1]) if graph is None else f32c(f).reshape(n, -1) for f in features]
         pts, weight = (src, None) if graph is not None else (None, src)
         out = _run_forward(n, k, eps, pts, weight, graph, feats)
         ctx.save_for_backward(src, out, *feats)
@@ -123,7 +109,7 @@ class _Moran(torch.autograd.Function):
         lib = _lib.load()
         src, out, *feats = ctx.saved_tensors
         graph, k, n, dev = ctx.graph, ctx.k, src.shape[0], src.device
-        g = _f32(g_value).reshape(1)
+        g = f32c(g_value).reshape(1)
         want_src = ctx.needs_input_grad[0]
         want = [ctx.needs_input_grad[4 + i] for i in range(len(feats))]
         widths = (C.c_int * len(feats))(*[f.shape[1] for f in feats])
@@ -133,12 +119,11 @@ class _Moran(torch.autograd.Function):
             d_feats = [torch.empty_like(f) if w else None for f, w in zip(feats, want)]
             d_src = torch.empty_like(src) if want_src else None
             pts, weight = (src, None) if graph is not None else (None, src)
-            _lib.check(lib.sr_moran_backward(n, k, ctx.eps, _ptr(pts), _ptr(weight), _ptr(graph.nn_ix) if graph else None,
-                                             _ptr(graph.order) if graph else None, _ptr(graph.rev_start) if graph else None,
-                                             _ptr(graph.rev_edges) if graph else None, len(feats), _pointer_array(feats), widths,
-                                             _ptr(out) if ctx.which == _TOTAL else None, _ptr(g), _ptr(edges), _pointer_array(d_feats),
-                                             _ptr(d_src) if graph is not None else None, _ptr(d_src) if graph is None else None,
-                                             _stream(dev)))
+            _lib.check(lib.sr_moran_backward(n, k, ctx.eps, ptr(pts), ptr(weight), ptr(graph.nn_ix) if graph else None,
+                                             ptr(graph.order) if graph else None, ptr(graph.rev_start) if graph else None,
+                                             ptr(graph.rev_edges) if graph else None, len(feats), _pointer_array(feats), widths,
+                                             ptr(out) if ctx.which == _TOTAL else None, ptr(g), ptr(edges), _pointer_array(d_feats),
+                                             ptr(d_src) if graph is not None else None, ptr(d_src) if graph is None else None, _lib.stream(dev)))
         grads = [None if d is None else d.reshape(shape).to(dt) for d, (shape, dt) in zip([d_src] + d_feats, ctx.meta)]
         return (grads[0], None, None, None) + tuple(grads[1:])
 
@@ -148,9 +133,9 @@ def _call(source, graph, eps, which, features):
     if tracked:
         return _Moran.apply(source, graph, eps, which, *features)
     # nothing to differentiate: nothing is kept
-    src = _f32(source)
+    src = f32c(source)
     n = src.shape[0]
-    feats = [_f32(f).reshape(-1, f.shape[-1]) if graph is None else _f32(f).reshape(n, -1) for f in features]
+    feats = [f32c(f).reshape(-1, f.shape[-1]) if graph is None else f32c(f).reshape(n, -1) for f in features]
     pts, weight = (src, None) if graph is not None else (None, src)
     k = graph.nn_ix.shape[1] if graph is not None else src.shape[-1]
     out = _run_forward(n, k, eps, pts, weight, graph, feats)
@@ -191,11 +176,11 @@ class _QueryWeights(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, graph, eps):
         lib = _lib.load()
-        pts = _f32(points)
+        pts = f32c(points)
         n, k, dev = graph.nn_ix.shape[0], graph.nn_ix.shape[1], pts.device
         with torch.cuda.device(dev):
             weights = torch.empty((n, k, k), dtype=torch.float32, device=dev)
-            _lib.check(lib.sr_moran_weights(n, k, eps, _ptr(pts), _ptr(graph.nn_ix), _ptr(weights), _stream(dev)))
+            _lib.check(lib.sr_moran_weights(n, k, eps, ptr(pts), ptr(graph.nn_ix), ptr(weights), _lib.stream(dev)))
         ctx.save_for_backward(pts)
         ctx.graph, ctx.eps, ctx.meta = graph, eps, (points.shape, points.dtype)
         return weights.to(points.dtype)
@@ -206,12 +191,12 @@ class _QueryWeights(torch.autograd.Function):
         pts, = ctx.saved_tensors
         graph = ctx.graph
         n, k, dev = graph.nn_ix.shape[0], graph.nn_ix.shape[1], pts.device
-        g = _f32(g)
+        g = f32c(g)
         with torch.cuda.device(dev):
             edges = torch.empty(lib.sr_moran_edges_bytes(n, k, 0), dtype=torch.uint8, device=dev)
             d_pts = torch.empty_like(pts)
-            _lib.check(lib.sr_moran_weights_backward(n, k, ctx.eps, _ptr(pts), _ptr(graph.nn_ix), _ptr(graph.rev_start),
-                                                     _ptr(graph.rev_edges), _ptr(g), _ptr(edges), _ptr(d_pts), _stream(dev)))
+            _lib.check(lib.sr_moran_weights_backward(n, k, ctx.eps, ptr(pts), ptr(graph.nn_ix), ptr(graph.rev_start),
+                                                     ptr(graph.rev_edges), ptr(g), ptr(edges), ptr(d_pts), _lib.stream(dev)))
         shape, dt = ctx.meta
         return d_pts.reshape(shape).to(dt), None, None
 

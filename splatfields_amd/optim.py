@@ -143,8 +143,8 @@ class SplatAdam(torch.optim.Optimizer):
         lib = _lib.load()
         for dev, items in jobs.items():
             with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                mask = None if visible is None else C.c_void_p(visible.data_ptr())
+                stream = _lib.stream(dev)
+                mask = _lib.ptr(visible)
                 for first in range(0, len(items), _lib.ADAM_MAX_TENSORS):
                     part = items[first:first + _lib.ADAM_MAX_TENSORS]
                     table = (_lib.SrAdamJob * len(part))(*[_lib.SrAdamJob(*fields) for fields, _ in part])

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from ._lib import f32c
 from .triplane import TriPlaneSampler
 
 EPS = 1e-6      # every GroupNorm of the decoder (time_decoders.py: resnet_eps, conv_norm_out)
@@ -48,7 +49,7 @@ class _Run:
         if n < 1 or n > _lib.PLANE_MAX_JOBS:
             raise ValueError(f"1 .. {_lib.PLANE_MAX_JOBS} planes go through one launch, got {n}")
         self.lib, self.dev, self.n, self.groups = _lib.load(), dev, n, groups
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self.stream = _lib.stream(dev)
 
     def jobs(self, **fields):
         arr = (_lib.SrPlaneJob * self.n)()
@@ -122,17 +123,13 @@ def _no_cpu(*tensors):
         raise RuntimeError("splatfields_amd.plane_generator has no CPU path: tensors must be on a HIP ('cuda') device")
 
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 # ---- one fused layer (the unit the kernels are tested by) --------------------------------------------------------------------
 class _FusedLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, groups, prologue, upsample, silu_out, has_residual, *tensors):
         # per plane: x [cin, h, w], weight, bias, gamma, beta, residual (the last three may be absent -> None)
         _no_cpu(*[t for t in tensors if t is not None])
-        P = [[None if t is None else _f32(t) for t in tensors[i * 6:(i + 1) * 6]] for i in range(n)]
+        P = [[None if t is None else f32c(t) for t in tensors[i * 6:(i + 1) * 6]] for i in range(n)]
         col = lambda j: [p[j] for p in P]
         x, w, b = col(0), col(1), col(2)
         cout, cin = w[0].shape[:2]
@@ -151,7 +148,7 @@ class _FusedLayer(torch.autograd.Function):
         n, groups, prologue, upsample, silu_out, has_residual, cin, cout, h, wd = ctx.args
         P, norm, pre = ctx.P, ctx.norm, ctx.pre
         col = lambda j: [p[j] for p in P]
-        g = _f32(g)
+        g = f32c(g)
         run = _Run(g.device, n, groups)
         with torch.cuda.device(run.dev):
             dw, db, dres = run.weight_grad(g, col(0), cin, cout, h, wd, norm=norm, up=upsample, pre=pre, want_residual=True)
@@ -215,7 +212,7 @@ class _PlaneGenerator(torch.autograd.Function):
         _no_cpu(*tensors)
         offs, k = _offsets(ops)
         assert len(tensors) == n * k
-        P = [[_f32(t) for t in tensors[i * k:(i + 1) * k]] for i in range(n)]
+        P = [[f32c(t) for t in tensors[i * k:(i + 1) * k]] for i in range(n)]
         col = lambda j: [p[j] for p in P]
         run = _Run(P[0][0].device, n, groups)
         saved = []
@@ -264,7 +261,7 @@ class _PlaneGenerator(torch.autograd.Function):
             for i in range(n):
                 G[i][j] = batched[i]
 
-        g = _f32(g)
+        g = f32c(g)
         run = _Run(g.device, n, groups)
         with torch.cuda.device(run.dev):
             for op, o, sv in zip(reversed(ops), reversed(offs), reversed(saved)):

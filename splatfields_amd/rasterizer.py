@@ -331,13 +331,15 @@ def redeemed(render_fn, scope: bool = False):
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    """data pointer or None (ctypes takes either for a void* argument and for a pointer field of a struct)"""
+    """data pointer or None (ctypes takes either for a void* argument and for a pointer field of a struct).  Not _lib.ptr: an int,
+    which a struct field takes and a c_void_p does not"""
     return None if t is None else t.data_ptr()
 
 
 def _f32c(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     """fp32, contiguous, on `device`: the tensor itself when the kernels can read it in place (the normal case, no Python or
-    GPU work), otherwise a detached converted copy -- the camera tensors arrive strided (scene/cameras.py:68,74)."""
+    GPU work), otherwise a detached converted copy -- the camera tensors arrive strided (scene/cameras.py:68,74).  Not _lib.f32c:
+    this one also moves the tensor to `device`."""
     if t is None:
         return None
     if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
@@ -420,10 +422,6 @@ def _aligned16(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return t if (t is None or t.data_ptr() % 16 == 0) else t.clone()
 
 
-def _stream_ptr(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _check_inputs(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest, slice_hook, color_grad_sink):
     """The per-splat inputs as the kernels read them (fp32, contiguous, on means3D's device; None for an absent or empty one),
     validated: (means3D, opacities [N], scales, rotations, cov3D, shs, colors, shs_rest, sh_coeffs)."""
@@ -470,7 +468,7 @@ def _launch_forward(lib, view, splats, n: int, H: int, W: int, dev, may_async: b
     """Allocates the state buffers and launches both stages for the planned capacity, ticketed or waiting.  Returns (geom,
     binning, image, capacity, instances, pending): a ticketed launch has `pending` and no `instances` yet."""
     with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
+        stream = _lib.stream(dev)
         geom = torch.empty(lib.sr_geom_bytes(n, H, W), dtype=torch.uint8, device=dev)
         image = torch.empty(lib.sr_image_bytes(H, W), dtype=torch.uint8, device=dev)
         promise = _ESTIMATES.plan(dev.index, n, H, W, view, may_async)
@@ -583,7 +581,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             d_col = new(n, 3) if (col is not None or sink is not None) else None
             d_rest = new(*sh_rest.shape) if (sh_rest is not None and d_sh is not None) else None
         with torch.cuda.device(dev):
-            stream = _stream_ptr(dev)
+            stream = _lib.stream(dev)
             splats = _splats_struct(n, means3D, opac, sc, rot, cov, sh, col, ctx.raw_params, sh_rest)
             scratch = torch.empty(lib.sr_backward_scratch_bytes(ctx.capacity), dtype=torch.uint8, device=dev)
             grads = _lib.SrGrads(*map(_ptr, (d_means3D, d_means2D, d_opac, d_sc, d_rot, d_cov, d_sh, d_col, d_rest)))
@@ -648,7 +646,7 @@ class GaussianRasterizer(nn.Module):
             vm, pj = _f32c(rs.viewmatrix, dev), _f32c(rs.projmatrix, dev)
             present = torch.zeros(pos.shape[0], dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.sr_mark_visible(pos.shape[0], _ptr(pos), _ptr(vm), _ptr(pj), _ptr(present), _stream_ptr(dev)))
+                _lib.check(lib.sr_mark_visible(pos.shape[0], _ptr(pos), _ptr(vm), _ptr(pj), _ptr(present), _lib.stream(dev)))
         return present.bool()
 
     def _check(self, shs, colors_precomp, scales, rotations, cov3D_precomp):

@@ -7,19 +7,11 @@ Splitting the stage out is what lets the view-parallel step exchange 12-byte col
 gradients (splatfields_amd/view_parallel.py)."""
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from ._lib import ptr
 
 
 def sh_forward(means3D: torch.Tensor, shs: torch.Tensor, campos: torch.Tensor, sh_degree: int):
@@ -35,7 +27,7 @@ def sh_forward(means3D: torch.Tensor, shs: torch.Tensor, campos: torch.Tensor, s
     colors = torch.empty(n, 3, dtype=torch.float32, device=dev)
     clamped = torch.empty(n, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.sr_sh_forward(n, k, int(sh_degree), _p(m), _p(s), _p(c), _p(colors), _p(clamped), _stream(dev)))
+        _lib.check(lib.sr_sh_forward(n, k, int(sh_degree), ptr(m), ptr(s), ptr(c), ptr(colors), ptr(clamped), _lib.stream(dev)))
     return colors, clamped
 
 
@@ -60,7 +52,7 @@ def sh_forward_views(means3D: torch.Tensor, shs: torch.Tensor, campos_views: tor
         colors = torch.empty(v, n, 3, dtype=torch.float32, device=dev)
     keep = torch.empty(v, n, 3, dtype=torch.float32, device=dev) if want_keep else None
     with torch.cuda.device(dev):
-        _lib.check(lib.sr_sh_forward_views(n, k, int(sh_degree), v, _p(m), _p(s), _p(cp), _p(colors), _p(keep), _stream(dev)))
+        _lib.check(lib.sr_sh_forward_views(n, k, int(sh_degree), v, ptr(m), ptr(s), ptr(cp), ptr(colors), ptr(keep), _lib.stream(dev)))
     return colors, keep
 
 
@@ -88,8 +80,8 @@ def sh_backward(means3D, shs, campos_views, dcolors_views, sh_degree: int, *, sc
     if means_grad is not None and not (means_grad.is_contiguous() and means_grad.dtype == torch.float32):
         raise RuntimeError("means_grad must be a contiguous float32 tensor")
     with torch.cuda.device(dev):
-        _lib.check(lib.sr_sh_backward(n, k, int(sh_degree), v, _p(m), _p(s), _p(cp), _p(dc), float(scale), _p(d_shs),
-                                      _p(means_grad), int(bool(accumulate_means)), _stream(dev)))
+        _lib.check(lib.sr_sh_backward(n, k, int(sh_degree), v, ptr(m), ptr(s), ptr(cp), ptr(dc), float(scale), ptr(d_shs),
+                                      ptr(means_grad), int(bool(accumulate_means)), _lib.stream(dev)))
     return d_shs
 
 

@@ -12,17 +12,13 @@ the default `SplatFields()` constructs.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Optional
 
 import torch
 from torch import nn
 
 from . import _lib
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._lib import ptr
 
 
 class _TriPlaneLookup(torch.autograd.Function):
@@ -43,8 +39,7 @@ class _TriPlaneLookup(torch.autograd.Function):
         hwc = torch.empty(3, h, w, ch, dtype=torch.float32, device=dev)
         out = torch.empty(n, 3 * ch, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.sr_triplane_forward(n, ch, h, w, _ptr(p32), _ptr(hwc), _ptr(x32), _ptr(out),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(lib.sr_triplane_forward(n, ch, h, w, ptr(p32), ptr(hwc), ptr(x32), ptr(out), _lib.stream(dev)))
         ctx.save_for_backward(hwc, x32)
         ctx.shape = (ch, h, w)
         ctx.dtypes = (planes.dtype, pts.dtype)
@@ -63,8 +58,7 @@ class _TriPlaneLookup(torch.autograd.Function):
         d_pts = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_pts else None
         fixed = torch.empty(lib.sr_triplane_backward_workspace(n, ch, h, w), dtype=torch.uint8, device=dev) if need_planes else None
         with torch.cuda.device(dev):
-            _lib.check(lib.sr_triplane_backward(n, ch, h, w, _ptr(hwc), _ptr(x32), _ptr(g32), _ptr(d_planes), _ptr(d_pts), _ptr(fixed),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(lib.sr_triplane_backward(n, ch, h, w, ptr(hwc), ptr(x32), ptr(g32), ptr(d_planes), ptr(d_pts), ptr(fixed), _lib.stream(dev)))
         if d_planes is not None and ctx.dtypes[0] != torch.float32:
             d_planes = d_planes.to(ctx.dtypes[0])
         if d_pts is not None and ctx.dtypes[1] != torch.float32:

@@ -81,11 +81,14 @@ def entry_point_text():
 
 def test_the_loss_never_waits_for_the_device_and_has_no_float_atomics():
     from splatfields_amd.build import strip_comments
-    text = strip_comments(open(os.path.join(ROOT, "splatfields_amd", "csrc", "loss.hip")).read()) + "\n" + entry_point_text()
+    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
+    text = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("loss.hip", "reduce.h", "window11.h"))
+    text += "\n" + entry_point_text()
+    assert "block_sum" in text and "win_filter_column" in text      # the sums and the window it is built from
     assert "sr_photometric_backward" in text and "k_loss_forward" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy(", "hipMemcpyAsync", "atomicAdd",
                  "atomic"):
         assert word not in text, word
-    py = open(os.path.join(ROOT, "splatfields_amd", "losses.py")).read()
+    py = "\n".join(open(os.path.join(ROOT, "splatfields_amd", f)).read() for f in ("losses.py", "_lib.py"))   # with the shared call helpers
     for word in (".item()", ".cpu()", "synchronize", ".tolist()"):
         assert word not in py, word

@@ -86,12 +86,15 @@ def entry_point_text():
 
 def test_the_metrics_never_wait_for_the_device_and_have_no_float_atomics():
     from splatfields_amd.build import strip_comments
-    text = strip_comments(open(os.path.join(ROOT, "splatfields_amd", "csrc", "metrics.hip")).read()) + "\n" + entry_point_text()
+    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
+    text = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("metrics.hip", "reduce.h", "window11.h"))
+    text += "\n" + entry_point_text()
+    assert "block_sum" in text and "win_filter_column" in text      # the sums and the window it is built from
     assert "sr_image_metrics" in text and "k_metrics" in text and "k_metrics_reduce" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMemset", "hipMalloc",
                  "atomicAdd", "atomic"):
         assert word not in text, word
-    py = open(os.path.join(ROOT, "splatfields_amd", "metrics.py")).read()
+    py = "\n".join(open(os.path.join(ROOT, "splatfields_amd", f)).read() for f in ("metrics.py", "_lib.py"))   # with the shared call helpers
     for word in (".item()", ".cpu()", "synchronize", ".tolist()", ".numpy()"):
         assert word not in py, word
 

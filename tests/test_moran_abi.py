@@ -120,10 +120,10 @@ def entry_point_text():
 def test_nothing_waits_for_the_device_and_no_float_is_added_atomically():
     from splatfields_amd.build import strip_comments
     csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    moran = strip_comments(open(os.path.join(csrc, "moran.hip")).read())
+    moran = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("moran.hip", "reduce.h"))   # with its sums
     knn = strip_comments(open(os.path.join(csrc, "knn.hip")).read())
     entries = entry_point_text()
-    assert "sr_moran_backward" in entries and "k_moran_forward" in moran and "k_knn_search_k" in knn
+    assert "sr_moran_backward" in entries and "k_moran_forward" in moran and "block_sum" in moran and "k_knn_search_k" in knn
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy(", "hipMemcpyAsync"):
         assert word not in moran and word not in knn and word not in entries, word
     assert "atomic" not in moran and "atomic" not in entries
@@ -134,6 +134,6 @@ def test_nothing_waits_for_the_device_and_no_float_is_added_atomically():
     for target in ("count", "cursor"):       # ... and those are integers
         assert re.search(r"uint32_t\* __restrict__ %s\b" % target, knn), target
         assert not re.search(r"float\* (__restrict__ )?%s\b" % target, knn), target
-    py = open(os.path.join(ROOT, "splatfields_amd", "moran.py")).read()
+    py = "\n".join(open(os.path.join(ROOT, "splatfields_amd", f)).read() for f in ("moran.py", "_lib.py"))   # with the shared call helpers
     for word in (".item()", ".cpu()", "synchronize", ".tolist()"):
         assert word not in py, word

@@ -99,7 +99,7 @@ def test_bad_calls_are_refused_on_the_host_and_empty_ones_launch_nothing(lib):
 def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
     from splatfields_amd.build import strip_comments
     csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    code = strip_comments(open(os.path.join(csrc, "objective.hip")).read())
+    code = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("objective.hip", "reduce.h"))   # with its sums
     api = open(os.path.join(csrc, "api.hip")).read()
     entries = []
     for name in NEW:
@@ -107,13 +107,13 @@ def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
         assert m, name
         entries.append(m.group(0))
     entries = "\n".join(entries)
-    assert "k_splat_reg_backward" in code and "k_depth_l1_backward" in code and "launch_depth_l1_backward" in entries
+    assert "k_splat_reg_backward" in code and "block_sum" in code and "k_depth_l1_backward" in code and "launch_depth_l1_backward" in entries
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMalloc", "atomic"):
         assert word not in code and word not in entries, word
     for word in ("rsqrt", "__frsqrt", "__fdividef", "__fsqrt_r"):      # IEEE sqrt and division only
         assert word not in code, word
     for flag in ("-ffast-math", "-fapprox-func", "-freciprocal-math"):
         assert flag not in open(os.path.join(ROOT, "splatfields_amd", "build.py")).read(), flag
-    py = open(os.path.join(ROOT, "splatfields_amd", "losses.py")).read()
+    py = "\n".join(open(os.path.join(ROOT, "splatfields_amd", f)).read() for f in ("losses.py", "_lib.py"))   # with the shared call helpers
     for word in (".item()", ".cpu()", "synchronize", ".tolist()"):
         assert word not in py, word
