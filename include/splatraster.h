@@ -48,6 +48,11 @@
  *   sr_groupnorm_stats, sr_conv3x3_forward / _backward_data / _weight_grad, sr_groupnorm_silu_backward
  *        <- reference scene/time_decoders.py (`TimeVAEDecoder`) behind scene/tripFields.py:176-204 (`Tensorial2D`): the plane
  *           generator's GroupNorm -> SiLU -> [nearest x2] -> conv 3x3 -> [+ residual] layers, all planes per launch.
+ *   sr_hull_carve + sr_hull_gather
+ *        <- the visual hull every shipped recipe starts from (`--pts_samples hull` / `load`), reference
+ *           scene/dataset_readers.py:1385-1417 (`visual_hull_samples`), :1419-1458 (`visual_hull_samples_list`), :605-644 (the
+ *           Blender `hull` branch of `readNerfSyntheticInfo`) and :544-588 (its `load` branch, a point cloud filtered by the same
+ *           test): the host's projection of a G^3 grid into every training view, as one streaming pass plus an ordered compaction.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -690,6 +695,55 @@ int sr_groupnorm_silu_backward(int n_planes, const SrPlaneJob* jobs, int channel
 size_t sr_conv3x3_weight_grad_workspace(int n_planes, int cin, int cout, int h_in, int w_in, int flags);
 int sr_conv3x3_weight_grad(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags,
                            void* workspace, void* hip_stream);
+
+/* Visual-hull initialisation (reference scene/dataset_readers.py:1385-1417, :1419-1458, :605-644, :544-588): which voxels of a
+ * G^3 grid -- or which points of a list -- fall, in every view, on a pixel of that view's mask.
+ *
+ * Per view (SrHullView), all in double, in this order of operations, without fused multiply-adds:
+ *   h = m [x y z 1]^T (m: 3x4, row-major; each row summed left to right),  u = h0 / h2,  v = h1 / h2   (no test on the sign of h2)
+ *   SR_HULL_KRT   un = 2 (u / (W - 1)) - 1,  px = ((un + 1) / 2) (W - 1)   -- grid_sample's round trip with align_corners=True;
+ *                 the same for y with H; m is the reference's KRT (:1389)
+ *   SR_HULL_NDC   un = u,  px = ((u + 1) W - 1) 0.5 (`ndc2Pix` :515),  py likewise with H; m holds columns 0, 1, 2 of the
+ *                 reference's transposed full_proj_transform as rows, so h2 is clip z, not w (:625).  The reference swaps H and W
+ *                 in both the scale and the bounds test: this equals it for square images, the only ones it is defined for
+ *   the nearest pixel is (rint(px), rint(py)), halves to even; the view keeps the item iff that pixel is inside the image and its
+ *   mask byte is non-zero.  SR_HULL_OUTSIDE_CARVE: an item outside the image is carved.  SR_HULL_OUTSIDE_KEEP (:1443,1450): an
+ *   item with un or vn outside [-1, 1] is kept by this view.  A non-finite px or py is carved under both.
+ * An item survives iff every view keeps it.
+ *
+ * Items: with `grid` (device, double [3][G]: the coordinate tables of x, y, z, made on the host -- np.linspace -- and uploaded)
+ * item i = (iy G + ix) G + iz is the voxel (grid[0][ix], grid[1][iy], grid[2][iz]), the order of np.meshgrid(g, g, g) flattened;
+ * with `points` (device, [n_points, 3] float32, or float64 with point_is_double) item i is row i.  Exactly one of the two.
+ * `masks`: device, one flat byte buffer of `mask_bytes` bytes (non-zero = inside the silhouette); view k's H x W image starts at
+ * its mask_offset, so ragged sizes are fine.  `views`: HOST array of n_views records; it is checked on the host and copied into
+ * the workspace through the stream.
+ *
+ * sr_hull_carve: 2 launches (one lane per item, then one workgroup that orders the workgroup counts); writes the number of
+ * survivors to `count_out` (device, int32) and one survivor bit per item into the workspace.  Nothing waits for the device.
+ * sr_hull_gather (same items, same workspace, after sr_hull_carve): 1 launch; writes the first `capacity` survivors in item
+ * order: indices_out [capacity] int32 (item index) and points_out [capacity, 3] float32 (the coordinates rounded from double);
+ * either may be NULL.  A capacity below the count gives an ordered prefix.  No atomics: the same inputs give the same bytes.
+ * `workspace`: sr_hull_workspace_bytes(items) bytes, items = G^3 or n_points.
+ * Refused on the host, before any launch: n_views outside 1 .. SR_HULL_MAX_VIEWS, G < 1, G^3 or n_points > 2^31 - 1, both or
+ * neither of grid and points, H or W < 1, H or W == 1 under SR_HULL_KRT (the normalisation divides by W - 1), an unknown
+ * convention or policy, a mask that does not fit into mask_bytes.  n_points = 0 is valid (count 0). */
+#define SR_HULL_KRT 0
+#define SR_HULL_NDC 1
+#define SR_HULL_OUTSIDE_CARVE 0
+#define SR_HULL_OUTSIDE_KEEP 1
+#define SR_HULL_MAX_VIEWS 1024
+typedef struct SrHullView {
+    double m[12];              /* 3x4 projection, row-major */
+    long long mask_offset;     /* first byte of this view's mask in `masks` */
+    int height, width;
+    int convention;            /* SR_HULL_KRT / SR_HULL_NDC */
+    int outside;               /* SR_HULL_OUTSIDE_CARVE / SR_HULL_OUTSIDE_KEEP */
+} SrHullView;
+size_t sr_hull_workspace_bytes(long long n_items);
+int sr_hull_carve(int n_views, const SrHullView* views, const unsigned char* masks, long long mask_bytes, const double* grid, int G,
+                  const void* points, long long n_points, int point_is_double, void* workspace, int* count_out, void* hip_stream);
+int sr_hull_gather(const double* grid, int G, const void* points, long long n_points, int point_is_double, const void* workspace,
+                   long long capacity, int* indices_out, float* points_out, void* hip_stream);
 
 /* Diagnostics for the parity tests: byte offsets of four arrays inside the opaque buffers of a view with these sizes
  * (`instances` = the capacity the binning buffer was carved for):

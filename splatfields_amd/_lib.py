@@ -72,6 +72,12 @@ class SrPlaneJob(C.Structure):
         "d_residual", "add", "dx_out")]
 
 
+class SrHullView(C.Structure):
+    _fields_ = [("m", C.c_double * 12), ("mask_offset", C.c_longlong), ("height", C.c_int), ("width", C.c_int),
+                ("convention", C.c_int), ("outside", C.c_int)]
+
+
+HULL_KRT, HULL_NDC, HULL_OUTSIDE_CARVE, HULL_OUTSIDE_KEEP, HULL_MAX_VIEWS = 0, 1, 0, 1, 1024   # include/splatraster.h: SR_HULL_*
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 PLANE_MAX_JOBS = 8                                           # include/splatraster.h: SR_PLANE_MAX_JOBS
 CONV_PROLOGUE, CONV_UPSAMPLE, CONV_RESIDUAL, CONV_SILU_OUT = 1, 2, 4, 8   # include/splatraster.h: SR_CONV_*
@@ -154,6 +160,11 @@ SYMBOLS = {
                                   C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "sr_densify_gather": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "sr_hull_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "sr_hull_carve": (C.c_int, [C.c_int, C.POINTER(SrHullView), C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
+                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_hull_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
     "sr_mlp_pack": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
     "sr_mlp_weight_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob)]),
     "sr_mlp_weight_grad": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob), C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1,0 +1,191 @@
+// Visual-hull initialisation on the device (the one piece of the dataset readers that is arithmetic).
+//
+// Restates the hull test of reference scene/dataset_readers.py: :1385-1417 (`visual_hull_samples`), :1419-1458
+// (`visual_hull_samples_list`), :605-644 (the Blender `hull` branch of `readNerfSyntheticInfo`) and :544-588 (its `load`
+// branch).  The reference projects a G^3 grid into every training view on the host (a [V, G^3, 4] float64 temporary for
+// the first two, a per-camera loop over a float32 [G^3, 4] matrix for the Blender branches) and keeps the voxels whose nearest
+// pixel lies in the mask of every view.  Here:
+//
+//   carve    one lane per voxel (or per explicit point): the lane walks the V views and leaves the loop once it is carved;
+//            the wavefront's survivors become one 64-bit word (__ballot), the workgroup's count one uint32;
+//   scan     one workgroup turns the workgroup counts into exclusive offsets, in index order, and writes the total;
+//   gather   every survivor's rank = its workgroup's offset + the bits in front of it: indices and float32 coordinates are
+//            written in grid order, up to a caller-supplied capacity.
+//
+// No atomics anywhere: the same inputs give the same bytes from call to call.
+//
+// Arithmetic: double throughout, in the reference's order of operations, with floating-point contraction switched off in the
+// functions below (a fused multiply-add rounds once where numpy rounds twice).  The result then equals a float64 evaluation on
+// the host except for voxels whose pixel coordinate lies within ~1e-13 px of a rounding boundary (k + 1/2), where the order of
+// the four-term dot product inside the host's BLAS can decide.  About 20 fp64 operations per voxel and view: the pass is
+// bound by its byte gathers, not by the fp64 rate.
+#include "kernels.h"
+
+namespace sr {
+
+namespace {
+
+// does view `w` keep the point (x, y, z)?
+__device__ __forceinline__ bool hull_view_keeps(const SrHullView& w, const uint8_t* __restrict__ masks, double x, double y, double z) {
+#pragma clang fp contract(off)
+    const double h0 = w.m[0] * x + w.m[1] * y + w.m[2] * z + w.m[3];
+    const double h1 = w.m[4] * x + w.m[5] * y + w.m[6] * z + w.m[7];
+    const double h2 = w.m[8] * x + w.m[9] * y + w.m[10] * z + w.m[11];
+    const double u = h0 / h2, v = h1 / h2;            // no sign test on h2: the reference has none
+    const double Wd = (double)w.width, Hd = (double)w.height;
+    double px, py, un, vn;
+    if (w.convention == SR_HULL_KRT) {
+        // the reference normalises for grid_sample, which un-normalises again (align_corners=True): the round trip is kept
+        un = 2.0 * (u / (Wd - 1.0)) - 1.0;
+        vn = 2.0 * (v / (Hd - 1.0)) - 1.0;
+        px = ((un + 1.0) / 2.0) * (Wd - 1.0);
+        py = ((vn + 1.0) / 2.0) * (Hd - 1.0);
+    } else {
+        un = u; vn = v;                                // already normalised device coordinates
+        px = ((u + 1.0) * Wd - 1.0) * 0.5;             // ndc2Pix
+        py = ((v + 1.0) * Hd - 1.0) * 0.5;
+    }
+    // non-finite: carved under both policies (NaN fails every comparison below anyway; infinities are named here)
+    if (!(fabs(px) <= 1.7976931348623157e308) || !(fabs(py) <= 1.7976931348623157e308)) return false;
+    if (w.outside == SR_HULL_OUTSIDE_KEEP && (un < -1.0 || un > 1.0 || vn < -1.0 || vn > 1.0)) return true;
+    const double rx = rint(px), ry = rint(py);         // nearest pixel, halves to even
+    if (!(rx >= 0.0 && rx <= Wd - 1.0 && ry >= 0.0 && ry <= Hd - 1.0)) return false;
+    const long long at = w.mask_offset + (long long)ry * (long long)w.width + (long long)rx;
+    return masks[at] != 0;
+}
+
+// item -> its position: the voxel with linear index i = (iy G + ix) G + iz sits at (gx[ix], gy[iy], gz[iz]) -- the order of
+// np.meshgrid(g, g, g) (default indexing) flattened --, or row i of the point list widened to double
+struct HullItems {
+    const double* grid;      // [3][G] (x, y, z tables) or NULL
+    int G;
+    const void* points;      // [n, 3] float32 / float64 or NULL
+    int point_is_double;
+    long long n;
+};
+
+__device__ __forceinline__ void hull_position(const HullItems& it, long long i, double& x, double& y, double& z) {
+    if (it.grid) {
+        const long long G = it.G;
+        const int iz = (int)(i % G), ix = (int)((i / G) % G), iy = (int)(i / (G * G));
+        x = it.grid[ix]; y = it.grid[G + iy]; z = it.grid[2 * G + iz];
+    } else if (it.point_is_double) {
+        const double* p = static_cast<const double*>(it.points) + 3 * i;
+        x = p[0]; y = p[1]; z = p[2];
+    } else {
+        const float* p = static_cast<const float*>(it.points) + 3 * i;
+        x = (double)p[0]; y = (double)p[1]; z = (double)p[2];
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_hull_carve(const HullItems it, int n_views, const SrHullView* __restrict__ views,
+                                                       const uint8_t* __restrict__ masks, unsigned long long* __restrict__ words,
+                                                       uint32_t* __restrict__ block_counts) {
+    __shared__ uint32_t s_count[kBlock / kWave];
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    bool alive = i < it.n;
+    if (alive) {
+        double x, y, z;
+        hull_position(it, i, x, y, z);
+        for (int v = 0; v < n_views && alive; ++v) alive = hull_view_keeps(views[v], masks, x, y, z);   // views[v]: the same record for every lane
+    }
+    const unsigned long long word = __ballot(alive);     // every lane of the workgroup arrives here: lanes past n vote 0
+    if (lane_id() == 0) {
+        words[i / kWave] = word;                          // = 4 blockIdx + wave: the word array holds whole workgroups (carve_hull),
+        s_count[wave_id()] = (uint32_t)__popcll(word);    // so the waves of the last one that start past n have their slot too
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_count[0] + s_count[1] + s_count[2] + s_count[3];
+}
+
+// exclusive prefix over the workgroup counts, in index order, in place; the total goes to `total` (workspace) and `count_out`
+__global__ void __launch_bounds__(1024) k_hull_scan(long long blocks, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ total,
+                                                    int* __restrict__ count_out) {
+    __shared__ uint32_t s_wave[1024 / kWave];
+    uint32_t carry = 0u;                                  // the same value in every thread
+    for (long long base = 0; base < blocks; base += 1024) {
+        const long long j = base + threadIdx.x;
+        const uint32_t v = j < blocks ? block_counts[j] : 0u;
+        const uint32_t inc = wave_inclusive_scan(v);
+        __syncthreads();                                  // s_wave of the previous round has been read
+        if (lane_id() == 63) s_wave[wave_id()] = inc;
+        __syncthreads();
+        uint32_t before = 0u, all = 0u;
+#pragma unroll
+        for (int w = 0; w < 1024 / kWave; ++w) {
+            const uint32_t s = s_wave[w];
+            if (w < wave_id()) before += s;
+            all += s;
+        }
+        if (j < blocks) block_counts[j] = carry + before + inc - v;
+        carry += all;
+    }
+    if (threadIdx.x == 0) { *total = carry; if (count_out) *count_out = (int)carry; }
+}
+
+__global__ void __launch_bounds__(kBlock) k_hull_gather(const HullItems it, const unsigned long long* __restrict__ words,
+                                                        const uint32_t* __restrict__ block_offsets, long long capacity,
+                                                        int* __restrict__ indices_out, float* __restrict__ points_out) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= it.n) return;
+    const long long w0 = (long long)blockIdx.x * (kBlock / kWave);
+    const int w = wave_id(), lane = lane_id();
+    const unsigned long long word = words[w0 + w];
+    if (!((word >> lane) & 1ull)) return;
+    long long rank = block_offsets[blockIdx.x];
+    for (int k = 0; k < w; ++k) rank += __popcll(words[w0 + k]);
+    rank += __popcll(word & ((1ull << lane) - 1ull));
+    if (rank >= capacity) return;                        // an ordered prefix when the caller's buffers are short
+    if (indices_out) indices_out[rank] = (int)i;
+    if (points_out) {
+        double x, y, z;
+        hull_position(it, i, x, y, z);
+        points_out[3 * rank + 0] = (float)x; points_out[3 * rank + 1] = (float)y; points_out[3 * rank + 2] = (float)z;
+    }
+}
+
+struct HullCarve { SrHullView* views; unsigned long long* words; uint32_t* counts; uint32_t* total; };
+
+// view table [kHullMaxViews] | survivor words [4 per workgroup] | workgroup counts / offsets | total
+size_t carve_hull(void* base, long long n, HullCarve* out) {
+    Carver c{static_cast<char*>(base), 0};
+    const size_t blocks = (size_t)(((n > 0 ? n : 1) + kBlock - 1) / kBlock);
+    HullCarve t;
+    t.views = c.take<SrHullView>(SR_HULL_MAX_VIEWS);
+    t.words = c.take<unsigned long long>(blocks * (kBlock / kWave));
+    t.counts = c.take<uint32_t>(blocks);
+    t.total = c.take<uint32_t>(1);
+    if (out) *out = t;
+    return align_up(c.off, 256);
+}
+
+}  // namespace
+
+size_t hull_workspace_bytes(long long n) { return carve_hull(nullptr, n, nullptr); }
+
+hipError_t launch_hull_carve(int n_views, const SrHullView* host_views, const uint8_t* masks, const double* grid, int G, const void* points,
+                             long long n, int point_is_double, void* workspace, int* count_out, hipStream_t st) {
+    HullCarve c;
+    carve_hull(workspace, n, &c);
+    // the table travels through the stream in front of the kernel that reads it (pageable source: staged before the call returns)
+    const hipError_t e = hipMemcpyAsync(c.views, host_views, sizeof(SrHullView) * (size_t)n_views, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    const HullItems it{grid, G, points, point_is_double, n};
+    const long long blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 0)
+        hipLaunchKernelGGL(k_hull_carve, dim3((unsigned)blocks), dim3(kBlock), 0, st, it, n_views, c.views, masks, c.words, c.counts);
+    hipLaunchKernelGGL(k_hull_scan, dim3(1), dim3(1024), 0, st, blocks, c.counts, c.total, count_out);
+    return hipSuccess;
+}
+
+void launch_hull_gather(const double* grid, int G, const void* points, long long n, int point_is_double, const void* workspace,
+                        long long capacity, int* indices_out, float* points_out, hipStream_t st) {
+    HullCarve c;
+    carve_hull(const_cast<void*>(workspace), n, &c);
+    const HullItems it{grid, G, points, point_is_double, n};
+    const long long blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 0 && capacity > 0)
+        hipLaunchKernelGGL(k_hull_gather, dim3((unsigned)blocks), dim3(kBlock), 0, st, it, c.words, c.counts, capacity, indices_out, points_out);
+}
+
+}  // namespace sr

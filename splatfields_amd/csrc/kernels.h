@@ -54,6 +54,13 @@ void launch_densify_plan(int n, const float* log_scales, int scale_cols, const f
 void launch_densify_gather(int n, int row, const float* src, float* dst, const int32_t* dest, int mode, const float* log_scales,
                            int scale_cols, const float* rotations, const float* unit, hipStream_t st);
 
+// hull.hip: arguments are checked by the caller (sr_hull_*); exactly one of grid / points, n = G^3 or the number of points
+size_t hull_workspace_bytes(long long n);
+hipError_t launch_hull_carve(int n_views, const SrHullView* host_views, const uint8_t* masks, const double* grid, int G, const void* points,
+                             long long n, int point_is_double, void* workspace, int* count_out, hipStream_t st);
+void launch_hull_gather(const double* grid, int G, const void* points, long long n, int point_is_double, const void* workspace,
+                        long long capacity, int* indices_out, float* points_out, hipStream_t st);
+
 // mlp.hip
 size_t mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs);
 int launch_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, void* workspace, size_t workspace_bytes, hipStream_t st);
