@@ -696,6 +696,68 @@ size_t sr_conv3x3_weight_grad_workspace(int n_planes, int cin, int cout, int h_i
 int sr_conv3x3_weight_grad(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags,
                            void* workspace, void* hip_stream);
 
+/* The attention layer of the generator's mid block (the `Attention` inside `TimeDecoder.mid_block`, scene/time_decoders.py), for
+ * every plane of the encoder in the same launches.  Per plane, with T = height * width tokens of width `channels`:
+ *   t = gamma GroupNorm(x) + beta  (no SiLU),   q, k, v = t W^T + b,   P = softmax(q k^T / sqrt(channels))  (one head),
+ *   out = x + (P v) Wo^T + bo.
+ * Tensors are fp32 and contiguous, activations [channels, height, width], weights [out, in] as nn.Linear holds them.  Every
+ * product and sum is a double (the group statistics included: two passes over the group); the softmax subtracts the row
+ * maximum; each result is rounded to fp32 once, on store.  No floating-point atomics: the parameter gradients are sums over
+ * tokens that go through per-chunk partials in the workspace and are added in an order the shape alone fixes, so repeated calls
+ * are bit-identical.  Nothing waits on the host.  sr_profile_collect counts the forward's launches under stage 0 and the
+ * backward's under stage 6.
+ *
+ * channels: a multiple of 8 in 8..64; groups divides channels; 1 <= height * width <= 4096; channels / groups * height * width
+ * >= 2 (a group of one value has no variance); 1 <= n_planes <= SR_PLANE_MAX_JOBS.  Anything else returns nonzero before any
+ * launch, and the size queries return 0.
+ *
+ * `saved` is the caller's buffer that carries the forward's intermediates (the statistics, q, k, v, P v and the rows'
+ * log-sum-exp, as doubles) to the backward: sr_attention_saved_bytes is the size for the whole call, plane i's part is the
+ * i-th of n_planes equal pieces (8-byte aligned), or any buffer of that piece's size. */
+typedef struct SrAttentionJob {
+    const float* x;      /* [channels, h, w] layer input                                                                          */
+    const float* gamma;  /* [channels] GroupNorm weight                                                                           */
+    const float* beta;   /* [channels] GroupNorm bias                                                                             */
+    float* stats;        /* [groups, 4], written by the forward in sr_groupnorm_stats' format (mean, rstd, mean_lo, 0)            */
+    const float* wq;     /* [channels, channels] to_q.weight                                                                      */
+    const float* bq;     /* [channels]                                                                                            */
+    const float* wk;     /* to_k                                                                                                  */
+    const float* bk;
+    const float* wv;     /* to_v                                                                                                  */
+    const float* bv;
+    const float* wo;     /* to_out.0                                                                                              */
+    const float* bo;
+    float* out;          /* [channels, h, w]                                                                                      */
+    void* saved;         /* this plane's piece of the saved buffer: written by the forward, read by the backward                  */
+    const float* dy;     /* [channels, h, w] gradient at `out`                                                                    */
+    float* dx;           /* [channels, h, w] gradient at x, the residual branch included                                          */
+    float* dgamma;       /* [channels]                                                                                            */
+    float* dbeta;        /* [channels]                                                                                            */
+    float* dwq;          /* [channels, channels]                                                                                  */
+    float* dbq;          /* [channels]                                                                                            */
+    float* dwk;
+    float* dbk;          /* written as zeros: a key bias shifts every score of a row alike, and the softmax does not see it      */
+    float* dwv;
+    float* dbv;
+    float* dwo;
+    float* dbo;
+} SrAttentionJob;
+
+size_t sr_attention_saved_bytes(int n_planes, int channels, int groups, int height, int width);          /* 0: unsupported */
+size_t sr_attention_backward_workspace(int n_planes, int channels, int groups, int height, int width);   /* 0: unsupported */
+
+/* Three launches: the group statistics, the three projections, the streaming softmax with the output projection and the
+ * residual.  No workspace.  Fields: x, gamma, beta, stats, wq .. bo, out, saved. */
+int sr_attention_forward(int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width, float eps,
+                         void* hip_stream);
+
+/* Every gradient of the layer the forward ran on the same fields and `saved`.  Six launches: dO and D per token with the
+ * partials of dwo / dbo; dq per block of query rows; dk and dv per block of key rows; the gradient at t with the partials of
+ * the other parameter gradients; the partials' fixed-order sums; dx.  The workspace is 8-byte aligned.
+ * Fields: x, gamma, beta, wq, wk, wv, wo, saved, dy, dx and the ten parameter gradients. */
+int sr_attention_backward(int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width, float eps,
+                          void* workspace, void* hip_stream);
+
 /* Visual-hull initialisation (reference scene/dataset_readers.py:1385-1417, :1419-1458, :605-644, :544-588): which voxels of a
  * G^3 grid -- or which points of a list -- fall, in every view, on a pixel of that view's mask.
  *

@@ -9,4 +9,4 @@ from .optim import SplatAdam  # noqa: F401
 from .fused_mlp import mlp_precision, set_mlp_precision  # noqa: F401
 from .init import (hull_filter, hull_matrices, splats_from_points, visual_hull, visual_hull_samples,  # noqa: F401
                    visual_hull_samples_list)
-from .plane_generator import Tensorial2D, TimeVAEDecoder, VarTriPlaneEncoder, fused_layer, generate_planes  # noqa: F401
+from .plane_generator import Tensorial2D, TimeVAEDecoder, VarTriPlaneEncoder, fused_attention, fused_layer, generate_planes, set_attention  # noqa: F401

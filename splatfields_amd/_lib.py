@@ -72,6 +72,12 @@ class SrPlaneJob(C.Structure):
         "d_residual", "add", "dx_out")]
 
 
+class SrAttentionJob(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in (
+        "x", "gamma", "beta", "stats", "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "out", "saved", "dy", "dx", "dgamma", "dbeta",
+        "dwq", "dbq", "dwk", "dbk", "dwv", "dbv", "dwo", "dbo")]
+
+
 class SrHullView(C.Structure):
     _fields_ = [("m", C.c_double * 12), ("mask_offset", C.c_longlong), ("height", C.c_int), ("width", C.c_int),
                 ("convention", C.c_int), ("outside", C.c_int)]
@@ -191,6 +197,11 @@ SYMBOLS = {
     "sr_conv3x3_weight_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sr_conv3x3_weight_grad": (C.c_int, [C.c_int, C.POINTER(SrPlaneJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p]),
+    "sr_attention_saved_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sr_attention_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sr_attention_forward": (C.c_int, [C.c_int, C.POINTER(SrAttentionJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "sr_attention_backward": (C.c_int, [C.c_int, C.POINTER(SrAttentionJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                        C.c_void_p]),
     "sr_debug_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_size_t)]),
     "sr_debug_backward_stats": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "sr_profile_enable": (C.c_int, [C.c_int]),

@@ -159,6 +159,17 @@ size_t gn_silu_backward_workspace(int n_planes, int channels, int h, int w);
 void launch_gn_silu_backward_partial(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, void* ws, hipStream_t st);
 void launch_gn_silu_backward_apply(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, const void* ws, hipStream_t st);
 
+// attention.hip: shapes are checked by the caller (attention_shape_error: null = supported); every launch_* is one kernel launch
+constexpr int kAttentionBackwardSteps = 6;     // launch_attention_backward(step = 0 .. 5), in this order
+const char* attention_shape_error(int channels, int groups, int h, int w);
+size_t attention_saved_bytes(int n_planes, int channels, int groups, int h, int w);
+size_t attention_backward_workspace(int n_planes, int channels, int h, int w);
+void launch_attention_stats(int n, const SrAttentionJob* jobs, int channels, int groups, int h, int w, float eps, hipStream_t st);
+void launch_attention_qkv(int n, const SrAttentionJob* jobs, int channels, int groups, int h, int w, float eps, hipStream_t st);
+void launch_attention_softmax(int n, const SrAttentionJob* jobs, int channels, int groups, int h, int w, float eps, hipStream_t st);
+void launch_attention_backward(int step, int n, const SrAttentionJob* jobs, int channels, int groups, int h, int w, float eps, void* ws,
+                               hipStream_t st);
+
 // sh.hip
 void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
                        unsigned char* clamped, hipStream_t st);

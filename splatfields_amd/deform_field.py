@@ -117,9 +117,9 @@ class SplatFields(nn.Module):
             # reference does it (utils/time_utils.py:316-328)
             from .plane_generator import VarTriPlaneEncoder
             ea = kwargs["encoder_args"]
-            unknown = sorted(k for k in ea if k not in ("generator", "in_ch", "out_ch", "noise_res", "fuse_mode"))
+            unknown = sorted(k for k in ea if k not in ("generator", "in_ch", "out_ch", "noise_res", "fuse_mode", "attention"))
             if unknown:
-                raise ValueError("SplatFields: encoder_args %s are not arguments of the plane generator (in_ch, out_ch, noise_res, fuse_mode)" % unknown)
+                raise ValueError("SplatFields: encoder_args %s are not arguments of the plane generator (in_ch, out_ch, noise_res, fuse_mode, attention)" % unknown)
             encoder = VarTriPlaneEncoder({**{k: v for k, v in ea.items() if k != "generator"},
                                           "layer_kwargs": {"n_frames": n_frames, "strategy": kwargs.get("layer_strategy", "none")}})
         if encoder is None and self.encoder_type in ["VarTriPlaneEncoder"]:

@@ -9,15 +9,19 @@ has the same classes with the reference's constructor keywords and exactly its p
 
 Every 3 x 3 convolution with the GroupNorm + SiLU in front of it, the upsample and the residual add behind it is ONE kernel
 launch for ALL planes (a job table with one row per plane); one `torch.autograd.Function` spans the whole generator, saves the
-layer inputs and the GroupNorm statistics and recomputes the activations in the backward.  What stays torch ops: the mid
-block's attention (400 tokens x 32 channels, the planes batched through `torch.bmm`) and the `weight + frame_weights[frame_id]`
-of `layer_strategy='per_frame'` (indexed on the device).  Blocks that change width (a 1 x 1 `conv_shortcut`) do not occur in the
+layer inputs and the GroupNorm statistics and recomputes the activations in the backward.  The mid block's attention (400
+tokens x 32 channels) has two paths: "torch" (the default: float64 torch ops, the planes batched through `torch.bmm`, the
+backward a second evaluation under autograd) and "fused" (opt-in: csrc/attention.hip, 3 launches forward and 6 backward for all
+planes, double arithmetic inside the kernels, float32 tensors only); `set_attention`, SPLATFIELDS_PLANE_ATTENTION or the
+`attention=` keyword of the modules select it.  What stays torch ops with "fused": the `weight + frame_weights[frame_id]` of
+`layer_strategy='per_frame'` (indexed on the device).  Blocks that change width (a 1 x 1 `conv_shortcut`) do not occur in the
 reference's configuration and are not built.  There is no CPU path.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -30,6 +34,37 @@ from .triplane import TriPlaneSampler
 
 EPS = 1e-6      # every GroupNorm of the decoder (time_decoders.py: resnet_eps, conv_norm_out)
 _N_TENSORS = {"conv": 2, "res": 8, "attn": 10, "up": 2, "out": 4}
+
+ATTENTIONS = ("torch", "fused")
+ATTENTION_LAUNCHES = (3, 6)     # library launches of the "fused" attention layer: (forward, backward), whatever the number of planes
+
+
+def _checked_attention(name) -> str:
+    if name not in ATTENTIONS:
+        raise ValueError(f"unknown plane-generator attention {name!r}: expected one of {ATTENTIONS}")
+    return name
+
+
+# process default of the mid block's attention layer, read once: SPLATFIELDS_PLANE_ATTENTION=fused turns the HIP kernels on for
+# every generator that does not name a path itself
+_ATTENTION = _checked_attention(os.environ.get("SPLATFIELDS_PLANE_ATTENTION") or "torch")
+
+
+def set_attention(name: str) -> str:
+    """Process default of the generator's attention layer: "torch" (float64 torch ops) or "fused" (csrc/attention.hip).
+    Returns the previous setting."""
+    global _ATTENTION
+    prev, _ATTENTION = _ATTENTION, _checked_attention(name)
+    return prev
+
+
+def attention() -> str:
+    return _ATTENTION
+
+
+def resolve_attention(name: Optional[str]) -> str:
+    """`None` -> the process default, at call time."""
+    return _ATTENTION if name is None else _checked_attention(name)
 
 
 # ---- the kernels behind one entry each -----------------------------------------------------------------------------------------
@@ -53,6 +88,13 @@ class _Run:
 
     def jobs(self, **fields):
         arr = (_lib.SrPlaneJob * self.n)()
+        for i in range(self.n):
+            for name, v in fields.items():
+                setattr(arr[i], name, _addr(v, i))
+        return arr
+
+    def attention_jobs(self, **fields):
+        arr = (_lib.SrAttentionJob * self.n)()
         for i in range(self.n):
             for name, v in fields.items():
                 setattr(arr[i], name, _addr(v, i))
@@ -118,6 +160,30 @@ class _Run:
         return (dw, db, dres) if want_residual else (dw, db)
 
 
+    def attention_forward(self, x, p, channels, h, wd):
+        """x [channels, h, wd] per plane, p = ten lists of per-plane tensors (group_norm w, b, q w, b, k w, b, v w, b, out w, b)
+        -> out [n, channels, h, wd] and the buffer that carries the intermediates to `attention_backward`"""
+        size = self.lib.sr_attention_saved_bytes(self.n, channels, self.groups, h, wd)
+        saved = self.bytes(size).view(self.n, size // self.n if size else 1)
+        out, stats = self.new(channels, h, wd), self.new(self.groups, 4)
+        self.call(self.lib.sr_attention_forward, self.n,
+                  self.attention_jobs(x=x, gamma=p[0], beta=p[1], stats=stats, wq=p[2], bq=p[3], wk=p[4], bk=p[5], wv=p[6], bv=p[7], wo=p[8],
+                                      bo=p[9], out=out, saved=saved), channels, self.groups, h, wd, EPS, self.stream)
+        return out, saved
+
+    def attention_backward(self, dy, x, p, saved, channels, h, wd):
+        """-> dx [n, channels, h, wd] and the ten parameter gradients [n, ...] in the order of `p`"""
+        dx = self.new(channels, h, wd)
+        mat, vec = (lambda: self.new(channels, channels)), (lambda: self.new(channels))
+        dg, dbe, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo = vec(), vec(), mat(), vec(), mat(), vec(), mat(), vec(), mat(), vec()
+        ws = self.bytes(self.lib.sr_attention_backward_workspace(self.n, channels, self.groups, h, wd))
+        self.call(self.lib.sr_attention_backward, self.n,
+                  self.attention_jobs(x=x, gamma=p[0], beta=p[1], wq=p[2], wk=p[4], wv=p[6], wo=p[8], saved=saved, dy=dy, dx=dx, dgamma=dg,
+                                      dbeta=dbe, dwq=dwq, dbq=dbq, dwk=dwk, dbk=dbk, dwv=dwv, dbv=dbv, dwo=dwo, dbo=dbo),
+                  channels, self.groups, h, wd, EPS, C.c_void_p(ws.data_ptr()), self.stream)
+        return dx, (dg, dbe, dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo)
+
+
 def _no_cpu(*tensors):
     if not all(t.is_cuda for t in tensors):
         raise RuntimeError("splatfields_amd.plane_generator has no CPU path: tensors must be on a HIP ('cuda') device")
@@ -180,6 +246,51 @@ def fused_layer(x: Sequence[torch.Tensor], weight, bias, gamma=None, beta=None, 
     return _FusedLayer.apply(n, groups, prologue, upsample, silu_out, has_res, *flat)
 
 
+# ---- the attention layer on its kernels (the unit they are tested by) ---------------------------------------------------------
+class _FusedAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n, groups, *tensors):
+        # per plane: x [C, h, w], then the ten parameters in the order of `TimeVAEDecoder.program`
+        _no_cpu(*tensors)
+        P = [[f32c(t) for t in tensors[i * 11:(i + 1) * 11]] for i in range(n)]
+        col = lambda j: [p[j] for p in P]
+        c, h, wd = P[0][0].shape[-3:]
+        run = _Run(P[0][0].device, n, groups)
+        with torch.cuda.device(run.dev):
+            out, saved = run.attention_forward(col(0), [col(j) for j in range(1, 11)], c, h, wd)
+        ctx.P, ctx.kept, ctx.args = P, saved, (n, groups, c, h, wd)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        n, groups, c, h, wd = ctx.args
+        P = ctx.P
+        col = lambda j: [p[j] for p in P]
+        g = f32c(g)
+        run = _Run(g.device, n, groups)
+        with torch.cuda.device(run.dev):
+            dx, dp = run.attention_backward(g, col(0), [col(j) for j in range(1, 11)], ctx.kept, c, h, wd)
+        grads = []
+        for i in range(n):
+            grads += [dx[i].view_as(P[i][0])] + [d[i] for d in dp]
+        return (None, None) + tuple(grads)
+
+
+def fused_attention(x: Sequence[torch.Tensor], group_norm_weight, group_norm_bias, to_q_weight, to_q_bias, to_k_weight, to_k_bias,
+                    to_v_weight, to_v_bias, to_out_weight, to_out_bias, groups: int = 1) -> torch.Tensor:
+    """The mid block's attention layer for n planes on the kernels of csrc/attention.hip (3 launches forward, 6 backward): every
+    argument is a list of n per-plane tensors (x [C, h, w], GroupNorm weight / bias [C], the four linears' weight [C, C] and
+    bias [C]) -> x + to_out(softmax(q k^T / sqrt(C)) v) as [n, C, h, w].  Differentiable with respect to every tensor argument;
+    the gradient of `to_k_bias` is exactly zero."""
+    cols = (x, group_norm_weight, group_norm_bias, to_q_weight, to_q_bias, to_k_weight, to_k_bias, to_v_weight, to_v_bias, to_out_weight,
+            to_out_bias)
+    n = len(x)
+    if any(len(c) != n for c in cols):
+        raise ValueError("every argument of fused_attention is a list with one tensor per plane")
+    return _FusedAttention.apply(n, groups, *[c[i] for i in range(n) for c in cols])
+
+
 # ---- the whole generator -----------------------------------------------------------------------------------------------------
 def _attention(x, params, groups):
     """the mid block's attention for n planes at once: x [n, C, H, W], params[i] = (group_norm w, b, q w, b, k w, b, v w, b, out w, b)"""
@@ -208,7 +319,7 @@ def _offsets(ops):
 
 class _PlaneGenerator(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ops, groups, n, *tensors):
+    def forward(ctx, ops, groups, n, attention, *tensors):
         _no_cpu(*tensors)
         offs, k = _offsets(ops)
         assert len(tensors) == n * k
@@ -233,6 +344,10 @@ class _PlaneGenerator(torch.autograd.Function):
                     out = run.conv(t, col(o + 6), col(o + 7), ch, ch, hh, ww, norm=(col(o + 4), col(o + 5), s2), residual=h)
                     saved.append((h, s1, t, s2, ch, hh, ww))
                     h = out
+                elif op == "attn" and attention == "fused":
+                    out, kept = run.attention_forward(h, [col(o + j) for j in range(10)], ch, hh, ww)
+                    saved.append((h, kept, ch, hh, ww))
+                    h = out
                 elif op == "attn":
                     saved.append((h,))
                     h = _attention(h, [p[o:o + 10] for p in P], groups).contiguous()
@@ -245,13 +360,13 @@ class _PlaneGenerator(torch.autograd.Function):
                     s = run.stats(h, ch, hh, ww)
                     saved.append((h, s, ch, cout, hh, ww))
                     h = run.conv(h, col(o + 2), col(o + 3), ch, cout, hh, ww, norm=(col(o), col(o + 1), s))
-        ctx.P, ctx.saved, ctx.spec = P, saved, (ops, groups, n)
+        ctx.P, ctx.saved, ctx.spec = P, saved, (ops, groups, n, attention)
         return h
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        ops, groups, n = ctx.spec
+        ops, groups, n, attention = ctx.spec
         P, saved = ctx.P, ctx.saved
         offs, k = _offsets(ops)
         col = lambda j: [p[j] for p in P]
@@ -277,6 +392,11 @@ class _PlaneGenerator(torch.autograd.Function):
                     dw, db = run.weight_grad(g, h, ch, ch, hh, ww, up=True)
                     g = run.backward_data(g, col(o), ch, ch, hh, ww, up=True)
                     put(o, dw); put(o + 1, db)
+                elif op == "attn" and attention == "fused":
+                    h, kept, ch, hh, ww = sv
+                    g, dp = run.attention_backward(g, h, [col(o + j) for j in range(10)], kept, ch, hh, ww)
+                    for j, v in enumerate(dp):
+                        put(o + j, v)
                 elif op == "attn":
                     (h,) = sv
                     with torch.enable_grad():
@@ -303,7 +423,7 @@ class _PlaneGenerator(torch.autograd.Function):
                     cout = P[0][o].shape[0]
                     dw, db = run.weight_grad(g, h, ch, cout, hh, ww)
                     put(o, dw); put(o + 1, db)
-        return (None, None, None) + tuple(t for row in G for t in row)
+        return (None, None, None, None) + tuple(t for row in G for t in row)
 
 
 # ---- modules with the reference's names --------------------------------------------------------------------------------------
@@ -372,8 +492,10 @@ class TimeVAEDecoder(nn.Module):
     """reference scene/time_decoders.py:447-625 (`TimeDecoder` + `TimeVAEDecoder.init_weights`), same keywords."""
 
     def __init__(self, in_channels=12, out_channels=24, up_block_types=("TimeUpDecoderBlock2D",), block_out_channels=(64,), layers_per_block=2,
-                 norm_num_groups=32, act_fn="silu", norm_type="group", zero_init_residual=True, layer_kwargs=None):
+                 norm_num_groups=32, act_fn="silu", norm_type="group", zero_init_residual=True, layer_kwargs=None, attention=None):
         super().__init__()
+        # path of the mid block's attention layer: "torch", "fused" or None = the process default at call time (set_attention)
+        self.attention = None if attention is None else _checked_attention(attention)
         if any(t != "TimeUpDecoderBlock2D" for t in up_block_types) or act_fn not in ("silu", "swish") or norm_type != "group":
             raise NotImplementedError("TimeUpDecoderBlock2D blocks with SiLU and GroupNorm are implemented")
         if len(set(block_out_channels)) != 1:
@@ -441,8 +563,10 @@ class TimeVAEDecoder(nn.Module):
         return generate_planes([self], [z], frame_id)
 
 
-def generate_planes(decoders: Sequence[TimeVAEDecoder], noises: Sequence[torch.Tensor], frame_id=None) -> torch.Tensor:
-    """decoders of identical shape, one noise map [1, Cin, h, w] each -> [n, Cout, H, W]: every layer is one launch for all of them"""
+def generate_planes(decoders: Sequence[TimeVAEDecoder], noises: Sequence[torch.Tensor], frame_id=None, attention: Optional[str] = None) -> torch.Tensor:
+    """decoders of identical shape, one noise map [1, Cin, h, w] each -> [n, Cout, H, W]: every layer is one launch for all of them.
+    `attention`: "torch", "fused" or None = what the first decoder names, else the process default (set_attention)."""
+    mode = resolve_attention(attention if attention is not None else decoders[0].attention)
     flat, ops0 = [], None
     for net, z in zip(decoders, noises):
         ops, ts = net.program(frame_id)
@@ -451,19 +575,19 @@ def generate_planes(decoders: Sequence[TimeVAEDecoder], noises: Sequence[torch.T
         elif ops != ops0 or [t.shape for t in ts] + [z.shape] != shapes0:
             raise ValueError("the decoders of one call must have identical shapes")
         flat += [z] + ts
-    return _PlaneGenerator.apply(ops0, decoders[0].norm_num_groups, len(decoders), *flat)
+    return _PlaneGenerator.apply(ops0, decoders[0].norm_num_groups, len(decoders), mode, *flat)
 
 
 class Tensorial2D(nn.Module):
     """reference scene/tripFields.py:176-204: a fixed noise map (buffer `noise`) and the decoder `net` that turns it into a plane"""
 
-    def __init__(self, noise_ch=8, out_ch=16, noise_res=20, layer_kwargs=None):
+    def __init__(self, noise_ch=8, out_ch=16, noise_res=20, layer_kwargs=None, attention=None):
         super().__init__()
         self.noise_ch, self.out_ch, self.noise_res = noise_ch, out_ch, noise_res
         self.upx = 16        # the reference's attribute; its forward (and this one) returns 8 x noise_res: three of four up blocks upsample
         self.register_buffer("noise", torch.randn(1, noise_ch, noise_res, noise_res))
         self.net = TimeVAEDecoder(in_channels=noise_ch, out_channels=out_ch, up_block_types=("TimeUpDecoderBlock2D",) * 4,
-                                  block_out_channels=(32, 32, 32, 32), layers_per_block=1, layer_kwargs=layer_kwargs)
+                                  block_out_channels=(32, 32, 32, 32), layers_per_block=1, layer_kwargs=layer_kwargs, attention=attention)
 
     def get_output_shape(self):
         return [self.out_ch, self.noise.size(-2) * self.upx, self.noise.size(-1) * self.upx]
@@ -474,7 +598,8 @@ class Tensorial2D(nn.Module):
 
 class VarTriPlaneEncoder(TriPlaneSampler):
     """reference scene/tripFields.py:383-436: three `Tensorial2D` generators (`subs`) + the per-point lookup of `TriPlaneSampler`.
-    `config` holds the reference's keys: in_ch, out_ch, noise_res, fuse_mode, layer_kwargs (n_frames, strategy)."""
+    `config` holds the reference's keys: in_ch, out_ch, noise_res, fuse_mode, layer_kwargs (n_frames, strategy), and `attention`
+    ("torch", "fused" or None: the path of the generators' attention layer, see `set_attention`)."""
 
     takes_frame_id = True     # SplatFields hands `frame_id` to an encoder that says so
 
@@ -484,7 +609,7 @@ class VarTriPlaneEncoder(TriPlaneSampler):
         super().__init__(out_ch=out_ch, resolution=8 * noise_res, fuse_mode=config.get("fuse_mode", "cat"), plane_source=self._generate)
         self.config = config
         self.in_ch, self.out_ch, self.noise_res = in_ch, out_ch, noise_res
-        self.subs = nn.ModuleList([Tensorial2D(in_ch, out_ch, noise_res, layer_kwargs=config.get("layer_kwargs")) for _ in ("xy", "yz", "zx")])
+        self.subs = nn.ModuleList([Tensorial2D(in_ch, out_ch, noise_res, layer_kwargs=config.get("layer_kwargs"), attention=config.get("attention")) for _ in ("xy", "yz", "zx")])
 
     def _generate(self, frame_id=None):
         return generate_planes([s.net for s in self.subs], [s.noise for s in self.subs], frame_id)
