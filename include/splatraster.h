@@ -328,7 +328,9 @@ int sr_sh_backward(int n_splats, int sh_coeffs, int sh_degree, int n_views, cons
 
 /* mean_dist2[i] = mean squared distance from point i to its 3 nearest other points (exact k-NN).
  * Replaces [EXT] simple_knn._C.distCUDA2 (reference README.md:29), called once at initialisation by reference
- * scene/gaussian_model.py:105.  `workspace` holds sr_knn_workspace_bytes(n) bytes of device memory. */
+ * scene/gaussian_model.py:105.  `workspace` holds sr_knn_workspace_bytes(n) bytes of device memory.
+ * With fewer than 4 points the sum over the neighbours that exist is divided by 3.  A row with a NaN or infinite coordinate,
+ * or one whose neighbours' squared distances overflow float32, gets +inf and takes no part in any other row's search. */
 size_t sr_knn_workspace_bytes(int n_points);
 int sr_knn3_mean_dist2(int n_points, const float* points, float* mean_dist2, void* workspace, void* hip_stream);
 

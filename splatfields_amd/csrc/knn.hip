@@ -16,9 +16,12 @@ namespace sr {
 struct KnnGrid { float3 lo; float inv_cell, cell; int gx, gy, gz; };
 
 __device__ __forceinline__ int3 cell_of(const KnnGrid& g, float x, float y, float z) {
-    int cx = (int)((x - g.lo.x) * g.inv_cell), cy = (int)((y - g.lo.y) * g.inv_cell), cz = (int)((z - g.lo.z) * g.inv_cell);
-    cx = min(max(cx, 0), g.gx - 1); cy = min(max(cy, 0), g.gy - 1); cz = min(max(cz, 0), g.gz - 1);
-    return make_int3(cx, cy, cz);
+    // clamped as floats, before the conversion: a NaN coordinate lands in cell 0 and an infinite one in an end cell (fmaxf and
+    // fminf return their other argument for a NaN), and no out-of-range value ever meets the float -> int conversion
+    const float fx = fminf(fmaxf((x - g.lo.x) * g.inv_cell, 0.f), (float)(g.gx - 1));
+    const float fy = fminf(fmaxf((y - g.lo.y) * g.inv_cell, 0.f), (float)(g.gy - 1));
+    const float fz = fminf(fmaxf((z - g.lo.z) * g.inv_cell, 0.f), (float)(g.gz - 1));
+    return make_int3((int)fx, (int)fy, (int)fz);
 }
 
 // one workgroup: bounding box of all finite points -> bounds[0..5]
@@ -26,7 +29,10 @@ __global__ void __launch_bounds__(1024) k_knn_bounds(int n, const float* __restr
     __shared__ float s_lo[3][16], s_hi[3][16];
     float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
     for (int i = threadIdx.x; i < n; i += 1024)
-        for (int c = 0; c < 3; ++c) { const float v = pts[3 * (size_t)i + c]; if (v == v) { lo[c] = fminf(lo[c], v); hi[c] = fmaxf(hi[c], v); } }
+        for (int c = 0; c < 3; ++c) {  // NaN and +-inf stay out: one infinite coordinate would collapse the grid to a single cell
+            const float v = pts[3 * (size_t)i + c];
+            if (fabsf(v) <= 3.0e38f) { lo[c] = fminf(lo[c], v); hi[c] = fmaxf(hi[c], v); }
+        }
     for (int c = 0; c < 3; ++c) {
         for (int d = 32; d > 0; d >>= 1) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], d, 64)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], d, 64)); }
         if ((threadIdx.x & 63) == 0) { s_lo[c][threadIdx.x >> 6] = lo[c]; s_hi[c][threadIdx.x >> 6] = hi[c]; }
@@ -146,11 +152,13 @@ __global__ void k_knn_search(int n, const float* __restrict__ pts, const float* 
         const float safe = r * g.cell;  // every unvisited point is farther than this
         if (best[2] <= safe * safe) break;
     }
-    // fewer than 4 points: missing neighbours contribute 0, as the published code's zero-initialised best[]... it starts
-    // from FLT_MAX; keep the mean over the neighbours that exist
-    float sum = 0.f; int cnt = 0;
-    for (int k = 0; k < 3; ++k) if (best[k] < 3.0e38f) { sum += best[k]; ++cnt; }
-    out[i] = cnt == 3 ? sum / 3.0f : (cnt > 0 ? sum / 3.0f : 0.0f);
+    // always a third of the sum: with fewer than 4 points the missing neighbours contribute 0.  A neighbour that exists but
+    // whose squared distance is no finite float32 (a point beyond ~1.8e19, a NaN or infinite row) counts as +inf, which is what
+    // the published code's sum of FLT_MAX entries overflows to
+    const int have = min(n - 1, 3);
+    float sum = 0.f;
+    for (int k = 0; k < have; ++k) sum += best[k] < 3.0e38f ? best[k] : __builtin_inff();
+    out[i] = sum / 3.0f;
 }
 
 size_t knn_workspace_bytes(int n) {

@@ -14,11 +14,22 @@ from . import _lib
 from ._lib import ptr
 
 
+def _check_splats(who: str, means3D: torch.Tensor, shs: torch.Tensor) -> None:
+    """Raised before anything is launched: the kernels index means3D [N,3] and shs [N,K,3] through raw pointers."""
+    if not means3D.is_cuda or not shs.is_cuda:
+        raise RuntimeError(f"{who} has no CPU path: tensors must be on a HIP ('cuda') device")
+    if shs.device != means3D.device:
+        raise RuntimeError(f"{who}: shs must be on the splats' device")
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise RuntimeError(f"{who}: means3D must be [N,3]")
+    if shs.dim() != 3 or shs.shape[2] != 3 or shs.shape[0] != means3D.shape[0]:
+        raise RuntimeError(f"{who}: shs must be [N,K,3] with one row per splat")
+
+
 def sh_forward(means3D: torch.Tensor, shs: torch.Tensor, campos: torch.Tensor, sh_degree: int):
     """-> (colors[N,3] f32, clamped[N] u8).  No autograd."""
     lib = _lib.load()
-    if not means3D.is_cuda:
-        raise RuntimeError("sh_forward has no CPU path: tensors must be on a HIP ('cuda') device")
+    _check_splats("sh_forward", means3D, shs)
     dev = means3D.device
     m = means3D.detach().to(torch.float32).contiguous()
     s = shs.detach().to(torch.float32).contiguous()
@@ -37,8 +48,7 @@ def sh_forward_views(means3D: torch.Tensor, shs: torch.Tensor, campos_views: tor
     a channel was not clamped to 0 and 0 where it was (multiply the colour gradient by it before ``sh_backward``).
     ``out``: optional contiguous float32 [V,N,3] tensor to write the colours into (e.g. a communication buffer)."""
     lib = _lib.load()
-    if not means3D.is_cuda:
-        raise RuntimeError("sh_forward_views has no CPU path: tensors must be on a HIP ('cuda') device")
+    _check_splats("sh_forward_views", means3D, shs)
     dev = means3D.device
     m = means3D.detach().to(torch.float32).contiguous()
     s = shs.detach().to(torch.float32).contiguous()
@@ -68,17 +78,23 @@ def sh_backward(means3D, shs, campos_views, dcolors_views, sh_degree: int, *, sc
     through the view directions into ``means_grad`` when given.  ``out``: write dL/dshs into this contiguous float32 [N,K,3]
     tensor (e.g. a row range of a larger gradient) instead of allocating it."""
     lib = _lib.load()
+    _check_splats("sh_backward", means3D, shs)
     dev = means3D.device
+    if dcolors_views.device != dev:
+        raise RuntimeError("sh_backward has no CPU path: dcolors_views must be on the splats' device")
     m = means3D.detach().to(torch.float32).contiguous()
     s = shs.detach().to(torch.float32).contiguous()
     cp = campos_views.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1, 3)
-    dc = dcolors_views.detach().to(torch.float32).contiguous().reshape(cp.shape[0], m.shape[0], 3)
     n, k, v = m.shape[0], s.shape[1], cp.shape[0]
+    if dcolors_views.numel() != v * n * 3:
+        raise RuntimeError("dcolors_views must be [V,N,3]: one colour gradient per view and splat")
+    dc = dcolors_views.detach().to(torch.float32).contiguous().reshape(v, n, 3)
     d_shs = (out if out is not None else torch.empty_like(s)) if want_shs else None
-    if out is not None and not (out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == tuple(s.shape)):
-        raise RuntimeError("out must be a contiguous float32 tensor of the shape of shs")
-    if means_grad is not None and not (means_grad.is_contiguous() and means_grad.dtype == torch.float32):
-        raise RuntimeError("means_grad must be a contiguous float32 tensor")
+    if out is not None and not (out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == tuple(s.shape) and out.device == dev):
+        raise RuntimeError("out must be a contiguous float32 tensor of the shape of shs on the splats' device")
+    if means_grad is not None and not (means_grad.is_contiguous() and means_grad.dtype == torch.float32 and
+                                       tuple(means_grad.shape) == (n, 3) and means_grad.device == dev):
+        raise RuntimeError("means_grad must be a contiguous float32 [N,3] tensor on the splats' device")
     with torch.cuda.device(dev):
         _lib.check(lib.sr_sh_backward(n, k, int(sh_degree), v, ptr(m), ptr(s), ptr(cp), ptr(dc), float(scale), ptr(d_shs),
                                       ptr(means_grad), int(bool(accumulate_means)), _lib.stream(dev)))

@@ -156,6 +156,29 @@ def cloud(kind: str, n: int, seed: int) -> torch.Tensor:
     return p.to(torch.float32)
 
 
+def cloud_with_duplicates():
+    """1500 points of which the last 500 repeat the first 500 exactly: every third row of the exact search has a twin pair
+    astride its k-th place, which only the index can order."""
+    points = cloud("uniform", 1500, 46)
+    points[1000:] = points[:500]
+    return points
+
+
+def cloud_with_non_finite_rows():
+    """2000 uniform points of which 5 rows hold a NaN and 5 an infinity, in one or in every coordinate."""
+    points = cloud("uniform", 2000, 47)
+    nan, inf = float("nan"), float("inf")
+    points[[3, 700, 1999], 1] = nan
+    points[[256, 1024]] = nan
+    points[5, 0], points[900, 2] = inf, -inf
+    points[1500] = inf
+    points[1501] = torch.tensor([inf, -inf, 0.5])
+    points[64] = -inf
+    finite = torch.isfinite(points).all(1)
+    assert int((~finite).sum()) == 10 and int(torch.isnan(points).any(1).sum()) == 5
+    return points, finite
+
+
 # the clouds on which the device's neighbour search is compared with the exact one: (kind, points, seed)
 KNN_CLOUDS = (("uniform", 1000, 45), ("clustered", 20000, 42), ("planar", 4000, 43), ("uniform", 300000, 44))
 

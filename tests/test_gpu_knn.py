@@ -49,6 +49,58 @@ def test_matches_exact_knn(hip_device, n, kind):
     np.testing.assert_allclose(got, ref, rtol=2e-5, atol=1e-12)
 
 
+def degenerate_cloud(kind):
+    rng = np.random.default_rng(len(kind))
+    if kind == "four":                      # exactly three neighbours each
+        return rng.uniform(-1, 1, size=(4, 3)).astype(np.float32)
+    if kind == "collinear":                 # two axes without extent: both sit on the floor that make_grid gives thin axes
+        pts = np.empty((3000, 3), np.float32)
+        pts[:, 0], pts[:, 1], pts[:, 2] = rng.uniform(-1, 1, 3000), 0.25, -0.5
+        return pts
+    if kind == "identical":                 # no extent at all: one cell
+        return np.full((2000, 3), 0.375, np.float32)
+    pts = rng.uniform(-1, 1, size=(2001, 3)).astype(np.float32)
+    pts[777] = (1e30, 0.5, -0.5) if kind == "far_point_x" else (1e30, 1e30, 1e30)    # its squared distances overflow float32
+    return pts
+
+
+@pytest.mark.parametrize("kind", ["four", "collinear", "identical", "far_point_x", "far_point_xyz"])
+def test_degenerate_clouds_match_exact_knn(hip_device, kind):
+    """The exact search in the output's number format: a mean that float32 cannot hold (the point at 1e30) is +inf there, as the
+    published code's sum of FLT_MAX entries is."""
+    from simple_knn._C import distCUDA2
+    pts = degenerate_cloud(kind)
+    got = distCUDA2(torch.from_numpy(pts).to(hip_device)).cpu().numpy()
+    with np.errstate(over="ignore"):
+        ref = oracle_mean_dist2(pts).astype(np.float32)
+    assert got.shape == (len(pts),) and got.dtype == np.float32
+    np.testing.assert_allclose(got, ref, rtol=2e-5, atol=1e-12)
+    if kind == "identical":
+        assert (got == 0).all()
+    if kind.startswith("far_point"):
+        assert np.isinf(ref[777]) and np.isfinite(np.delete(ref, 777)).all() and (np.delete(ref, 777) > 0).all()
+
+
+def test_non_finite_rows_leave_the_finite_rows_exact(hip_device):
+    """2000 points of which 5 rows hold a NaN and 5 an infinity: every finite row gets the exact search over the finite rows
+    only; the others are only required to be written (NaN or inf will do)."""
+    from splatfields_amd import _lib
+    from tests.moran_reference import cloud_with_non_finite_rows
+    points, finite = cloud_with_non_finite_rows()
+    n = points.shape[0]
+    lib = _lib.load()
+    pts = points.to(hip_device)
+    out = torch.full((n,), -7.0, device=hip_device)              # no mean of squares is negative
+    work = torch.empty(lib.sr_knn_workspace_bytes(n), dtype=torch.uint8, device=hip_device)
+    _lib.check(lib.sr_knn3_mean_dist2(n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(work), _lib.stream(hip_device)))
+    got = out.cpu().numpy()
+    assert (got != -7.0).all()
+    f = finite.numpy()
+    np.testing.assert_allclose(got[f], oracle_mean_dist2(points[finite].numpy()), rtol=2e-5, atol=1e-12)
+    from simple_knn._C import distCUDA2
+    assert np.array_equal(distCUDA2(pts).cpu().numpy(), got, equal_nan=True)
+
+
 def test_initial_scales_as_the_reference_computes_them(hip_device):
     """scene/gaussian_model.py:105-109: scales = log(sqrt(clamp_min(distCUDA2(points), 1e-7)))"""
     from simple_knn._C import distCUDA2

@@ -40,9 +40,12 @@ def assert_within(tag, got, want, r):
         assert d[k] <= 4.0 * r[k], (tag, k, d[k], 4.0 * r[k])
 
 
-def assert_same_neighbours(tag, nn_ix, points, k, swap_rel=1e-5, max_share=1e-4):
+def assert_same_neighbours(tag, nn_ix, points, k, swap_rel=1e-5, max_share=1e-4, ties_by_index=False):
     """nn_ix [N,k] (device search) against the exact search on the float64 points: the same set for every point, nearest first;
-    a point whose k-th and (k+1)-th squared distances lie within swap_rel may differ by exactly that swap."""
+    a point whose k-th and (k+1)-th squared distances lie within swap_rel may differ by exactly that swap.
+    ties_by_index (clouds with exact duplicates): where the k-th and the (k+1)-th point are one and the same position the two
+    distances are equal in every number format, so nothing is ambiguous there: the lower index is the neighbour, as in
+    R.exact_knn, and such rows get no allowance and do not count towards max_share."""
     want, d2, following = R.exact_knn(points, k, with_next=True)
     got = nn_ix.cpu().long()
     n = points.shape[0]
@@ -53,6 +56,12 @@ def assert_same_neighbours(tag, nn_ix, points, k, swap_rel=1e-5, max_share=1e-4)
     assert (dist[:, 1:] >= dist[:, :-1] - 1e-6 * dist[:, 1:]).all(), tag
     same = (got.sort(1).values == want.sort(1).values).all(1)
     ambiguous = torch.isfinite(d2[:, -1]) & ((d2[:, -1] - d2[:, -2]) <= swap_rel * d2[:, -1])
+    if ties_by_index:
+        twins = (points[want[:, -1]] == points[following]).all(1)
+        assert twins.any(), (tag, "no tie at the k-th place: the cloud does not test the index rule")
+        ambiguous &= ~twins
+        tied = (points[got[:, 1:]] == points[got[:, :-1]]).all(-1)          # inside a row, equal positions stand by index
+        assert tied.any() and (got[:, 1:] > got[:, :-1])[tied].all(), tag
     share = ambiguous.double().mean().item()
     print(f"[moran] {tag}: {int((~same).sum())} of {n} rows differ from the exact search, {int(ambiguous.sum())} are ambiguous (share {share:.2e})")
     assert share <= max_share
@@ -130,16 +139,52 @@ def test_neighbours_against_the_exact_search(hip_device, kind, n, seed):
     graph = knn_graph(points.to(hip_device), 5)
     assert graph.nn_ix.dtype == torch.int32
     assert_same_neighbours(f"{kind} {n}", graph.nn_ix, points, 5)
-    # the reverse adjacency lists every edge once, under its target, in ascending order
+    assert_reverse_adjacency(graph, n, 5)
+
+
+def assert_reverse_adjacency(graph, n, k):
+    """the reverse adjacency lists every edge once, under its target, in ascending order"""
     start, edges = graph.rev_start.cpu().long(), graph.rev_edges.cpu().long()
-    assert start[0] == 0 and start[-1] == n * 5 and (start[1:] >= start[:-1]).all()
-    assert torch.equal(edges.sort().values, torch.arange(n * 5))
+    assert start[0] == 0 and start[-1] == n * k and (start[1:] >= start[:-1]).all()
+    assert torch.equal(edges.sort().values, torch.arange(n * k))
     target = torch.repeat_interleave(torch.arange(n), start[1:] - start[:-1])
     assert torch.equal(graph.nn_ix.cpu().long().reshape(-1)[edges], target)
-    inner = torch.ones(n * 5, dtype=torch.bool)
-    inner[start[:-1][start[:-1] < n * 5]] = False
+    inner = torch.ones(n * k, dtype=torch.bool)
+    inner[start[:-1][start[:-1] < n * k]] = False
     assert (edges[1:] > edges[:-1])[inner[1:]].all()
     assert torch.equal(graph.order.cpu().long().sort().values, torch.arange(n))
+
+
+@pytest.mark.parametrize("kind", ("uniform", "duplicates"))
+@pytest.mark.parametrize("k", (2, 4, 6, 7), ids=lambda k: f"K{k}")
+def test_neighbours_at_every_other_width_of_the_search(hip_device, k, kind):
+    """k_knn_search_k<K> is instantiated for K = 2 .. 8; the golden cases and the clouds above launch K = 3, 5 and 8 (the
+    `default:` arm of the switch in launch_knn_graph).  These are k_knn_search_k<2>, <4>, <6> and <7>."""
+    from splatfields_amd.moran import knn_graph
+    points = R.cloud("uniform", 1000, 45) if kind == "uniform" else R.cloud_with_duplicates()
+    n = points.shape[0]
+    graph = knn_graph(points.to(hip_device), k)
+    assert graph.nn_ix.dtype == torch.int32 and tuple(graph.nn_ix.shape) == (n, k)
+    assert_same_neighbours(f"{kind} {n} K={k}", graph.nn_ix, points, k, ties_by_index=kind == "duplicates")
+    assert (graph.nn_ix[:, 0].cpu().long() == torch.arange(n))[500 if kind == "duplicates" else 0:1000].all()    # itself first, unless a twin has the lower index
+    assert_reverse_adjacency(graph, n, k)
+
+
+def test_non_finite_rows_leave_the_finite_rows_exact(hip_device):
+    """A NaN or infinite coordinate takes its row out of every other row's search (its distance to anything is no finite number)
+    and out of the grid's bounds; the row itself names in-range indices only, so that every gather stays inside."""
+    from splatfields_amd.moran import knn_graph
+    points, finite = R.cloud_with_non_finite_rows()
+    n, k = points.shape[0], 5
+    graph = knn_graph(points.to(hip_device), k)
+    got = graph.nn_ix.cpu().long()
+    assert tuple(got.shape) == (n, k) and (got >= 0).all() and (got < n).all()
+    index = torch.nonzero(finite).flatten()
+    want, d2 = R.exact_knn(points[finite], k)
+    assert R.ambiguous_share(d2, 1e-5) == 0.0
+    assert torch.equal(got[finite].sort(1).values, index[want].sort(1).values)
+    assert torch.equal(got[finite][:, 0], index)
+    assert_reverse_adjacency(graph, n, k)
 
 
 def test_full_size_against_the_restatement(hip_device):
