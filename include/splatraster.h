@@ -809,6 +809,65 @@ int sr_hull_carve(int n_views, const SrHullView* views, const unsigned char* mas
 int sr_hull_gather(const double* grid, int G, const void* points, long long n_points, int point_is_double, const void* workspace,
                    long long capacity, int* indices_out, float* points_out, void* hip_stream);
 
+/* The flow head of the deform network (reference utils/time_utils.py:194-304 `FlowHead`, the last stage of a dynamic step; replaces
+ * two to four nn.Linear calls, ~25 small per-point kernels and their autograd backward): per point n, with the row h = hidden[n]
+ * (`width` floats) and the point p = pts[n],
+ *   z = [ branch_0(h) | branch_1(h) | ... ],  branch_i(h) = weight_i h + bias_i  (weight_i [rows_i, width] as nn.Linear holds it)
+ * and an epilogue by `model` (eps = 1e-5; I + sin(t) [w] + (1 - cos t) [w]^2 = R(w, t), [w]^2 = w w^T - |w|^2 I;
+ * T(w, v, t) = t v + (1 - cos t) w x v + (t - sin t) w x (w x v)):
+ *   SR_FLOW_OFFSET      branches warp(3)                    flow = z,  means3D = p + flow
+ *   SR_FLOW_SE3         w(3), v(3)                          t = |w|, w' = w / t + eps, v' = v / t + eps, R = R(w', t), T = T(w', v', t):
+ *                                                           means3D = R p + T,  flow = [R T; 0 0 0 1]  ([N, 4, 4], row-major)
+ *   SR_FLOW_SE3_AFFINE  w(3), v(3), offset(3)               means3D = R p + T + offset,  flow = means3D - p
+ *   SR_FLOW_SE3_SCALED  w(3), v(3), scale(1), offset(3)     means3D = softplus(scale) R p + T + offset  (softplus: log1p(exp x), x itself
+ *                                                           above 20),  flow = means3D - p
+ *   SR_FLOW_AFFINE      w(9), v(3)                          means3D = A p + v, A = the nine outputs row-major,  flow = means3D - p
+ *   SR_FLOW_DCT         coeff(3 n_basis)                    flow[c] = sum_k coeff[c n_basis + k] bases[k],  means3D = p + flow
+ * `flow` is [N, 3] except for SR_FLOW_SE3.  A point with |w| = 0 gives non-finite results (as in the reference).
+ *
+ * Tensors are fp32, contiguous and 16-byte aligned (pts, means3D, flow [N, 3] and bases: 4-byte).  z is a sum of doubles in a fixed order
+ * (bias, then the columns of h in order), the epilogue runs in double, and every stored value is rounded once; a workgroup is 256
+ * consecutive points whatever the device, nothing is added atomically and nothing waits on the host: repeated calls are
+ * bit-identical.  Rows are addressed with 64-bit offsets.  One launch each.
+ *
+ * Limits: width a multiple of 4 in 4 .. SR_FLOW_MAX_WIDTH; 1 <= n_basis <= SR_FLOW_MAX_BASIS for SR_FLOW_DCT (ignored otherwise);
+ * the branch count and rows of the model as listed; 0 <= n_points < 2^31.  Anything else, a null pointer where one is read or
+ * written, or a misaligned one, returns nonzero with sr_last_error set before any launch, and the three size queries return 0.
+ * n_points = 0 is valid and launches nothing.
+ *
+ * forward:  `saved` (may be null: no backward will follow) receives z as doubles, sr_flow_head_saved_bytes bytes, 8-byte aligned.
+ * backward: reads pts, bases, `saved`, the branch weights (bias is not read), dL_dmeans3D and dL_dflow (may be null = zeros);
+ *   writes dL_dz [n_points, dz_row] fp32 with dz_row = sr_flow_head_dz_row: every branch's columns start at the next multiple of 4
+ *   (the padding is written as zeros), so that one SrMlpGradJob per branch -- dz = dL_dz + first column, m = rows -- gives all
+ *   weight and bias gradients in one sr_mlp_weight_grad call (allocate one row more than n_points: such a job reads whole rows
+ *   from its first column on); dL_dpts [N, 3] and dL_dhidden [N, width] = dz W (either may be null); and, for SR_FLOW_DCT, one
+ *   partial sum of dL_dbases per workgroup into `workspace`: doubles [ceil(n_points / 256)][n_basis], to be added in this order.
+ *   `workspace`: sr_flow_head_workspace_bytes bytes (never 0 for a supported shape), 8-byte aligned. */
+#define SR_FLOW_OFFSET 0
+#define SR_FLOW_SE3 1
+#define SR_FLOW_SE3_AFFINE 2
+#define SR_FLOW_SE3_SCALED 3
+#define SR_FLOW_AFFINE 4
+#define SR_FLOW_DCT 5
+#define SR_FLOW_MAX_BRANCHES 4
+#define SR_FLOW_MAX_WIDTH 256
+#define SR_FLOW_MAX_OUT 32
+#define SR_FLOW_MAX_BASIS 10
+typedef struct SrFlowBranch {
+    const float* weight;       /* [rows, width] */
+    const float* bias;         /* [rows]; not read by the backward */
+    int rows;
+} SrFlowBranch;
+size_t sr_flow_head_saved_bytes(int model, long long n_points, int width, int n_basis);
+size_t sr_flow_head_workspace_bytes(int model, long long n_points, int width, int n_basis);
+int sr_flow_head_dz_row(int model, int n_basis);
+int sr_flow_head_forward(int model, long long n_points, int width, int n_basis, int n_branches, const SrFlowBranch* branches,
+                         const float* hidden, const float* pts, const float* bases, float* means3D, float* flow, void* saved,
+                         void* hip_stream);
+int sr_flow_head_backward(int model, long long n_points, int width, int n_basis, int n_branches, const SrFlowBranch* branches,
+                          const float* pts, const float* bases, const void* saved, const float* dL_dmeans3D, const float* dL_dflow,
+                          float* dL_dpts, float* dL_dz, float* dL_dhidden, void* workspace, void* hip_stream);
+
 /* Diagnostics for the parity tests: byte offsets of four arrays inside the opaque buffers of a view with these sizes
  * (`instances` = the capacity the binning buffer was carved for):
  *   out[0]  geom:    tile_start  uint32[tiles + 1]   first list entry of every 16x16 tile (row-major tiles)

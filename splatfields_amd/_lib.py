@@ -83,6 +83,13 @@ class SrHullView(C.Structure):
                 ("convention", C.c_int), ("outside", C.c_int)]
 
 
+class SrFlowBranch(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("rows", C.c_int)]
+
+
+# include/splatraster.h: SR_FLOW_*
+FLOW_OFFSET, FLOW_SE3, FLOW_SE3_AFFINE, FLOW_SE3_SCALED, FLOW_AFFINE, FLOW_DCT = 0, 1, 2, 3, 4, 5
+FLOW_MAX_BRANCHES, FLOW_MAX_WIDTH, FLOW_MAX_OUT, FLOW_MAX_BASIS = 4, 256, 32, 10
 HULL_KRT, HULL_NDC, HULL_OUTSIDE_CARVE, HULL_OUTSIDE_KEEP, HULL_MAX_VIEWS = 0, 1, 0, 1, 1024   # include/splatraster.h: SR_HULL_*
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 PLANE_MAX_JOBS = 8                                           # include/splatraster.h: SR_PLANE_MAX_JOBS
@@ -202,6 +209,13 @@ SYMBOLS = {
     "sr_attention_forward": (C.c_int, [C.c_int, C.POINTER(SrAttentionJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "sr_attention_backward": (C.c_int, [C.c_int, C.POINTER(SrAttentionJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                         C.c_void_p]),
+    "sr_flow_head_saved_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "sr_flow_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "sr_flow_head_dz_row": (C.c_int, [C.c_int, C.c_int]),
+    "sr_flow_head_forward": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(SrFlowBranch), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_flow_head_backward": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(SrFlowBranch), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_debug_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_size_t)]),
     "sr_debug_backward_stats": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "sr_profile_enable": (C.c_int, [C.c_int]),

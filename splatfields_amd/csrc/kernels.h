@@ -159,6 +159,20 @@ size_t gn_silu_backward_workspace(int n_planes, int channels, int h, int w);
 void launch_gn_silu_backward_partial(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, void* ws, hipStream_t st);
 void launch_gn_silu_backward_apply(int n, const SrPlaneJob* jobs, int channels, int groups, int h, int w, float eps, const void* ws, hipStream_t st);
 
+// flow_head.hip: arguments are checked by the caller (sr_flow_head_*: flow_head_shape_error / flow_head_branch_error, null = fine);
+// n > 0; every launch_* is one kernel launch
+const char* flow_head_shape_error(int model, long long n_points, int width, int n_basis);
+const char* flow_head_branch_error(int model, int n_basis, int n_branches, const SrFlowBranch* branches);
+int flow_head_outputs(int model, int n_basis);
+int flow_head_dz_row(int model, int n_basis);
+size_t flow_head_saved_bytes(int model, long long n, int n_basis);
+size_t flow_head_workspace_bytes(int model, long long n, int n_basis);
+void launch_flow_head_forward(int model, long long n, int width, int n_basis, int n_branches, const SrFlowBranch* branches, const float* hidden,
+                              const float* pts, const float* bases, float* means, float* flow, void* saved, hipStream_t st);
+void launch_flow_head_backward(int model, long long n, int width, int n_basis, int n_branches, const SrFlowBranch* branches, const float* pts,
+                               const float* bases, const void* saved, const float* g_means, const float* g_flow, float* d_pts, float* d_z,
+                               float* d_hidden, void* workspace, hipStream_t st);
+
 // attention.hip: shapes are checked by the caller (attention_shape_error: null = supported); every launch_* is one kernel launch
 constexpr int kAttentionBackwardSteps = 6;     // launch_attention_backward(step = 0 .. 5), in this order
 const char* attention_shape_error(int channels, int groups, int h, int w);

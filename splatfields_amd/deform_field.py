@@ -19,8 +19,11 @@ attribute `out_dim`, e.g. the reference's own `VarTriPlaneEncoder` instance) as 
 reference's list runs without plane features (`feat_dim = 0`, utils/time_utils.py:333-334).  State-dict keys of the
 decoder-free sampler are `encoder.planes`; a reference checkpoint's `encoder.subs.*` keys need the generator opt-in.
 
-`FlowHead` (utils/time_utils.py:194-303): 'offset', 'se3' (default) and 'dct'; the SE(3) exponential is written out per point
-(no 4x4 batched matmuls), following the reference's formulas including its `w / theta + 1e-5` convention.
+`FlowHead` (utils/time_utils.py:194-303): all seven flow models of the reference -- 'offset', 'se3' (default), 'se3Affine',
+'se3Scaled', 'affine', 'dct' and 'dct_siren' -- with its parameter names; the SE(3) exponential is written out per point (no 4x4
+batched matmuls), following the reference's formulas including its `w / theta + 1e-5` convention (a row with |w_raw| = 0 is
+non-finite there and here).  `path="fused"` (opt-in: `SplatFields(flow_head="fused")`, `set_flow_head`, SPLATFIELDS_FLOW_HEAD) runs
+the branch linears, the per-point epilogue and their backward on the kernels of csrc/flow_head.hip (splatfields_amd/flow_head.py).
 """
 from __future__ import annotations
 
@@ -28,6 +31,7 @@ import math
 from typing import Optional
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from .fused_mlp import PointLinear
@@ -69,24 +73,89 @@ def dct_basis(num_basis: int, num_frames: int) -> torch.Tensor:
     return (math.sqrt(2.0 / num_frames) * torch.cos(math.pi / (2.0 * num_frames) * (2 * t + 1) * k)).to(torch.float32)
 
 
+class SirenMLP(nn.Module):
+    """the reference's SIREN (utils/time_utils.py:76-121): linear layers with sin(30 x) between them, the first layer's weight
+    uniform in +-1 / fan_in, the others' in +-sqrt(6 / fan_in) / 30; biases keep nn.Linear's initialisation"""
+
+    def __init__(self, in_features: int, out_features: int, hidden_features: int, num_hidden_layers: int):
+        super().__init__()
+        dims = [in_features] + [hidden_features] * num_hidden_layers + [out_features]
+        layers = []
+        for i in range(len(dims) - 1):
+            lin = nn.Linear(dims[i], dims[i + 1])
+            bound = 1.0 / dims[i] if i == 0 else math.sqrt(6.0 / dims[i]) / 30.0
+            with torch.no_grad():
+                lin.weight.uniform_(-bound, bound)
+            layers.append(lin)
+        self.net = nn.Sequential(*layers)
+
+    def forward(self, coords):
+        x = coords
+        for lin in self.net[:-1]:
+            x = torch.sin(30 * lin(x))
+        return self.net[-1](x)
+
+
+FLOW_MODELS = ("offset", "se3", "se3Affine", "se3Scaled", "affine", "dct", "dct_siren")
+
+
 class FlowHead(nn.Module):
-    def __init__(self, W: int = 256, flow_model: str = "offset", num_basis: int = 4, n_frames: int = 100):
+    def __init__(self, W: int = 256, flow_model: str = "offset", num_basis: int = 4, n_frames: int = 100, path: Optional[str] = None):
+        """`path`: "torch" (PyTorch ops), "fused" (csrc/flow_head.hip) or None = the process default at call time (set_flow_head)."""
         super().__init__()
         self.W, self.flow_model, self.n_frames, self.num_basis = W, flow_model, n_frames, num_basis
         if flow_model == "offset":
             self.gaussian_warp = PointLinear(W, 3)
-        elif flow_model == "se3":
+        elif flow_model in ("se3", "se3Affine", "se3Scaled"):
             self.branch_w = PointLinear(W, 3)
             self.branch_v = PointLinear(W, 3)
-        elif flow_model == "dct":
+            if flow_model == "se3Scaled":
+                self.branch_scale = PointLinear(W, 1)
+            if flow_model != "se3":
+                self.branch_offset = PointLinear(W, 3)
+        elif flow_model == "affine":
+            self.branch_w = PointLinear(W, 9)
+            self.branch_v = PointLinear(W, 3)
+        elif flow_model in ("dct", "dct_siren"):
             self.branch_coeff = PointLinear(W, 3 * num_basis)
             nn.init.zeros_(self.branch_coeff.weight)
             nn.init.zeros_(self.branch_coeff.bias)
-            self.trajectory_basis = nn.Parameter(dct_basis(num_basis, n_frames * 2))
+            if flow_model == "dct":
+                self.trajectory_basis = nn.Parameter(dct_basis(num_basis, n_frames * 2))
+            else:
+                self.basis_net = SirenMLP(in_features=1, out_features=num_basis, hidden_features=128, num_hidden_layers=2)
         else:
-            raise NotImplementedError(f"flow_model={flow_model!r}: offset, se3 and dct are implemented")
+            raise NotImplementedError(f"flow_model={flow_model!r}: expected one of {FLOW_MODELS}")
+        from .flow_head import checked_flow_head, fused_shape_error, resolve_flow_head
+        self.path = None if path is None else checked_flow_head(path)
+        if resolve_flow_head(self.path) == "fused" and fused_shape_error(flow_model, W, num_basis):    # asked for here, or the process default
+            raise ValueError("FlowHead on the fused path: " + fused_shape_error(flow_model, W, num_basis))
+
+    def branches(self):
+        """the branch linears in the order of the fused kernel's z layout (include/splatraster.h: sr_flow_head_forward)"""
+        names = {"offset": ("gaussian_warp",), "se3": ("branch_w", "branch_v"), "se3Affine": ("branch_w", "branch_v", "branch_offset"),
+                 "se3Scaled": ("branch_w", "branch_v", "branch_scale", "branch_offset"), "affine": ("branch_w", "branch_v"),
+                 "dct": ("branch_coeff",), "dct_siren": ("branch_coeff",)}[self.flow_model]
+        return [getattr(self, n) for n in names]
+
+    def _bases(self, time_step, frame_id):
+        """bases [K] of the fused path: a row of `trajectory_basis`, or the SIREN evaluated in float64 (one point, 17 k
+        multiply-adds: the kernels compute in double, and sin(30 x) in float32 would be the largest error of the head)"""
+        if self.flow_model == "dct":
+            return self.trajectory_basis[frame_id.long() if torch.is_tensor(frame_id) else int(frame_id)]
+        with torch.autocast(time_step.device.type, enabled=False):
+            x = time_step.view(1, 1).double()
+            layers = list(self.basis_net.net)
+            for lin in layers[:-1]:
+                x = torch.sin(30 * F.linear(x, lin.weight.double(), lin.bias.double()))
+            return F.linear(x, layers[-1].weight.double(), layers[-1].bias.double()).view(-1)
 
     def forward(self, hidden, pts, time_step=None, frame_id=None):
+        from .flow_head import fused_flow_head, resolve_flow_head
+        if resolve_flow_head(self.path) == "fused":
+            bases = self._bases(time_step, frame_id) if self.flow_model in ("dct", "dct_siren") else None
+            lins = self.branches()
+            return fused_flow_head(self.flow_model, hidden, pts, [l.weight for l in lins], [l.bias for l in lins], bases)
         if self.flow_model == "offset":
             flow = self.gaussian_warp(hidden)
             return flow, pts + flow
@@ -98,8 +167,25 @@ class FlowHead(nn.Module):
             flow = se3_transform(w, v, theta)
             means3D = (flow[:, :3, :3] * pts[:, None, :]).sum(-1) + flow[:, :3, 3]
             return flow, means3D
+        if self.flow_model in ("se3Affine", "se3Scaled"):
+            w, v = self.branch_w(hidden), self.branch_v(hidden)
+            theta = torch.norm(w, dim=-1, keepdim=True)
+            w = w / theta + 1e-5
+            v = v / theta + 1e-5
+            R, p = _se3_parts(w, v, theta)
+            if self.flow_model == "se3Scaled":      # the rotation block is scaled, the translation is not
+                R = F.softplus(self.branch_scale(hidden))[:, :, None] * R
+            means3D = (R * pts[:, None, :]).sum(-1) + p + self.branch_offset(hidden)
+            return means3D - pts, means3D
+        if self.flow_model == "affine":
+            A = self.branch_w(hidden).view(-1, 3, 3)
+            means3D = (A * pts[:, None, :]).sum(-1) + self.branch_v(hidden)
+            return means3D - pts, means3D
         coeff = self.branch_coeff(hidden).view(-1, 3, self.num_basis)
-        bases = self.trajectory_basis[frame_id.long() if torch.is_tensor(frame_id) else int(frame_id)]
+        if self.flow_model == "dct":
+            bases = self.trajectory_basis[frame_id.long() if torch.is_tensor(frame_id) else int(frame_id)]
+        else:
+            bases = self.basis_net(time_step.view(1, 1))
         flow = (coeff * bases.view(1, 1, -1)).sum(-1)
         return flow, pts + flow
 
@@ -107,7 +193,8 @@ class FlowHead(nn.Module):
 class SplatFields(nn.Module):
     def __init__(self, radius=None, n_frames: int = 0, encoder: Optional[nn.Module] = None, mlp_precision: Optional[str] = None, **kwargs):
         """`mlp_precision`: "fp32", "bf16" or None (the process default, splatfields_amd.set_mlp_precision) for the fused layer
-        chains of every GeneralMLP built here."""
+        chains of every GeneralMLP built here.  `flow_head="torch" | "fused"` (a keyword, so it also arrives through
+        `SplatFieldsModel`'s hyper_args): the path of the flow head, None = the process default (splatfields_amd.set_flow_head)."""
         super().__init__()
         rank = kwargs.get("composition_rank", 0)
         self.n_frames = n_frames
@@ -168,7 +255,7 @@ class SplatFields(nn.Module):
         if n_frames > 0:
             self.mlp_flow = mlp("flow", kwargs.get("flow_w", 128), 128, 6, [3], kwargs.get("flow_multires", 6), "none")
             self.mlp_flow_head = FlowHead(W=self.mlp_flow.out_features, flow_model=kwargs.get("flow_model", "se3"),
-                                          num_basis=kwargs.get("dct_basis", 4), n_frames=n_frames)
+                                          num_basis=kwargs.get("dct_basis", 4), n_frames=n_frames, path=kwargs.get("flow_head"))
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """`nn.Module.load_state_dict`, plus one loud check: a reference default-config checkpoint holds the weights of its
