@@ -868,6 +868,51 @@ int sr_flow_head_backward(int model, long long n_points, int width, int n_basis,
                           const float* pts, const float* bases, const void* saved, const float* dL_dmeans3D, const float* dL_dflow,
                           float* dL_dpts, float* dL_dz, float* dL_dhidden, void* workspace, void* hip_stream);
 
+/* The view-dependent colour head (reference utils/time_utils.py:360-376, 494-498 `mlp_rgb_viewdep` with use_view_dep_rgb, evaluated per
+ * view by gaussian_renderer/__init__.py:43-46; replaces, per view, a subtract, a norm, a divide, a cat that materialises
+ * [N, width + 3], an addmm, a sigmoid and their autograd backward): for every point n and every view v of a step, in one launch,
+ *   z[v, c]   = bias[c] + sum_f weight[c, f] feature[n, f] + sum_k weight[c, width + k] r_v[k],   colours[v, n, c] = 1 / (1 + exp(-z[v, c]))
+ *   r_v = (p - c_v) / |p - c_v|, p = means3D[n], c_v = campos[v]   (SR_VIEW_FROM_CAMERAS: `campos_or_dirs` is campos [V, 3])
+ *   r_v = dirs[v, n]                                                (SR_VIEW_DIRS_GIVEN:   `campos_or_dirs` is dirs [V, N, 3]; means3D is not read)
+ * `weight` [3, width + 3] and `bias` [3] as nn.Linear holds them over cat([feature, viewdir]).  The one limit: a point that
+ * coincides with a camera centre gives non-finite values in that view (as in the reference).
+ *
+ * Tensors are fp32 and contiguous; feature, weight, dL_dfeature and dL_dzsum 16-byte aligned, saved and workspace 8-byte, the
+ * [., 3] tensors and bias 4-byte.  z is a sum of doubles in a fixed order (bias, then the feature columns in order, then the three
+ * direction columns); the direction, the sigmoid and the backward run in double and every stored value is rounded once; a workgroup
+ * is 256 consecutive points whatever the device, nothing is added atomically and nothing waits on the host: repeated calls are
+ * bit-identical.  Rows are addressed with 64-bit offsets.  One launch each; the feature rows are read once for all views.
+ *
+ * Limits: mode one of the two; width a multiple of 4 in 4 .. SR_VIEW_MAX_WIDTH; 1 <= n_views <= SR_VIEW_MAX_VIEWS (more views:
+ * several calls); 0 <= n_points < 2^31.  Anything else, a null pointer where one is read or written, or a misaligned one, returns
+ * nonzero with sr_last_error set before any launch, and the two size queries return 0.  n_points = 0 is valid and launches nothing.
+ *
+ * forward:  `saved` (may be null: no backward will follow) receives the view-independent part bias + weight[:, :width] feature as
+ *   doubles [3][n_points], sr_view_color_saved_bytes bytes: the backward re-derives every z[v] from it with the same three FMAs.
+ * backward: reads means3D / campos or dirs, weight, `saved` and dL_dcolours [V, N, 3] (feature and bias are not read).  With
+ *   g[v] = dL_dcolours[v, n] s (1 - s) it writes
+ *     dL_dzsum [n_points + 1, 4]: row n = [ sum_v g[v] in view order | 0 ] (the last row is not written), so that ONE SrMlpGradJob --
+ *       dz = dL_dzsum, dz_row = 4, m = 3, x = feature, k = width, dw_row = width + 3, dw_col0 = 0, db = null -- gives dweight[:, :width];
+ *     dL_dfeature [N, width] = that sum times weight[:, :width], written once (may be null);
+ *     dL_dpos (may be null): SR_VIEW_FROM_CAMERAS dL_dmeans3D [N, 3] = sum_v (I - r_v r_v^T) / |p - c_v| weight[:, width:]^T g[v] in view
+ *       order; SR_VIEW_DIRS_GIVEN dL_ddirs [V, N, 3], [v, n] = weight[:, width:]^T g[v];
+ *     one partial sum per workgroup of dweight[:, width:] = sum_n sum_v g[v] (x) r_v (row-major 3 x 3) and of dbias = sum_n sum_v g[v]
+ *       into `workspace`: doubles [ceil(n_points / 256)][12], nine and three, to be added in this order.  (dbias is summed here, in
+ *       double: its terms span the whole range of the upstream gradients, which a float32 sum over 10^5 points does not hold.)
+ *   `workspace`: sr_view_color_workspace_bytes bytes (never 0 for a supported shape). */
+#define SR_VIEW_FROM_CAMERAS 0
+#define SR_VIEW_DIRS_GIVEN 1
+#define SR_VIEW_MAX_WIDTH 256
+#define SR_VIEW_MAX_VIEWS 16
+size_t sr_view_color_saved_bytes(long long n_points, int width, int n_views);
+size_t sr_view_color_workspace_bytes(long long n_points, int width, int n_views);
+int sr_view_color_forward(int mode, long long n_points, int width, int n_views, const float* feature, const float* means3D,
+                          const float* campos_or_dirs, const float* weight, const float* bias, float* colours, void* saved,
+                          void* hip_stream);
+int sr_view_color_backward(int mode, long long n_points, int width, int n_views, const float* means3D, const float* campos_or_dirs,
+                           const float* weight, const void* saved, const float* dL_dcolours, float* dL_dfeature, float* dL_dpos,
+                           float* dL_dzsum, void* workspace, void* hip_stream);
+
 /* Diagnostics for the parity tests: byte offsets of four arrays inside the opaque buffers of a view with these sizes
  * (`instances` = the capacity the binning buffer was carved for):
  *   out[0]  geom:    tile_start  uint32[tiles + 1]   first list entry of every 16x16 tile (row-major tiles)

@@ -90,6 +90,7 @@ class SrFlowBranch(C.Structure):
 # include/splatraster.h: SR_FLOW_*
 FLOW_OFFSET, FLOW_SE3, FLOW_SE3_AFFINE, FLOW_SE3_SCALED, FLOW_AFFINE, FLOW_DCT = 0, 1, 2, 3, 4, 5
 FLOW_MAX_BRANCHES, FLOW_MAX_WIDTH, FLOW_MAX_OUT, FLOW_MAX_BASIS = 4, 256, 32, 10
+VIEW_FROM_CAMERAS, VIEW_DIRS_GIVEN, VIEW_MAX_WIDTH, VIEW_MAX_VIEWS = 0, 1, 256, 16   # include/splatraster.h: SR_VIEW_*
 HULL_KRT, HULL_NDC, HULL_OUTSIDE_CARVE, HULL_OUTSIDE_KEEP, HULL_MAX_VIEWS = 0, 1, 0, 1, 1024   # include/splatraster.h: SR_HULL_*
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 PLANE_MAX_JOBS = 8                                           # include/splatraster.h: SR_PLANE_MAX_JOBS
@@ -216,6 +217,12 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_flow_head_backward": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(SrFlowBranch), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_view_color_saved_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "sr_view_color_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "sr_view_color_forward": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_view_color_backward": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_debug_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_size_t)]),
     "sr_debug_backward_stats": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "sr_profile_enable": (C.c_int, [C.c_int]),
@@ -273,6 +280,16 @@ class use_library:
         global _lib
         _lib = self.prev
         return False
+
+
+def view_color_shape_error(width: int, n_views: int):
+    """why sr_view_color_* refuses this shape, or None (the limits of include/splatraster.h, restated so that a module can be
+    refused at construction without the library)"""
+    if width < 4 or width % 4 or width > VIEW_MAX_WIDTH:
+        return f"the feature width must be a multiple of 4 in 4..{VIEW_MAX_WIDTH}, got {width}"
+    if not (1 <= n_views <= VIEW_MAX_VIEWS):
+        return f"the number of views of one call must be in 1..{VIEW_MAX_VIEWS}, got {n_views}"
+    return None
 
 
 def check(status: int) -> None:

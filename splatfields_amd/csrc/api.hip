@@ -1176,6 +1176,46 @@ int sr_flow_head_backward(int model, long long n_points, int width, int n_basis,
     return check_hip(hipGetLastError(), "flow_head_backward");
 }
 
+// ---- the view-dependent colour head (view_color.hip) ------------------------------------------------------------------------------
+size_t sr_view_color_saved_bytes(long long n_points, int width, int n_views) {
+    return sr::view_color_shape_error(SR_VIEW_FROM_CAMERAS, n_points, width, n_views) ? 0 : sr::view_color_saved_bytes(n_points);
+}
+
+size_t sr_view_color_workspace_bytes(long long n_points, int width, int n_views) {
+    return sr::view_color_shape_error(SR_VIEW_FROM_CAMERAS, n_points, width, n_views) ? 0 : sr::view_color_workspace_bytes(n_points);
+}
+
+int sr_view_color_forward(int mode, long long n_points, int width, int n_views, const float* feature, const float* means3D,
+                          const float* campos_or_dirs, const float* weight, const float* bias, float* colours, void* saved,
+                          void* hip_stream) {
+    if (const char* why = sr::view_color_shape_error(mode, n_points, width, n_views)) return fail(std::string("sr_view_color_forward: ") + why);
+    if (n_points == 0) return 0;
+    if (!feature || !campos_or_dirs || !weight || !bias || !colours) return fail("null pointer in sr_view_color_forward");
+    if (mode == SR_VIEW_FROM_CAMERAS && !means3D) return fail("null pointer in sr_view_color_forward: the camera mode reads means3D");
+    if (((reinterpret_cast<uintptr_t>(feature) | reinterpret_cast<uintptr_t>(weight)) & 15u) || (reinterpret_cast<uintptr_t>(saved) & 7u) ||
+        any_unaligned4(means3D, campos_or_dirs, bias, colours))
+        return fail("sr_view_color_forward: feature and weight must be 16-byte aligned, saved 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_view_color_forward(mode, n_points, width, n_views, feature, means3D, campos_or_dirs, weight, bias, colours, saved, st); }
+    return check_hip(hipGetLastError(), "view_color_forward");
+}
+
+int sr_view_color_backward(int mode, long long n_points, int width, int n_views, const float* means3D, const float* campos_or_dirs,
+                           const float* weight, const void* saved, const float* dL_dcolours, float* dL_dfeature, float* dL_dpos,
+                           float* dL_dzsum, void* workspace, void* hip_stream) {
+    if (const char* why = sr::view_color_shape_error(mode, n_points, width, n_views)) return fail(std::string("sr_view_color_backward: ") + why);
+    if (n_points == 0) return 0;
+    if (!campos_or_dirs || !weight || !saved || !dL_dcolours || !dL_dzsum || !workspace) return fail("null pointer in sr_view_color_backward");
+    if (mode == SR_VIEW_FROM_CAMERAS && !means3D) return fail("null pointer in sr_view_color_backward: the camera mode reads means3D");
+    if (((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(dL_dfeature) | reinterpret_cast<uintptr_t>(dL_dzsum)) & 15u) ||
+        ((reinterpret_cast<uintptr_t>(saved) | reinterpret_cast<uintptr_t>(workspace)) & 7u) || any_unaligned4(means3D, campos_or_dirs, dL_dcolours, dL_dpos))
+        return fail("sr_view_color_backward: weight, dL_dfeature and dL_dzsum must be 16-byte aligned, saved and workspace 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_view_color_backward(mode, n_points, width, n_views, means3D, campos_or_dirs, weight, saved, dL_dcolours, dL_dfeature,
+                                                           dL_dpos, dL_dzsum, workspace, st); }
+    return check_hip(hipGetLastError(), "view_color_backward");
+}
+
 // ---- the generator's attention layer (attention.hip) ---------------------------------------------------------------------------
 static int attention_check(const char* who, int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width) {
     if (!jobs) return fail(std::string("null pointer in ") + who + ": jobs");

@@ -4,10 +4,8 @@
 //
 // Mapping.  A workgroup owns 256 consecutive points, one per thread, on every device: no sum depends on the grid.  The branch
 // weights are staged once per workgroup into LDS as one [M][width] fp32 matrix (M = all branch rows, <= 32).  `hidden` rows are
-// 512 bytes at the reference's width, so a thread walking its own row would touch 64 cache lines per wave instruction: the
-// workgroup instead moves 16 columns of its 256 rows at a time through an LDS tile -- four lanes load the four 16-byte vectors of
-// one row's 64-byte piece, and each thread then reads its own row's piece back (row stride 20 floats: the 16 lanes of a
-// ds_read_b128 group land on 16 different 4-bank slots).  The weights of a column group are the same LDS address in every lane
+// 512 bytes at the reference's width: the workgroup moves 16 columns of its 256 rows at a time through an LDS tile (point_tile.h),
+// coalesced in, and each thread then reads its own row's piece back.  The weights of a column group are the same LDS address in every lane
 // (a broadcast read).  dL/dhidden goes the same way in the other direction: 16 columns per thread into the tile, coalesced out.
 //
 // Arithmetic.  z[m] = bias[m] + sum over columns c = 0, 1, ... of h[c] W[m][c], a chain of double FMAs (the product of two
@@ -16,14 +14,12 @@
 // the forward's z, saved as doubles ([M][N], so that a wavefront's loads and stores of one z are contiguous), and multiplies the
 // unrounded dz with W for dL/dhidden.  No atomics, no host wait.
 #include "kernels.h"
+#include "point_tile.h"
 #include "reduce.h"
 
 namespace sr {
 
 namespace {
-
-constexpr int kFlowCols = 16;            // columns of `hidden` per pass through the tile
-constexpr int kFlowTileRow = 20;         // floats per tile row: 16 + 4 of padding
 
 struct FlowK {
     int model, width, n_basis, n_branches, dz_row;
@@ -131,28 +127,6 @@ __device__ __forceinline__ void stage_weights(const FlowK& P, float* s_w) {
     }
 }
 
-// 16 columns [c0, c0 + 16) of this workgroup's 256 rows of `src` into the tile; columns past the width and rows past n read as zeros
-__device__ __forceinline__ void tile_load(const float* __restrict__ src, long long first, long long n, int width, int c0, float* s_tile) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = (int)threadIdx.x + kBlock * i, row = idx >> 2, q = idx & 3;
-        const long long point = first + row;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (point < n && c0 + 4 * q < width) v = *reinterpret_cast<const float4*>(src + (size_t)point * width + c0 + 4 * q);
-        *reinterpret_cast<float4*>(s_tile + row * kFlowTileRow + 4 * q) = v;
-    }
-}
-
-__device__ __forceinline__ void tile_store(float* __restrict__ dst, long long first, long long n, int width, int c0, const float* s_tile) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = (int)threadIdx.x + kBlock * i, row = idx >> 2, q = idx & 3;
-        const long long point = first + row;
-        if (point < n && c0 + 4 * q < width)
-            *reinterpret_cast<float4*>(dst + (size_t)point * width + c0 + 4 * q) = *reinterpret_cast<const float4*>(s_tile + row * kFlowTileRow + 4 * q);
-    }
-}
-
 __device__ __forceinline__ Vec3 load3(const float* __restrict__ p, long long i) { return v3((double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]); }
 __device__ __forceinline__ void store3(float* __restrict__ p, long long i, Vec3 v) { p[3 * i] = (float)v.x; p[3 * i + 1] = (float)v.y; p[3 * i + 2] = (float)v.z; }
 
@@ -183,13 +157,13 @@ __global__ void __launch_bounds__(kBlock) k_flow_head_forward(const FlowK P) {
     double z[kM];
 #pragma unroll
     for (int m = 0; m < kM; ++m) z[m] = s_bias[m];
-    for (int c0 = 0; c0 < P.width; c0 += kFlowCols) {
+    for (int c0 = 0; c0 < P.width; c0 += kTileCols) {
         tile_load(P.hidden, first, P.n, P.width, c0, s_tile);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (c0 + 4 * q < P.width) {                   // the same in every thread
-                const float4 h = *reinterpret_cast<const float4*>(s_tile + tid * kFlowTileRow + 4 * q);
+                const float4 h = *reinterpret_cast<const float4*>(s_tile + tid * kTileRow + 4 * q);
                 const double h0 = h.x, h1 = h.y, h2 = h.z, h3 = h.w;
 #pragma unroll
                 for (int m = 0; m < kM; ++m) {
@@ -369,7 +343,7 @@ __global__ void __launch_bounds__(kBlock) k_flow_head_backward(const FlowK P) {
         }
     }
     if (!P.d_hidden) return;
-    for (int c0 = 0; c0 < P.width; c0 += kFlowCols) {
+    for (int c0 = 0; c0 < P.width; c0 += kTileCols) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (c0 + 4 * q < P.width) {
@@ -382,7 +356,7 @@ __global__ void __launch_bounds__(kBlock) k_flow_head_backward(const FlowK P) {
                     o2 = fma(dz[m], (double)w.z, o2);
                     o3 = fma(dz[m], (double)w.w, o3);
                 }
-                *reinterpret_cast<float4*>(s_tile + tid * kFlowTileRow + 4 * q) = make_float4((float)o0, (float)o1, (float)o2, (float)o3);
+                *reinterpret_cast<float4*>(s_tile + tid * kTileRow + 4 * q) = make_float4((float)o0, (float)o1, (float)o2, (float)o3);
             }
         }
         __syncthreads();
@@ -405,7 +379,7 @@ int flow_rows(int model, int n_basis, int* rows) {
 
 template <bool kBackward, int kM>
 void flow_launch_m(const FlowK& k, hipStream_t st) {
-    const size_t lds = ((size_t)kM * k.width + (size_t)kBlock * kFlowTileRow) * sizeof(float);      // <= 32 KiB + 20 KiB
+    const size_t lds = ((size_t)kM * k.width + (size_t)kBlock * kTileRow) * sizeof(float);      // <= 32 KiB + 20 KiB
     const unsigned blocks = (unsigned)((k.n + kBlock - 1) / kBlock);
     if (kBackward) hipLaunchKernelGGL(k_flow_head_backward<kM>, dim3(blocks), dim3(kBlock), lds, st, k);
     else hipLaunchKernelGGL(k_flow_head_forward<kM>, dim3(blocks), dim3(kBlock), lds, st, k);

@@ -173,6 +173,17 @@ void launch_flow_head_backward(int model, long long n, int width, int n_basis, i
                                const float* bases, const void* saved, const float* g_means, const float* g_flow, float* d_pts, float* d_z,
                                float* d_hidden, void* workspace, hipStream_t st);
 
+// view_color.hip: arguments are checked by the caller (sr_view_color_*: view_color_shape_error, null = fine); n > 0; every
+// launch_* is one kernel launch
+const char* view_color_shape_error(int mode, long long n_points, int width, int n_views);
+size_t view_color_saved_bytes(long long n);
+size_t view_color_workspace_bytes(long long n);
+void launch_view_color_forward(int mode, long long n, int width, int n_views, const float* feature, const float* means, const float* cam_or_dirs,
+                               const float* weight, const float* bias, float* colours, void* saved, hipStream_t st);
+void launch_view_color_backward(int mode, long long n, int width, int n_views, const float* means, const float* cam_or_dirs, const float* weight,
+                                const void* saved, const float* g_colours, float* d_feature, float* d_pos, float* d_zsum, void* workspace,
+                                hipStream_t st);
+
 // attention.hip: shapes are checked by the caller (attention_shape_error: null = supported); every launch_* is one kernel launch
 constexpr int kAttentionBackwardSteps = 6;     // launch_attention_backward(step = 0 .. 5), in this order
 const char* attention_shape_error(int channels, int groups, int h, int w);

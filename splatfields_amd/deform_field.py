@@ -24,6 +24,10 @@ decoder-free sampler are `encoder.planes`; a reference checkpoint's `encoder.sub
 batched matmuls), following the reference's formulas including its `w / theta + 1e-5` convention (a row with |w_raw| = 0 is
 non-finite there and here).  `path="fused"` (opt-in: `SplatFields(flow_head="fused")`, `set_flow_head`, SPLATFIELDS_FLOW_HEAD) runs
 the branch linears, the per-point epilogue and their backward on the kernels of csrc/flow_head.hip (splatfields_amd/flow_head.py).
+
+`ViewColor` is `out["rgb_fnc"]` of a `use_view_dep_rgb` network (utils/time_utils.py:496): the reference's call, plus
+`for_cameras(means3D, camera_centers)` for all views of a step.  `view_color="fused"` (opt-in: `SplatFields(view_color="fused")`,
+`set_view_color`, SPLATFIELDS_VIEW_COLOR) runs it on the kernels of csrc/view_color.hip (splatfields_amd/view_color.py).
 """
 from __future__ import annotations
 
@@ -190,11 +194,43 @@ class FlowHead(nn.Module):
         return flow, pts + flow
 
 
+class ViewColor:
+    """`out["rgb_fnc"]` of a view-dependent network: the reference's `lambda viewdir: mlp_rgb_viewdep(cat([rgb, viewdir]))`
+    (utils/time_utils.py:496) as an object that can also evaluate every view of a step at once.
+
+    fnc(viewdir [N, 3]) -> [N, 3]: the reference's call.  `path == "torch"`: the same PyTorch ops; "fused": the kernels of
+    csrc/view_color.hip with the directions as given (splatfields_amd/view_color.py).
+    fnc.for_cameras(means3D [N, 3], camera_centers [V, 3]) -> [V, N, 3]: what reference gaussian_renderer/__init__.py:44-46
+    computes per view -- "torch": a loop over those expressions; "fused": one launch for all views."""
+
+    def __init__(self, head: nn.Sequential, feature: torch.Tensor, path: str):
+        self.head, self.feature, self.path = head, feature, path
+
+    def __call__(self, viewdir):
+        if self.path == "fused":
+            from .view_color import fused_view_color
+            return fused_view_color(self.feature, self.head[0].weight, self.head[0].bias, dirs=viewdir[None])[0]
+        return self.head(torch.cat([self.feature, viewdir], dim=-1))
+
+    def for_cameras(self, means3D, camera_centers):
+        if self.path == "fused":
+            from .view_color import fused_view_color
+            return fused_view_color(self.feature, self.head[0].weight, self.head[0].bias, means3D=means3D, camera_centers=camera_centers)
+        colours = []
+        for centre in camera_centers:
+            ray_d = means3D - centre[None]
+            ray_d = ray_d / torch.norm(ray_d, dim=-1, keepdim=True)
+            colours.append(self(ray_d))
+        return torch.stack(colours)
+
+
 class SplatFields(nn.Module):
     def __init__(self, radius=None, n_frames: int = 0, encoder: Optional[nn.Module] = None, mlp_precision: Optional[str] = None, **kwargs):
         """`mlp_precision`: "fp32", "bf16" or None (the process default, splatfields_amd.set_mlp_precision) for the fused layer
         chains of every GeneralMLP built here.  `flow_head="torch" | "fused"` (a keyword, so it also arrives through
-        `SplatFieldsModel`'s hyper_args): the path of the flow head, None = the process default (splatfields_amd.set_flow_head)."""
+        `SplatFieldsModel`'s hyper_args): the path of the flow head, None = the process default (splatfields_amd.set_flow_head).
+        `view_color="torch" | "fused"`, likewise: the path of the view-dependent colour head of `use_view_dep_rgb`
+        (splatfields_amd.set_view_color)."""
         super().__init__()
         rank = kwargs.get("composition_rank", 0)
         self.n_frames = n_frames
@@ -246,6 +282,13 @@ class SplatFields(nn.Module):
                            "none" if self.use_view_dep_rgb else "sigmoid")
         if self.use_view_dep_rgb:
             self.mlp_rgb_viewdep = nn.Sequential(nn.Linear(3 + self.mlp_rgb.out_features, 3), nn.Sigmoid())
+        from . import _lib
+        from .view_color import checked_view_color, resolve_view_color
+        self.view_color = None if kwargs.get("view_color") is None else checked_view_color(kwargs["view_color"])
+        if self.use_view_dep_rgb and resolve_view_color(self.view_color) == "fused":      # asked for here, or the process default
+            why = _lib.view_color_shape_error(self.mlp_rgb.out_features, 1)
+            if why:
+                raise ValueError("SplatFields: the fused view-colour head cannot run this network: " + why)
         self.geo_model_disable_pts = bool(kwargs.get("geo_model_disable_pts", False))
         geo_in = in_ch - (3 if self.geo_model_disable_pts else 0)
         off = self.geo_model_disable_pts
@@ -314,7 +357,8 @@ class SplatFields(nn.Module):
         out["rotations"] = self.mlp_rotation(geo_xyz, geo_feat, frame_id=frame_id, **tk)
         rgb = self.mlp_rgb(xyz_can, feat, frame_id=frame_id, **tk)
         if self.use_view_dep_rgb:
-            out["rgb_fnc"] = lambda viewdir: self.mlp_rgb_viewdep(torch.cat([rgb, viewdir], dim=-1))
+            from .view_color import resolve_view_color
+            out["rgb_fnc"] = ViewColor(self.mlp_rgb_viewdep, rgb, resolve_view_color(self.view_color))
         else:
             out["rgb"] = rgb
         if self.n_frames > 0:

@@ -5,7 +5,8 @@ Same signature, same ``gaussian_dict`` keys in, same result dict out
 inside the boundary: (1) the alpha image comes out of the same rasterization (fused output) instead
 of a second full pass with white colours on a black background (:104-115) -- identical values, half
 the work; ``two_pass=True`` reproduces the reference's call pattern literally; (2) the device of the
-screen-space dummy follows ``means3D`` instead of the literal "cuda" (:49)."""
+screen-space dummy follows ``means3D`` instead of the literal "cuda" (:49).  Opt-in: a ``gaussian_rgb_fnc`` that is the
+network's ``ViewColor`` object on its fused path is asked for the view's colours in one launch instead of :44-46's ops."""
 from __future__ import annotations
 
 import torch
@@ -23,7 +24,11 @@ def render(viewpoint_camera, gaussian_dict: dict, pipe, bg_color: torch.Tensor, 
     gaussian_rotations = gaussian_dict['gaussian_rotations']
     gaussian_features = gaussian_dict.get('gaussian_features', None)
     gaussian_rgb = gaussian_dict.get('gaussian_rgb', None)
-    if gaussian_rgb is None and 'gaussian_rgb_fnc' in gaussian_dict:
+    rgb_fnc = gaussian_dict.get('gaussian_rgb_fnc', None) if gaussian_rgb is None else None
+    if rgb_fnc is not None and hasattr(rgb_fnc, "for_cameras") and getattr(rgb_fnc, "path", None) == "fused":
+        # the view-dependent head on its kernels (splatfields_amd/view_color.py): directions, linear and sigmoid in one launch
+        gaussian_rgb = rgb_fnc.for_cameras(means3D, viewpoint_camera.camera_center[None])[0]
+    elif gaussian_rgb is None and 'gaussian_rgb_fnc' in gaussian_dict:
         ray_d = means3D - viewpoint_camera.camera_center[None]
         ray_d = ray_d / torch.norm(ray_d, dim=-1, keepdim=True)
         gaussian_rgb = gaussian_dict['gaussian_rgb_fnc'](ray_d)
