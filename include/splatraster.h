@@ -545,6 +545,24 @@ int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
 int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
 int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream);
 
+/* Several networks of the SAME hidden width over the SAME points in one launch (the heads of a SplatFields step: reference
+ * utils/time_utils.py:466-503 evaluates five GeneralMLPs on one input): net y of `nets` is an op list in the format of
+ * sr_mlp_chain, the grid is (ceil(n_points / 128), n_nets) and workgroup (x, y) does for its 128 points exactly what
+ * sr_mlp_chain(n_points, hidden_tiles, nets[y].n_ops, nets[y].ops, ...) does for them -- per point and op the same arithmetic in
+ * the same order, so every stored value is bit-identical to n_nets separate calls.  What changes is the schedule: the
+ * workgroups of net y + 1 start in the tail of net y's last round of resident workgroups.  Nets may differ in depth, skips and
+ * output tiles.  At most SR_MLP_GROUP_MAX_NETS nets and SR_MLP_GROUP_MAX_OPS ops in total (the table is a kernel argument:
+ * < 4 KB); every op is validated as by sr_mlp_chain.  n_points == 0 or n_nets == 0: nothing is launched, success.
+ * sr_mlp_chain_group_bf16: the same for sr_mlp_chain_bf16. */
+#define SR_MLP_GROUP_MAX_NETS 8
+#define SR_MLP_GROUP_MAX_OPS 40
+typedef struct SrMlpNet {
+    const SrMlpOp* ops;
+    int n_ops;
+} SrMlpNet;
+int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream);
+int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream);
+
 /* Weight and bias gradients of the layers of a fused MLP: for every job
  *   dw[m * dw_row + dw_col0 + c] = sum over points p of dz[p * dz_row + m] * x[p * x_row + c],   m < job.m, c < job.k
  *   db[m]                        = sum over points p of dz[p * dz_row + m]                       (when db is set)
@@ -583,6 +601,46 @@ int sr_mlp_input_backward(int n_points, int multires, int n_features, int row, c
  * out_features <= c < row -- the padded matrix the backward chain's first op and the last layer's weight gradient read. */
 int sr_mlp_top_gradient(int n_points, int out_features, int row, const float* y, const float* dL_dy, float negative_slope, float* g,
                         void* hip_stream);
+
+/* The same three steps for ALL heads of a step in one launch each (job tables; <= SR_MLP_GROUP_MAX_HEADS heads), around
+ * sr_mlp_chain_group.  Pointwise arithmetic is in double with one rounding per stored value; no atomics, no host wait, 64-bit
+ * row offsets, bit-identical from run to run.  n_points == 0 or n_heads == 0: nothing is launched, success.
+ *   sr_mlp_group_input_forward   x0 of every head (its own `multires` and `row`, layout of sr_mlp_input_forward) from one
+ *                                xyz / features / time.
+ *   sr_mlp_group_input_backward  dL_dxyz [N, 3] and dL_dfeatures [N, n_features] (either may be NULL), WRITTEN once: the sum over
+ *                                the heads, in table order, of what sr_mlp_input_backward computes from each head's dL_dx0.
+ *   sr_mlp_group_output          out = act(y) per head: SR_MLP_OUT_SIGMOID 1 / (1 + exp(-y)), SR_MLP_OUT_NORMALIZE
+ *                                y / max(|y|, 1e-12) over the row (SR_MLP_OUT_NONE is a copy; a caller may leave such a head out).
+ *   sr_mlp_group_top_gradient    g [N, row] = dL_dout o act'(.) o leaky'(y), zero-padded to `row` (the matrix sr_mlp_top_gradient
+ *                                writes, with the output activation's backward folded in): sigmoid s (1 - s), s = sigmoid(y);
+ *                                normalize (n = |y|, u = y / max(n, 1e-12)): (n > 1e-12 ? d - u (d . u) : d) / max(n, 1e-12);
+ *                                a head with dL_dout == NULL gets g = 0. */
+#define SR_MLP_GROUP_MAX_HEADS 8
+#define SR_MLP_OUT_NONE 0
+#define SR_MLP_OUT_SIGMOID 1
+#define SR_MLP_OUT_NORMALIZE 2
+typedef struct SrMlpHeadInput {
+    float* x0;                 /* forward: [N, row], 16-byte aligned */
+    const float* dL_dx0;       /* backward: [N, row] */
+    int multires;              /* 0 .. 16 */
+    int row;                   /* multiple of 4, >= the width of the head's input */
+} SrMlpHeadInput;
+typedef struct SrMlpHeadOutput {
+    const float* y;            /* [N, out_features]: the chain's output */
+    float* out;                /* sr_mlp_group_output: [N, out_features] */
+    const float* dL_dout;      /* sr_mlp_group_top_gradient: [N, out_features] or NULL (no gradient reached this head) */
+    float* g;                  /* sr_mlp_group_top_gradient: [N, row], 16-byte aligned */
+    int out_features;          /* 1 .. 128 */
+    int row;                   /* multiple of 4, >= out_features */
+    int activation;            /* SR_MLP_OUT_* */
+    int reserved;
+} SrMlpHeadOutput;
+int sr_mlp_group_input_forward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, int time_multires, const float* xyz,
+                               const float* features, const float* time, void* hip_stream);
+int sr_mlp_group_input_backward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, const float* xyz, float* dL_dxyz,
+                                float* dL_dfeatures, void* hip_stream);
+int sr_mlp_group_output(int n_points, int n_heads, const SrMlpHeadOutput* heads, void* hip_stream);
+int sr_mlp_group_top_gradient(int n_points, int n_heads, const SrMlpHeadOutput* heads, float negative_slope, void* hip_stream);
 
 /* ResField weights of the current frame for all layers of one network in one launch (reference utils/resfields.py:185,229,
  * 294-300,378-405 in the configuration GeneralMLP builds -- compression 'vm', mode 'lookup', fuse 'add'):

@@ -43,6 +43,19 @@ class SrMlpOp(C.Structure):
                 ("keep_state", C.c_int)]
 
 
+class SrMlpNet(C.Structure):
+    _fields_ = [("ops", C.POINTER(SrMlpOp)), ("n_ops", C.c_int)]
+
+
+class SrMlpHeadInput(C.Structure):
+    _fields_ = [("x0", C.c_void_p), ("dL_dx0", C.c_void_p), ("multires", C.c_int), ("row", C.c_int)]
+
+
+class SrMlpHeadOutput(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("out", C.c_void_p), ("dL_dout", C.c_void_p), ("g", C.c_void_p), ("out_features", C.c_int),
+                ("row", C.c_int), ("activation", C.c_int), ("reserved", C.c_int)]
+
+
 class SrMlpPackJob(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias_src", C.c_void_p), ("dst", C.c_void_p), ("bias_dst", C.c_void_p), ("ld", C.c_int),
                 ("transposed", C.c_int), ("row0", C.c_int), ("n_rows", C.c_int), ("n_mem", C.c_int), ("mem_pad", C.c_int),
@@ -101,6 +114,8 @@ MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatrast
 ADAM_MAX_TENSORS = 32                                        # include/splatraster.h: SR_ADAM_MAX_TENSORS
 QUANT_NONE, QUANT_PNG, QUANT_TO8B = 0, 1, 2                     # include/splatraster.h: SR_QUANT_*
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
+MLP_GROUP_MAX_NETS, MLP_GROUP_MAX_OPS, MLP_GROUP_MAX_HEADS = 8, 40, 8      # include/splatraster.h: SR_MLP_GROUP_*
+MLP_OUT_NONE, MLP_OUT_SIGMOID, MLP_OUT_NORMALIZE = 0, 1, 2                 # include/splatraster.h: SR_MLP_OUT_*
 
 
 # every symbol include/splatraster.h declares: name -> (restype, argtypes)
@@ -185,6 +200,13 @@ SYMBOLS = {
     "sr_mlp_chain": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpOp), C.c_float, C.c_void_p]),
     "sr_mlp_pack_bf16": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
     "sr_mlp_chain_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpOp), C.c_float, C.c_void_p]),
+    "sr_mlp_chain_group": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpNet), C.c_float, C.c_void_p]),
+    "sr_mlp_chain_group_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpNet), C.c_float, C.c_void_p]),
+    "sr_mlp_group_input_forward": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadInput), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "sr_mlp_group_input_backward": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadInput), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_mlp_group_output": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadOutput), C.c_void_p]),
+    "sr_mlp_group_top_gradient": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadOutput), C.c_float, C.c_void_p]),
     "sr_mlp_input_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_mlp_top_gradient": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "sr_mlp_input_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

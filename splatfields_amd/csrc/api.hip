@@ -932,6 +932,48 @@ int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* 
     return mlp_chain_entry("sr_mlp_chain_bf16", true, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
 }
 
+// `empty`: the call was valid and launched nothing (no device is needed for that)
+static int mlp_group_entry(const char* name, const char* why, const char* kernel, bool empty) {
+    if (why) return fail(std::string(name) + ": " + why);
+    if (empty) return 0;
+    return check_hip(hipGetLastError(), kernel);
+}
+
+int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_chain_group", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, false,
+                                                                            static_cast<hipStream_t>(hip_stream)), "mlp_chain_group", n_points == 0 || n_nets == 0);
+}
+
+int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_chain_group_bf16", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, true,
+                                                                                 static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16", n_points == 0 || n_nets == 0);
+}
+
+int sr_mlp_group_input_forward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, int time_multires, const float* xyz,
+                               const float* features, const float* time, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_input_forward", sr::launch_mlp_group_input_forward(n_points, n_heads, heads, n_features, time_multires, xyz,
+                           features, time, static_cast<hipStream_t>(hip_stream)), "mlp_group_input_forward", n_points == 0 || n_heads == 0);
+}
+
+int sr_mlp_group_input_backward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, const float* xyz, float* dL_dxyz,
+                                float* dL_dfeatures, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_input_backward", sr::launch_mlp_group_input_backward(n_points, n_heads, heads, n_features, xyz, dL_dxyz,
+                           dL_dfeatures, static_cast<hipStream_t>(hip_stream)), "mlp_group_input_backward", n_points == 0 || n_heads == 0 || (!dL_dxyz && !dL_dfeatures));
+}
+
+int sr_mlp_group_output(int n_points, int n_heads, const SrMlpHeadOutput* heads, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_output", sr::launch_mlp_group_output(n_points, n_heads, heads, static_cast<hipStream_t>(hip_stream)),
+                           "mlp_group_output", n_points == 0 || n_heads == 0);
+}
+
+int sr_mlp_group_top_gradient(int n_points, int n_heads, const SrMlpHeadOutput* heads, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_group_top_gradient: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_group_top_gradient", sr::launch_mlp_group_top_gradient(n_points, n_heads, heads, negative_slope,
+                           static_cast<hipStream_t>(hip_stream)), "mlp_group_top_gradient", n_points == 0 || n_heads == 0);
+}
+
 int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
     return mlp_pack_entry("sr_mlp_pack", false, n_jobs, jobs, hip_stream);
 }

@@ -70,6 +70,14 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
 int launch_mlp_input_forward(int N, int L, int F, int TL, int row, const float* xyz, const float* feat, const float* time, float* x0, hipStream_t st);
 int launch_mlp_top_gradient(int N, int out, int row, const float* y, const float* dy, float slope, float* G, hipStream_t st);
 int launch_mlp_input_backward(int N, int L, int F, int row, const float* xyz, const float* g, float* d_xyz, float* d_feat, hipStream_t st);
+// the heads of a step as one group (sr_mlp_chain_group, sr_mlp_group_*): nullptr, or why the call is refused (nothing launched)
+const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float slope, bool bf16, hipStream_t st);
+const char* launch_mlp_group_input_forward(int N, int n_heads, const SrMlpHeadInput* heads, int F, int TL, const float* xyz, const float* feat,
+                                           const float* time, hipStream_t st);
+const char* launch_mlp_group_input_backward(int N, int n_heads, const SrMlpHeadInput* heads, int F, const float* xyz, float* d_xyz, float* d_feat,
+                                            hipStream_t st);
+const char* launch_mlp_group_output(int N, int n_heads, const SrMlpHeadOutput* heads, hipStream_t st);
+const char* launch_mlp_group_top_gradient(int N, int n_heads, const SrMlpHeadOutput* heads, float slope, hipStream_t st);
 int launch_resfield_compose(int n_jobs, const SrResFieldJob* jobs, const long long* frame, hipStream_t st);
 size_t resfield_backward_workspace(int n_jobs, const SrResFieldJob* jobs);
 int launch_resfield_backward(int n_jobs, const SrResFieldJob* jobs, const long long* frame, void* workspace, size_t workspace_bytes, hipStream_t st);

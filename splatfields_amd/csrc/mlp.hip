@@ -117,9 +117,11 @@ __device__ __forceinline__ void mlp_epilogue_plain(const f32x4 (&acc)[2][HT], f3
     }
 }
 
+// The chain itself, for one workgroup of 128 points and one op table: the body of k_mlp_chain (one network per launch) and of
+// k_mlp_chain_group (blockIdx.y picks the network).  `ops` points into the kernel argument; s_w: two chunks of a packed matrix,
+// [mt][tl][lane].  Every barrier below is reached by the whole workgroup: the op table is the workgroup's own.
 template <int HT>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_WAVES8 : 3, HT == 8 ? SR_MLP_WAVES8 : 3))) k_mlp_chain(const MlpK net, int n_points, float slope) {
-    __shared__ float4 s_w[2][HT * 2 * 64];   // two chunks of a packed matrix: [mt][tl][lane]
+__device__ __forceinline__ void mlp_chain_body(const SrMlpOp* ops, const int n_ops, float4 (&s_w)[2][HT * 2 * 64], int n_points, float slope) {
     const int wave = wave_id(), lane = lane_id();
     const int k = lane >> 4, n = lane & 15;
     const int p0 = (blockIdx.x * 4 + wave) * 32;              // first point of this wavefront
@@ -135,8 +137,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
         for (int t = 0; t < HT; ++t) prev[nt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     int buf = 0;
-    for (int l = 0; l < net.n_ops; ++l) {
-        const SrMlpOp L = net.op[l];
+    for (int l = 0; l < n_ops; ++l) {
+        const SrMlpOp L = ops[l];
         const float4* w4 = reinterpret_cast<const float4*>(L.w_packed);
         const int chunk_f4 = L.out_tiles * 128;                // float4 per chunk: mt x 2 x 64
         const int n_chunks = (L.mem_tiles + L.reg_tiles) / 2;
@@ -256,6 +258,25 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
     }
 }
 
+template <int HT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_WAVES8 : 3, HT == 8 ? SR_MLP_WAVES8 : 3))) k_mlp_chain(const MlpK net, int n_points, float slope) {
+    __shared__ float4 s_w[2][HT * 2 * 64];
+    mlp_chain_body<HT>(net.op, net.n_ops, s_w, n_points, slope);
+}
+
+// The networks of one group in one grid: workgroup (x, y) carries points 128 x .. 128 x + 127 through net y's ops
+// (op[first[y]] .. op[first[y + 1]] - 1).  The nets differ in depth, skips and output tiles; a workgroup belongs to one net, so
+// its barriers stay uniform, and the workgroups of net y + 1 fill the tail of net y's last round of resident workgroups.
+struct MlpGroupK { int n_nets; int first[SR_MLP_GROUP_MAX_NETS + 1]; SrMlpOp op[SR_MLP_GROUP_MAX_OPS]; };
+static_assert(sizeof(MlpGroupK) + 2 * sizeof(int) < 4096, "the op table of a group travels as a kernel argument: 4 KB");
+
+template <int HT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_WAVES8 : 3, HT == 8 ? SR_MLP_WAVES8 : 3))) k_mlp_chain_group(const MlpGroupK grp, int n_points, float slope) {
+    __shared__ float4 s_w[2][HT * 2 * 64];
+    const int f0 = grp.first[blockIdx.y];
+    mlp_chain_body<HT>(grp.op + f0, grp.first[blockIdx.y + 1] - f0, s_w, n_points, slope);
+}
+
 // ---- the same chains with bf16 matrix operands (opt-in: sr_mlp_chain_bf16) ------------------------------------------------
 // acc = bias + bf(W) . bf(x): both MFMA operands are rounded to bfloat16 (round to nearest even, v_cvt_pk_bf16_f32), products and
 // accumulation stay fp32 inside `v_mfma_f32_16x16x32_bf16`, and everything outside the MFMA is the fp32 kernel's: the bias as
@@ -294,9 +315,9 @@ __device__ __forceinline__ void mlp_chunk_bf16(f32x4 (&acc)[2][HT], const bf16x8
     }
 }
 
+// body of k_mlp_chain_bf16 and k_mlp_chain_group_bf16 (see mlp_chain_body); s_w: two chunks of a packed matrix, [mt][lane]
 template <int HT>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_BF16_WAVES8 : 3, HT == 8 ? SR_MLP_BF16_WAVES8 : 3))) k_mlp_chain_bf16(const MlpK net, int n_points, float slope) {
-    __shared__ bf16x8 s_w[2][HT * 64];       // two chunks of a packed matrix: [mt][lane]
+__device__ __forceinline__ void mlp_chain_body_bf16(const SrMlpOp* ops, const int n_ops, bf16x8 (&s_w)[2][HT * 64], int n_points, float slope) {
     const int wave = wave_id(), lane = lane_id();
     const int k = lane >> 4, n = lane & 15;
     const int p0 = (blockIdx.x * 4 + wave) * 32;              // first point of this wavefront
@@ -312,8 +333,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
         for (int t = 0; t < HT; ++t) prev[nt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     int buf = 0;
-    for (int l = 0; l < net.n_ops; ++l) {
-        const SrMlpOp L = net.op[l];
+    for (int l = 0; l < n_ops; ++l) {
+        const SrMlpOp L = ops[l];
         const bf16x8* w8 = reinterpret_cast<const bf16x8*>(L.w_packed);
         const int chunk_v = L.out_tiles * 64;                  // 16-byte vectors per chunk: mt x 64
         const int n_chunks = (L.mem_tiles + L.reg_tiles) / 2;
@@ -418,6 +439,19 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
             if (L.sign_store && pvalid[nt]) L.sign_store[(size_t)(p0 + 16 * nt + n) * 4 + k] = signs;
         }
     }
+}
+
+template <int HT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_BF16_WAVES8 : 3, HT == 8 ? SR_MLP_BF16_WAVES8 : 3))) k_mlp_chain_bf16(const MlpK net, int n_points, float slope) {
+    __shared__ bf16x8 s_w[2][HT * 64];
+    mlp_chain_body_bf16<HT>(net.op, net.n_ops, s_w, n_points, slope);
+}
+
+template <int HT>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT == 8 ? SR_MLP_BF16_WAVES8 : 3, HT == 8 ? SR_MLP_BF16_WAVES8 : 3))) k_mlp_chain_group_bf16(const MlpGroupK grp, int n_points, float slope) {
+    __shared__ bf16x8 s_w[2][HT * 64];
+    const int f0 = grp.first[blockIdx.y];
+    mlp_chain_body_bf16<HT>(grp.op + f0, grp.first[blockIdx.y + 1] - f0, s_w, n_points, slope);
 }
 
 struct MlpPackK { SrMlpPackJob job[SR_MLP_MAX_PACK_JOBS]; };
@@ -665,21 +699,26 @@ int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, bool bf16, hipStream_t
     return 0;
 }
 
+// what sr_mlp_chain requires of one op (shared by the single-net and the group launch)
+static bool mlp_op_ok(const SrMlpOp& s, int hidden_tiles) {
+    if (s.out_tiles < 1 || s.out_tiles > hidden_tiles || s.mem_tiles < 0 || s.reg_tiles < 0 || s.reg_tiles > hidden_tiles ||
+        (s.mem_tiles & 1) || (s.reg_tiles & 1) || s.mem_tiles + s.reg_tiles < 2 || !s.w_packed ||
+        (reinterpret_cast<uintptr_t>(s.w_packed) & 15u) || (reinterpret_cast<uintptr_t>(s.bias) & 15u)) return false;
+    if (s.mem_tiles > 0 && (!s.src || s.mem_tiles * 16 > s.src_row || (s.src_row & 3) || (reinterpret_cast<uintptr_t>(s.src) & 15u))) return false;
+    if (s.epilogue != SR_MLP_NONE && s.epilogue != SR_MLP_LEAKY && s.epilogue != SR_MLP_MASK) return false;
+    if (s.epilogue == SR_MLP_MASK && !s.mask_bits && (!s.mask || s.out_tiles * 16 > s.mask_row || (s.mask_row & 3) || (reinterpret_cast<uintptr_t>(s.mask) & 15u))) return false;
+    if ((reinterpret_cast<uintptr_t>(s.mask_bits) & 3u) || (reinterpret_cast<uintptr_t>(s.sign_store) & 3u)) return false;
+    if (s.store && (s.store_channels < 1 || s.store_channels > s.store_row || s.store_channels > 16 * s.out_tiles)) return false;
+    return true;
+}
+
 int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, bool bf16, hipStream_t st) {
     if (n_ops < 1 || n_ops > kMlpMaxOps) return 1;
     MlpK net;
     net.n_ops = n_ops;
     for (int l = 0; l < n_ops; ++l) {
-        const SrMlpOp& s = ops[l];
-        if (s.out_tiles < 1 || s.out_tiles > hidden_tiles || s.mem_tiles < 0 || s.reg_tiles < 0 || s.reg_tiles > hidden_tiles ||
-            (s.mem_tiles & 1) || (s.reg_tiles & 1) || s.mem_tiles + s.reg_tiles < 2 || !s.w_packed ||
-            (reinterpret_cast<uintptr_t>(s.w_packed) & 15u) || (reinterpret_cast<uintptr_t>(s.bias) & 15u)) return 1;
-        if (s.mem_tiles > 0 && (!s.src || s.mem_tiles * 16 > s.src_row || (s.src_row & 3) || (reinterpret_cast<uintptr_t>(s.src) & 15u))) return 1;
-        if (s.epilogue != SR_MLP_NONE && s.epilogue != SR_MLP_LEAKY && s.epilogue != SR_MLP_MASK) return 1;
-        if (s.epilogue == SR_MLP_MASK && !s.mask_bits && (!s.mask || s.out_tiles * 16 > s.mask_row || (s.mask_row & 3) || (reinterpret_cast<uintptr_t>(s.mask) & 15u))) return 1;
-        if ((reinterpret_cast<uintptr_t>(s.mask_bits) & 3u) || (reinterpret_cast<uintptr_t>(s.sign_store) & 3u)) return 1;
-        if (s.store && (s.store_channels < 1 || s.store_channels > s.store_row || s.store_channels > 16 * s.out_tiles)) return 1;
-        net.op[l] = s;
+        if (!mlp_op_ok(ops[l], hidden_tiles)) return 1;
+        net.op[l] = ops[l];
     }
     if (n_points <= 0) return 0;
     const int blocks = (n_points + 127) / 128;
@@ -693,6 +732,38 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
     else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
     else return 1;
     return 0;
+}
+
+// -> nullptr, or why the group is refused (nothing is launched then)
+const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float slope, bool bf16, hipStream_t st) {
+    if (n_points < 0) return "n_points must not be negative";
+    if (hidden_tiles != 4 && hidden_tiles != 8) return "hidden_tiles must be 4 or 8, the same for all nets of a group";
+    if (n_nets < 0 || n_nets > SR_MLP_GROUP_MAX_NETS) return "between 0 and SR_MLP_GROUP_MAX_NETS nets per group";
+    if (n_nets > 0 && !nets) return "null net table";
+    MlpGroupK grp;
+    grp.n_nets = n_nets;
+    int total = 0;
+    for (int y = 0; y < n_nets; ++y) {
+        if (!nets[y].ops || nets[y].n_ops < 1) return "every net needs at least one op";
+        if (nets[y].n_ops > SR_MLP_GROUP_MAX_OPS - total) return "more than SR_MLP_GROUP_MAX_OPS ops in one group";
+        grp.first[y] = total;
+        for (int l = 0; l < nets[y].n_ops; ++l) {
+            if (!mlp_op_ok(nets[y].ops[l], hidden_tiles))
+                return "unsupported op (tile counts within hidden_tiles, even input tile counts, 16-byte aligned rows wide enough for the tiles read)";
+            grp.op[total++] = nets[y].ops[l];
+        }
+    }
+    for (int y = n_nets; y <= SR_MLP_GROUP_MAX_NETS; ++y) grp.first[y] = total;
+    if (n_points == 0 || n_nets == 0) return nullptr;
+    const dim3 grid((n_points + 127) / 128, n_nets);
+    if (bf16) {
+        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group_bf16<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+        else hipLaunchKernelGGL((k_mlp_chain_group_bf16<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+        return nullptr;
+    }
+    if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+    else hipLaunchKernelGGL((k_mlp_chain_group<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+    return nullptr;
 }
 
 }  // namespace sr
@@ -952,6 +1023,270 @@ int launch_mlp_input_backward(int N, int L, int F, int row, const float* xyz, co
     const long long threads = (long long)N * (1 + (F + 3) / 4);
     hipLaunchKernelGGL(k_mlp_input_backward, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, N, L, F, row, xyz, g, d_xyz, d_feat);
     return 0;
+}
+
+// ---- the same steps for all heads of a step (sr_mlp_group_*): one launch each, job tables as kernel arguments -----------------------
+// The five head networks of a SplatFields step read the same (xyz, features, time): their input matrices, output activations, top
+// gradients and the sum of their input gradients are one launch each instead of one (or, for the activations and the sum,
+// several PyTorch kernels) per head.  Arithmetic in double, one rounding per stored value; a thread owns what it stores.
+struct GroupInK {
+    int n_heads, N, F, TL, q_total, l_max;
+    int qfirst[SR_MLP_GROUP_MAX_HEADS + 1];      // first float4 column of head h in a point's run of q_total columns
+    SrMlpHeadInput head[SR_MLP_GROUP_MAX_HEADS];
+    const float* xyz; const float* feat; const float* time;
+    float* d_xyz; float* d_feat;
+};
+struct GroupOutK {
+    int n_heads, N, q_total;
+    float slope;
+    int qfirst[SR_MLP_GROUP_MAX_HEADS + 1];
+    SrMlpHeadOutput head[SR_MLP_GROUP_MAX_HEADS];
+};
+
+__global__ void __launch_bounds__(kBlock) k_mlp_group_input_forward(const GroupInK P) {
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (long long)P.N * P.q_total) return;
+    const long long p = t / P.q_total;
+    const int q = (int)(t - p * P.q_total);
+    int h = 0;
+    while (h + 1 < P.n_heads && q >= P.qfirst[h + 1]) ++h;
+    const SrMlpHeadInput H = P.head[h];
+    const int L = H.multires, F = P.F, c0 = 4 * (q - P.qfirst[h]);
+    const double x[3] = {(double)P.xyz[3 * (size_t)p], (double)P.xyz[3 * (size_t)p + 1], (double)P.xyz[3 * (size_t)p + 2]};
+    // sin / cos of 2^j a come from ONE sincos per axis and j angle doublings in double (s <- 2 s c, c <- 1 - 2 s^2): a doubling
+    // costs three operations where a sin or cos of doubles costs a hundred, and its error, about 2^j ulps of double, stays ten
+    // binades below float32's rounding for j < 8; from octave 8 on the chain is restarted with a sincos of its own.
+    const int t0 = 3 + 6 * L + F;                       // first column of the time encoding
+    double sx[3] = {0.0, 0.0, 0.0}, cx[3] = {1.0, 1.0, 1.0}, st = 0.0, ct = 1.0;
+    if (c0 < 3 + 6 * L && c0 + 3 >= 3) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) sincos(x[r], &sx[r], &cx[r]);
+    }
+    const double tv = P.time ? (double)P.time[p] : 0.0;
+    if (P.time && c0 < t0 + 1 + 2 * P.TL && c0 + 3 > t0) sincos(tv, &st, &ct);
+    auto octave = [](double a, double s, double c, int j, double* so, double* co) {
+        if (j >= 8) { sincos(a * (double)(1 << (j & ~7)), &s, &c); j &= 7; }
+        for (int d = 0; d < j; ++d) { const double s2 = 2.0 * s * c; c = 1.0 - 2.0 * s * s; s = s2; }
+        *so = s; *co = c;
+    };
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + i;
+        float o = 0.0f;
+        if (c < 3) o = (float)x[c];
+        else if (c < 3 + 6 * L) {
+            const int k = c - 3, j = k / 6, r6 = k - 6 * j, r = r6 < 3 ? r6 : r6 - 3;
+            double s, cs;
+            octave(r == 0 ? x[0] : r == 1 ? x[1] : x[2], r == 0 ? sx[0] : r == 1 ? sx[1] : sx[2], r == 0 ? cx[0] : r == 1 ? cx[1] : cx[2], j, &s, &cs);
+            o = (float)(r6 < 3 ? s : cs);
+        } else if (c < t0) o = P.feat[(size_t)p * F + (c - 3 - 6 * L)];
+        else if (P.time && c < t0 + 1 + 2 * P.TL) {
+            const int m = c - t0;
+            if (m == 0) o = (float)tv;
+            else { double s, cs; octave(tv, st, ct, (m - 1) >> 1, &s, &cs); o = (float)(((m - 1) & 1) ? cs : s); }
+        }
+        v[i] = o;
+    }
+    *reinterpret_cast<float4*>(H.x0 + (size_t)p * H.row + c0) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// d_xyz[p] = sum over heads h (table order) of g_h[0:3], then for every frequency j the heads' 2^j (cos(2^j x) g_h,sin_j - sin(2^j x) g_h,cos_j)
+// in table order (one sincos per frequency and axis for all heads); d_feat[p][i] = sum over heads of g_h[3 + 6 L_h + i]
+__global__ void __launch_bounds__(kBlock) k_mlp_group_input_backward(const GroupInK P) {
+    const int F = P.F, per = 1 + (F + 3) / 4;
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (long long)P.N * per) return;
+    const long long p = t / per;
+    const int part = (int)(t - p * per);
+    if (part == 0) {
+        if (!P.d_xyz) return;
+        double d[3] = {0.0, 0.0, 0.0};
+        for (int h = 0; h < P.n_heads; ++h) {
+            const float* gp = P.head[h].dL_dx0 + (size_t)p * P.head[h].row;
+            d[0] += (double)gp[0]; d[1] += (double)gp[1]; d[2] += (double)gp[2];
+        }
+        const double x[3] = {(double)P.xyz[3 * (size_t)p], (double)P.xyz[3 * (size_t)p + 1], (double)P.xyz[3 * (size_t)p + 2]};
+        double sn3[3], cs3[3];
+        for (int j = 0; j < P.l_max; ++j) {
+            const double f = (double)(1 << j);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                // one sincos per axis and eight octaves, angle doublings between (see k_mlp_group_input_forward)
+                if ((j & 7) == 0) sincos(x[r] * f, &sn3[r], &cs3[r]);
+                else { const double s2 = 2.0 * sn3[r] * cs3[r]; cs3[r] = 1.0 - 2.0 * sn3[r] * sn3[r]; sn3[r] = s2; }
+                const double sn = sn3[r], cs = cs3[r];
+                for (int h = 0; h < P.n_heads; ++h) {
+                    if (j >= P.head[h].multires) continue;
+                    const float* gp = P.head[h].dL_dx0 + (size_t)p * P.head[h].row;
+                    d[r] += f * (cs * (double)gp[3 + 6 * j + r] - sn * (double)gp[3 + 6 * j + 3 + r]);
+                }
+            }
+        }
+        P.d_xyz[3 * (size_t)p] = (float)d[0]; P.d_xyz[3 * (size_t)p + 1] = (float)d[1]; P.d_xyz[3 * (size_t)p + 2] = (float)d[2];
+    } else if (P.d_feat) {
+        const int f0 = 4 * (part - 1);
+        for (int i = f0; i < min(f0 + 4, F); ++i) {
+            double s = 0.0;
+            for (int h = 0; h < P.n_heads; ++h) s += (double)P.head[h].dL_dx0[(size_t)p * P.head[h].row + 3 + 6 * P.head[h].multires + i];
+            P.d_feat[(size_t)p * F + i] = (float)s;
+        }
+    }
+}
+
+// one thread per (point, head): the head's whole output row
+__global__ void __launch_bounds__(kBlock) k_mlp_group_output(const GroupOutK P) {
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (long long)P.N * P.n_heads) return;
+    const long long p = t / P.n_heads;
+    const SrMlpHeadOutput H = P.head[(int)(t - p * P.n_heads)];
+    const float* y = H.y + (size_t)p * H.out_features;
+    float* out = H.out + (size_t)p * H.out_features;
+    if (H.activation == SR_MLP_OUT_SIGMOID) {
+        for (int c = 0; c < H.out_features; ++c) out[c] = (float)(1.0 / (1.0 + exp(-(double)y[c])));
+    } else if (H.activation == SR_MLP_OUT_NORMALIZE) {
+        double n2 = 0.0;
+        for (int c = 0; c < H.out_features; ++c) n2 += (double)y[c] * (double)y[c];
+        const double n = fmax(sqrt(n2), 1e-12);
+        for (int c = 0; c < H.out_features; ++c) out[c] = (float)((double)y[c] / n);
+    } else {
+        for (int c = 0; c < H.out_features; ++c) out[c] = y[c];
+    }
+}
+
+// one thread per (point, float4 of a head's padded row)
+__global__ void __launch_bounds__(kBlock) k_mlp_group_top_gradient(const GroupOutK P) {
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (long long)P.N * P.q_total) return;
+    const long long p = t / P.q_total;
+    const int q = (int)(t - p * P.q_total);
+    int h = 0;
+    while (h + 1 < P.n_heads && q >= P.qfirst[h + 1]) ++h;
+    const SrMlpHeadOutput H = P.head[h];
+    const int out = H.out_features, c0 = 4 * (q - P.qfirst[h]);
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (H.dL_dout && c0 < out) {
+        const float* y = H.y + (size_t)p * out;
+        const float* d = H.dL_dout + (size_t)p * out;
+        double n = 1.0, dot = 0.0;
+        bool above = true;
+        if (H.activation == SR_MLP_OUT_NORMALIZE) {
+            double n2 = 0.0;
+            for (int c = 0; c < out; ++c) n2 += (double)y[c] * (double)y[c];
+            const double raw = sqrt(n2);
+            above = raw > 1e-12;                  // below the clamp the norm is a constant: d (y / eps) = d / eps
+            n = fmax(raw, 1e-12);
+            for (int c = 0; c < out; ++c) dot += (double)d[c] * ((double)y[c] / n);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = c0 + i;
+            if (c >= out) continue;
+            const double yc = (double)y[c];
+            double g = (double)d[c];
+            if (H.activation == SR_MLP_OUT_SIGMOID) { const double s = 1.0 / (1.0 + exp(-yc)); g *= s * (1.0 - s); }
+            else if (H.activation == SR_MLP_OUT_NORMALIZE) g = (above ? g - (yc / n) * dot : g) / n;
+            v[i] = (float)(g * (y[c] > 0.f ? 1.0 : (double)P.slope));
+        }
+    }
+    *reinterpret_cast<float4*>(H.g + (size_t)p * H.row + c0) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+static const char* group_input_check(int N, int n_heads, const SrMlpHeadInput* heads, int F, int TL, bool time, bool backward) {
+    if (N < 0) return "n_points must not be negative";
+    if (n_heads < 0 || n_heads > SR_MLP_GROUP_MAX_HEADS) return "between 0 and SR_MLP_GROUP_MAX_HEADS heads";
+    if (n_heads > 0 && !heads) return "null head table";
+    if (F < 0) return "n_features must not be negative";
+    if (TL < 0 || TL > 16) return "time_multires must be in 0..16";
+    for (int h = 0; h < n_heads; ++h) {
+        const SrMlpHeadInput& s = heads[h];
+        if (s.multires < 0 || s.multires > 16) return "multires must be in 0..16";
+        if (s.row < 4 || (s.row & 3) || s.row < 3 + 6 * s.multires + F + (time ? 1 + 2 * TL : 0)) return "row must be a multiple of 4 that holds the head's input";
+        const float* ptr = backward ? s.dL_dx0 : s.x0;
+        if (!ptr) return "null pointer in the head table";
+        if (reinterpret_cast<uintptr_t>(ptr) & 15u) return "the heads' matrices must be 16-byte aligned";
+    }
+    return nullptr;
+}
+
+const char* launch_mlp_group_input_forward(int N, int n_heads, const SrMlpHeadInput* heads, int F, int TL, const float* xyz, const float* feat,
+                                           const float* time, hipStream_t st) {
+    if (const char* why = group_input_check(N, n_heads, heads, F, TL, time != nullptr, false)) return why;
+    if (N == 0 || n_heads == 0) return nullptr;
+    if (!xyz || (F > 0 && !feat)) return "null pointer (xyz, or features with n_features > 0)";
+    GroupInK P;
+    P.n_heads = n_heads; P.N = N; P.F = F; P.TL = TL; P.l_max = 0;
+    P.xyz = xyz; P.feat = feat; P.time = time; P.d_xyz = nullptr; P.d_feat = nullptr;
+    int q = 0;
+    for (int h = 0; h < n_heads; ++h) { P.head[h] = heads[h]; P.qfirst[h] = q; q += heads[h].row >> 2; }
+    for (int h = n_heads; h <= SR_MLP_GROUP_MAX_HEADS; ++h) P.qfirst[h] = q;
+    P.q_total = q;
+    const long long blocks = ((long long)N * q + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return "too many points for one launch";
+    hipLaunchKernelGGL(k_mlp_group_input_forward, dim3((unsigned)blocks), dim3(kBlock), 0, st, P);
+    return nullptr;
+}
+
+const char* launch_mlp_group_input_backward(int N, int n_heads, const SrMlpHeadInput* heads, int F, const float* xyz, float* d_xyz, float* d_feat,
+                                            hipStream_t st) {
+    if (const char* why = group_input_check(N, n_heads, heads, F, 0, false, true)) return why;
+    if (N == 0 || n_heads == 0 || (!d_xyz && !d_feat)) return nullptr;
+    if (!xyz) return "null pointer (xyz)";
+    GroupInK P;
+    P.n_heads = n_heads; P.N = N; P.F = F; P.TL = 0; P.l_max = 0; P.q_total = 0;
+    P.xyz = xyz; P.feat = nullptr; P.time = nullptr; P.d_xyz = d_xyz; P.d_feat = F > 0 ? d_feat : nullptr;
+    for (int h = 0; h < n_heads; ++h) { P.head[h] = heads[h]; P.qfirst[h] = 0; P.l_max = max(P.l_max, heads[h].multires); }
+    for (int h = n_heads; h <= SR_MLP_GROUP_MAX_HEADS; ++h) P.qfirst[h] = 0;
+    const long long blocks = ((long long)N * (1 + (F + 3) / 4) + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return "too many points for one launch";
+    hipLaunchKernelGGL(k_mlp_group_input_backward, dim3((unsigned)blocks), dim3(kBlock), 0, st, P);
+    return nullptr;
+}
+
+static const char* group_output_check(int N, int n_heads, const SrMlpHeadOutput* heads, bool top) {
+    if (N < 0) return "n_points must not be negative";
+    if (n_heads < 0 || n_heads > SR_MLP_GROUP_MAX_HEADS) return "between 0 and SR_MLP_GROUP_MAX_HEADS heads";
+    if (n_heads > 0 && !heads) return "null head table";
+    for (int h = 0; h < n_heads; ++h) {
+        const SrMlpHeadOutput& s = heads[h];
+        if (s.out_features < 1 || s.out_features > 128) return "out_features must be in 1..128";
+        if (s.activation != SR_MLP_OUT_NONE && s.activation != SR_MLP_OUT_SIGMOID && s.activation != SR_MLP_OUT_NORMALIZE) return "unknown output activation";
+        if (!s.y) return "null pointer in the head table";
+        if (top) {
+            if (s.row < 4 || (s.row & 3) || s.row < s.out_features) return "row must be a multiple of 4 and >= out_features";
+            if (!s.g) return "null pointer in the head table";
+            if (reinterpret_cast<uintptr_t>(s.g) & 15u) return "g must be 16-byte aligned";
+        } else if (!s.out) return "null pointer in the head table";
+        if ((reinterpret_cast<uintptr_t>(s.y) | reinterpret_cast<uintptr_t>(s.out) | reinterpret_cast<uintptr_t>(s.dL_dout)) & 3u) return "float arrays must be 4-byte aligned";
+    }
+    return nullptr;
+}
+
+const char* launch_mlp_group_output(int N, int n_heads, const SrMlpHeadOutput* heads, hipStream_t st) {
+    if (const char* why = group_output_check(N, n_heads, heads, false)) return why;
+    if (N == 0 || n_heads == 0) return nullptr;
+    GroupOutK P;
+    P.n_heads = n_heads; P.N = N; P.q_total = 0; P.slope = 0.0f;
+    for (int h = 0; h < n_heads; ++h) { P.head[h] = heads[h]; P.qfirst[h] = 0; }
+    for (int h = n_heads; h <= SR_MLP_GROUP_MAX_HEADS; ++h) P.qfirst[h] = 0;
+    const long long blocks = ((long long)N * n_heads + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_mlp_group_output, dim3((unsigned)blocks), dim3(kBlock), 0, st, P);
+    return nullptr;
+}
+
+const char* launch_mlp_group_top_gradient(int N, int n_heads, const SrMlpHeadOutput* heads, float slope, hipStream_t st) {
+    if (const char* why = group_output_check(N, n_heads, heads, true)) return why;
+    if (N == 0 || n_heads == 0) return nullptr;
+    GroupOutK P;
+    P.n_heads = n_heads; P.N = N; P.slope = slope;
+    int q = 0;
+    for (int h = 0; h < n_heads; ++h) { P.head[h] = heads[h]; P.qfirst[h] = q; q += heads[h].row >> 2; }
+    for (int h = n_heads; h <= SR_MLP_GROUP_MAX_HEADS; ++h) P.qfirst[h] = q;
+    P.q_total = q;
+    const long long blocks = ((long long)N * q + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return "too many points for one launch";
+    hipLaunchKernelGGL(k_mlp_group_top_gradient, dim3((unsigned)blocks), dim3(kBlock), 0, st, P);
+    return nullptr;
 }
 
 }  // namespace sr

@@ -230,7 +230,12 @@ class SplatFields(nn.Module):
         chains of every GeneralMLP built here.  `flow_head="torch" | "fused"` (a keyword, so it also arrives through
         `SplatFieldsModel`'s hyper_args): the path of the flow head, None = the process default (splatfields_amd.set_flow_head).
         `view_color="torch" | "fused"`, likewise: the path of the view-dependent colour head of `use_view_dep_rgb`
-        (splatfields_amd.set_view_color)."""
+        (splatfields_amd.set_view_color).  `heads="separate" | "grouped"`, likewise: how the step runs the networks behind
+        `mlp_deform` -- scale, opacity, rotation, rgb, flow, which all read (xyz_can, features, time).  "grouped" runs them through one
+        autograd function, the networks of one width in one launch per phase (splatfields_amd.set_heads; general_mlp.HeadGroup).  A
+        call whose inputs the grouped input kernel cannot take -- tensors that are not float32 on the device, a `t` that needs a
+        gradient or is not one value per point (the branch that builds the time embedding with PyTorch ops), no points -- runs the
+        separate path."""
         super().__init__()
         rank = kwargs.get("composition_rank", 0)
         self.n_frames = n_frames
@@ -300,6 +305,22 @@ class SplatFields(nn.Module):
             self.mlp_flow_head = FlowHead(W=self.mlp_flow.out_features, flow_model=kwargs.get("flow_model", "se3"),
                                           num_basis=kwargs.get("dct_basis", 4), n_frames=n_frames, path=kwargs.get("flow_head"))
 
+        from .fused_mlp import _checked_heads, resolve_heads
+        self.heads = None if kwargs.get("heads") is None else _checked_heads(kwargs["heads"])
+        self._head_group = None
+        if resolve_heads(self.heads) == "grouped":      # asked for here, or the process default: refuse now what can never run grouped
+            self._head_group = self._make_head_group()
+
+    def _make_head_group(self):
+        from .general_mlp import HeadGroup
+        if self.geo_model_disable_pts:
+            raise ValueError("SplatFields: heads='grouped' cannot run with geo_model_disable_pts=True (the geometry heads then read "
+                             "other inputs than the colour and flow heads)")
+        named = [("scales", self.mlp_scale), ("opacity", self.mlp_opacity), ("rotations", self.mlp_rotation), ("rgb", self.mlp_rgb)]
+        if self.n_frames > 0:
+            named.append(("flow", self.mlp_flow))
+        return HeadGroup(named, self.time_multires)
+
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """`nn.Module.load_state_dict`, plus one loud check: a reference default-config checkpoint holds the weights of its
         time-conditioned plane generators (`encoder.subs.*`, scene/tripFields.py:383-428).  The decoder-free sampler has no place
@@ -331,6 +352,10 @@ class SplatFields(nn.Module):
         parts = [f for f in (x_feat, t_feat) if f is not None]
         return torch.cat(parts, dim=-1) if parts else None
 
+    def _fuse_time(self, xyz_in, t) -> bool:
+        return self.n_frames > 0 and torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and not t.requires_grad and \
+            t.numel() == xyz_in.shape[0] and not self.geo_model_disable_pts
+
     def forward(self, xyz_in, t):
         out = {}
         time_step, frame_id = None, None
@@ -340,8 +365,7 @@ class SplatFields(nn.Module):
         # features of every network: [refined tri-plane features | time embedding] (extract_features).  With one float32 time per
         # point that takes no gradient, the time embedding is written by the networks' input kernel instead of ~15 small kernels
         # and a concatenation per step.
-        fuse_time = self.n_frames > 0 and torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and not t.requires_grad and \
-            t.numel() == xyz_in.shape[0] and not self.geo_model_disable_pts
+        fuse_time = self._fuse_time(xyz_in, t)
         if fuse_time:
             feat = self.mlp_refine_feat(self._encode(xyz_in, frame_id)) if self.feat_dim > 0 else None
             tk = dict(time=t.reshape(-1), time_multires=self.time_multires)
@@ -351,18 +375,27 @@ class SplatFields(nn.Module):
             xyz_can = torch.add(xyz_in, self.mlp_deform(xyz_in, feat, frame_id=frame_id, **tk), alpha=self.deform_weight)   # one kernel
         else:
             xyz_can = xyz_in
-        geo_xyz, geo_feat = (feat, None) if self.geo_model_disable_pts else (xyz_can, feat)
-        out["scales"] = self.mlp_scale(geo_xyz, geo_feat, frame_id=frame_id, **tk)
-        out["opacity"] = self.mlp_opacity(geo_xyz, geo_feat, frame_id=frame_id, **tk)
-        out["rotations"] = self.mlp_rotation(geo_xyz, geo_feat, frame_id=frame_id, **tk)
-        rgb = self.mlp_rgb(xyz_can, feat, frame_id=frame_id, **tk)
+        from .fused_mlp import grouped_inputs_ok, resolve_heads
+        grouped = None
+        if resolve_heads(self.heads) == "grouped" and (fuse_time or self.n_frames == 0) and grouped_inputs_ok(xyz_can, feat, tk.get("time")):
+            if self._head_group is None:       # the process default changed after construction
+                self._head_group = self._make_head_group()
+            grouped = self._head_group(xyz_can, feat, frame_id=frame_id, time=tk.get("time"))
+        if grouped is not None:
+            out["scales"], out["opacity"], out["rotations"], rgb = grouped["scales"], grouped["opacity"], grouped["rotations"], grouped["rgb"]
+        else:
+            geo_xyz, geo_feat = (feat, None) if self.geo_model_disable_pts else (xyz_can, feat)
+            out["scales"] = self.mlp_scale(geo_xyz, geo_feat, frame_id=frame_id, **tk)
+            out["opacity"] = self.mlp_opacity(geo_xyz, geo_feat, frame_id=frame_id, **tk)
+            out["rotations"] = self.mlp_rotation(geo_xyz, geo_feat, frame_id=frame_id, **tk)
+            rgb = self.mlp_rgb(xyz_can, feat, frame_id=frame_id, **tk)
         if self.use_view_dep_rgb:
             from .view_color import resolve_view_color
             out["rgb_fnc"] = ViewColor(self.mlp_rgb_viewdep, rgb, resolve_view_color(self.view_color))
         else:
             out["rgb"] = rgb
         if self.n_frames > 0:
-            flow_feat = self.mlp_flow(xyz_can, feat, frame_id=frame_id, **tk)
+            flow_feat = grouped["flow"] if grouped is not None else self.mlp_flow(xyz_can, feat, frame_id=frame_id, **tk)
             flow, means3D = self.mlp_flow_head(hidden=flow_feat, pts=xyz_can, time_step=time_step, frame_id=frame_id)
         else:
             flow, means3D = None, xyz_can

@@ -15,6 +15,11 @@ module-style wrapper.  No CPU path.
 chains on the bf16 MFMA: weights and the chains' inputs are rounded to bfloat16 where they enter a matrix product, products and
 sums, biases, the running state, the epilogues and everything stored stay fp32, and the weight gradients come from the fp32
 kernel on those stored values (include/splatraster.h: sr_mlp_chain_bf16).
+
+`fused_grouped_heads` (opt-in; `set_heads` / SPLATFIELDS_HEADS set the process default, "separate") evaluates several such networks
+that read the same points, features and time through one autograd function: the networks of one hidden width and precision in one
+chain launch per direction, the input matrices, output activations, top gradients and the summed input gradient of all of them in
+one launch each (include/splatraster.h: sr_mlp_chain_group, sr_mlp_group_*).
 """
 from __future__ import annotations
 
@@ -156,16 +161,13 @@ class _Plan:
         self.sizes.append((floats, 16 * job["out_tiles"] if with_bias else 0))
         self.ops.append(op)
 
-    def _freeze(self):
-        if len(self.jobs) > _lib.MLP_MAX_PACK_JOBS or len(self.ops) > _lib.MLP_MAX_OPS:
-            raise ValueError("network too deep for one fused chain")
-        n = len(self.jobs)
-        jobs = (_lib.SrMlpPackJob * n)()
-        ops = (_lib.SrMlpOp * n)()
-        binds, at = [], 0     # (struct, field, symbol, index, byte offset); `at`: bytes, every piece a multiple of 16
+    def _fill(self, jobs, ops, start: int, at: int):
+        """writes this plan's static fields into jobs[start:] / ops[start:] (its own arrays, or a group's: _GroupPlan) with its
+        packed matrices from byte `at` of the buffer on; -> (binds (struct, field, symbol, index, byte offset), next free byte)"""
+        binds = []            # `at`: bytes, every piece a multiple of 16
         wsize = 2 if self.bf16 else 4
         for j, (job, op, (wf, bf)) in enumerate(zip(self.jobs, self.ops, self.sizes)):
-            J, O = jobs[j], ops[j]
+            J, O = jobs[start + j], ops[start + j]
             J.ld, J.transposed, J.row0, J.n_rows = job["ld"], job["transposed"], job["row0"], job["n_rows"]
             J.n_mem, J.mem_pad, J.mem_col0 = job["n_mem"], job["mem_pad"], 0
             J.n_reg, J.reg_width, J.reg_col0 = job["n_reg"], job["reg_width"], job["reg_col0"]
@@ -184,6 +186,15 @@ class _Plan:
             for f in _OP_PTRS:
                 if op.get(f) is not None:
                     binds.append((O, f) + tuple(op[f]))
+        return binds, at
+
+    def _freeze(self):
+        if len(self.jobs) > _lib.MLP_MAX_PACK_JOBS or len(self.ops) > _lib.MLP_MAX_OPS:
+            raise ValueError("network too deep for one fused chain")
+        n = len(self.jobs)
+        jobs = (_lib.SrMlpPackJob * n)()
+        ops = (_lib.SrMlpOp * n)()
+        binds, at = self._fill(jobs, ops, 0, 0)
         self._arrays = (jobs, ops, binds, at)
 
     def run(self, lib, ptrs: dict, device, n_points: int, ht: int, slope: float, stream) -> torch.Tensor:
@@ -587,3 +598,327 @@ class FusedGeneralMLP:
 
     def __call__(self, h_in: torch.Tensor) -> torch.Tensor:
         return fused_general_mlp(h_in, self.weights, self.biases, negative_slope=self.slope, _shape=self.shape, precision=self.precision)
+
+
+# ---- the head networks of a step as groups (opt-in: SplatFields(heads="grouped"), set_heads, SPLATFIELDS_HEADS) -----------------
+# Several GeneralMLPs that read the same (xyz, features, time) run through ONE autograd function: one input kernel, one output
+# kernel, one top-gradient kernel and one input-backward kernel for all of them, and per group of nets of one hidden width and
+# precision one pack launch and one chain launch per direction (include/splatraster.h: sr_mlp_chain_group, sr_mlp_group_*; DESIGN.md
+# section 20).  Weight gradients stay one sr_mlp_weight_grad call per net.
+
+HEADS = ("separate", "grouped")
+OUT_ACTIVATIONS = {"none": _lib.MLP_OUT_NONE, "sigmoid": _lib.MLP_OUT_SIGMOID, "normalize": _lib.MLP_OUT_NORMALIZE}
+
+
+def _checked_heads(name) -> str:
+    if name not in HEADS:
+        raise ValueError(f"unknown heads mode {name!r}: expected one of {HEADS}")
+    return name
+
+
+# process default, read once: SPLATFIELDS_HEADS=grouped groups the heads of every SplatFields that does not name a mode itself
+_HEADS = _checked_heads(os.environ.get("SPLATFIELDS_HEADS") or "separate")
+
+
+def set_heads(name: str) -> str:
+    """Process default of how a SplatFields step runs its head networks: "separate" (one chain of launches per network) or
+    "grouped" (the networks of one width in one launch per phase).  Returns the previous setting."""
+    global _HEADS
+    prev, _HEADS = _HEADS, _checked_heads(name)
+    return prev
+
+
+def heads() -> str:
+    return _HEADS
+
+
+def resolve_heads(name: Optional[str]) -> str:
+    """`None` -> the process default, at call time."""
+    return _HEADS if name is None else _checked_heads(name)
+
+
+class HeadSpec:
+    """One network of a grouped step: its static shape, the frequencies of its positional encoding, its output activation
+    (a key of OUT_ACTIVATIONS) and the slope of its leaky ReLU."""
+
+    def __init__(self, name: str, shape: _Shape, multires: int, activation: str, slope: float):
+        if activation not in OUT_ACTIVATIONS:
+            raise ValueError(f"head {name!r}: the grouped path implements the output activations {tuple(OUT_ACTIVATIONS)}, not {activation!r}")
+        self.name, self.shape, self.multires, self.activation, self.slope = name, shape, int(max(multires, 0)), activation, float(slope)
+
+
+def net_op_count(shape: _Shape, precision: str = "fp32") -> int:
+    """ops of the longer of the net's two chains: what it takes of a group's table (forward and backward use the same groups)"""
+    return max(len(_forward_plan(shape, True, precision).ops), len(_backward_plan(shape, True, True, precision).ops))
+
+
+def partition_heads(specs: Sequence[HeadSpec], precisions: Sequence[str]) -> List[List[int]]:
+    """Indices of `specs`, grouped: one part per (hidden width, chain precision) in order of first appearance, a part cut where
+    the next net would exceed SR_MLP_GROUP_MAX_NETS nets or SR_MLP_GROUP_MAX_OPS ops (the table is a kernel argument)."""
+    parts: dict = {}
+    for i, (s, p) in enumerate(zip(specs, precisions)):
+        parts.setdefault((s.shape.hidden, _checked_precision(p)), []).append(i)
+    groups = []
+    for (_, precision), members in parts.items():
+        cur, ops = [], 0
+        for i in members:
+            k = net_op_count(specs[i].shape, precision)
+            if k > _lib.MLP_GROUP_MAX_OPS:
+                raise ValueError(f"head {specs[i].name!r}: {k} ops do not fit one group table ({_lib.MLP_GROUP_MAX_OPS})")
+            if cur and (len(cur) >= _lib.MLP_GROUP_MAX_NETS or ops + k > _lib.MLP_GROUP_MAX_OPS):
+                groups.append(cur)
+                cur, ops = [], 0
+            cur.append(i)
+            ops += k
+        groups.append(cur)
+    return groups
+
+
+class _GroupPlan:
+    """The plans of a group's nets as ONE pack job table and ONE op table (net after net, each net's entries exactly those of its
+    own _Plan) + the net table of sr_mlp_chain_group; built once, pointers patched per call like _Plan."""
+
+    def __init__(self, plans: Sequence[_Plan]):
+        self.plans = list(plans)
+        self.bf16 = self.plans[0].bf16
+        if any(p.bf16 != self.bf16 for p in self.plans):
+            raise ValueError("the nets of a group share one chain precision")
+        self._arrays = None
+        self._lock = threading.Lock()
+
+    def _freeze(self):
+        counts = [len(p.ops) for p in self.plans]
+        total = sum(counts)
+        if len(self.plans) > _lib.MLP_GROUP_MAX_NETS or total > _lib.MLP_GROUP_MAX_OPS:
+            raise ValueError("too many nets or ops for one group table")
+        jobs, ops, nets = (_lib.SrMlpPackJob * total)(), (_lib.SrMlpOp * total)(), (_lib.SrMlpNet * len(self.plans))()
+        binds, at, start = [], 0, 0
+        for y, (plan, cnt) in enumerate(zip(self.plans, counts)):
+            own, at = plan._fill(jobs, ops, start, at)
+            binds += [(obj, field, None if sym == "buf" else y, sym, idx, off) for obj, field, sym, idx, off in own]
+            nets[y].ops = C.cast(C.byref(ops, start * C.sizeof(_lib.SrMlpOp)), C.POINTER(_lib.SrMlpOp))
+            nets[y].n_ops = cnt
+            start += cnt
+        self._arrays = (jobs, ops, nets, binds, at)
+
+    def tables(self):
+        """(pack jobs, ops, nets, binds, buffer bytes): the frozen arrays"""
+        with self._lock:
+            if self._arrays is None:
+                self._freeze()
+            return self._arrays
+
+    def run(self, lib, ptrs_per_net: Sequence[dict], device, n_points: int, ht: int, slope: float, stream) -> torch.Tensor:
+        jobs, ops, nets, binds, total = self.tables()
+        with self._lock:      # the descriptor arrays are shared by every call with these shapes
+            buf = torch.empty(total // 4, dtype=torch.float32, device=device)
+            base = buf.data_ptr()
+            for obj, field, y, sym, idx, off in binds:
+                setattr(obj, field, (base if y is None else ptrs_per_net[y][sym][idx]) + off)
+            pack, chain = (lib.sr_mlp_pack_bf16, lib.sr_mlp_chain_group_bf16) if self.bf16 else (lib.sr_mlp_pack, lib.sr_mlp_chain_group)
+            step = _lib.MLP_MAX_PACK_JOBS
+            for lo in range(0, len(jobs), step):          # all nets' matrices: 32 jobs per pack launch
+                part = C.cast(C.byref(jobs, lo * C.sizeof(_lib.SrMlpPackJob)), C.POINTER(_lib.SrMlpPackJob))
+                _lib.check(pack(min(step, len(jobs) - lo), part, stream))
+            _lib.check(chain(n_points, ht, len(nets), nets, slope, stream))
+        return buf
+
+
+_GROUP_PLANS: dict = {}
+
+
+def _group_plan(kind: str, shapes: Sequence[_Shape], flag: bool, precision: str) -> _GroupPlan:
+    """kind "fwd": flag = save the activations; "bwd": flag = dL/dx0 is needed (leaky' always from the sign bits)"""
+    key = (kind, flag, precision, tuple(id(s) for s in shapes))
+    hit = _GROUP_PLANS.get(key)
+    if hit is None:
+        plans = [_forward_plan(s, flag, precision) if kind == "fwd" else _backward_plan(s, flag, True, precision) for s in shapes]
+        hit = _GROUP_PLANS[key] = (list(shapes), _GroupPlan(plans))      # the shapes are kept: their ids are the key
+    return hit[1]
+
+
+class GroupSpec:
+    """What one grouped call runs: the heads, the chain precision of each, the groups (lists of head indices, partition_heads),
+    the time encoding's frequencies."""
+
+    def __init__(self, specs: Sequence[HeadSpec], precisions: Sequence[str], time_multires: int = 0):
+        self.heads = list(specs)
+        self.precisions = [_checked_precision(p) for p in precisions]
+        if len({h.slope for h in self.heads}) > 1:
+            raise ValueError("the heads of a grouped step share one leaky-ReLU slope")
+        self.slope = self.heads[0].slope
+        self.time_multires = int(max(time_multires, 0))
+        self.groups = partition_heads(self.heads, self.precisions)
+        if len(self.heads) > _lib.MLP_GROUP_MAX_HEADS:
+            raise ValueError(f"at most {_lib.MLP_GROUP_MAX_HEADS} heads per grouped step")
+
+
+def grouped_inputs_ok(xyz, feat, time) -> bool:
+    """whether the grouped input kernel can take these per-call inputs (otherwise the caller runs the separate path)"""
+    if not (torch.is_tensor(xyz) and xyz.is_cuda and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.dtype == torch.float32 and xyz.shape[0] > 0):
+        return False
+    if feat is not None and not (feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 2 and feat.shape[0] == xyz.shape[0] and
+                                 feat.device == xyz.device):
+        return False
+    if time is not None and not (torch.is_tensor(time) and time.is_cuda and time.dtype == torch.float32 and not time.requires_grad and
+                                 time.numel() == xyz.shape[0] and time.device == xyz.device):
+        return False
+    return True
+
+
+def _head_input_table(heads: Sequence[HeadSpec], x0s=None, dx0s=None):
+    arr = (_lib.SrMlpHeadInput * len(heads))()
+    for i, h in enumerate(heads):
+        arr[i].multires, arr[i].row = h.multires, h.shape.mem_pad
+        arr[i].x0 = x0s[i].data_ptr() if x0s is not None else None
+        arr[i].dL_dx0 = dx0s[i].data_ptr() if dx0s is not None else None
+    return arr
+
+
+def _group_input_forward(lib, heads: Sequence[HeadSpec], time_multires: int, x32, f32, t32, x0s):
+    """x0 of every head: one launch (sr_mlp_group_input_forward)"""
+    dev = x32.device
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_mlp_group_input_forward(x32.shape[0], len(heads), _head_input_table(heads, x0s=x0s), 0 if f32 is None else f32.shape[1],
+                                                  time_multires, _lib.ptr(x32), _lib.ptr(f32), _lib.ptr(t32), _lib.stream(dev)))
+
+
+def _group_input_backward(lib, heads: Sequence[HeadSpec], n_feat: int, x32, dx0s, d_xyz, d_feat):
+    """d_xyz and d_feat, summed over the heads in table order: one launch (sr_mlp_group_input_backward)"""
+    dev = x32.device
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_mlp_group_input_backward(x32.shape[0], len(heads), _head_input_table(heads, dx0s=dx0s), n_feat, _lib.ptr(x32),
+                                                   _lib.ptr(d_xyz), _lib.ptr(d_feat), _lib.stream(dev)))
+
+
+def _head_output_table(heads: Sequence[HeadSpec], which, ys, outs=None, dOuts=None, Gs=None):
+    arr = (_lib.SrMlpHeadOutput * max(len(which), 1))()
+    for j, i in enumerate(which):
+        h = heads[i]
+        arr[j].y, arr[j].out_features, arr[j].row, arr[j].activation = ys[i].data_ptr(), h.shape.out_features, h.shape.out_pad, OUT_ACTIVATIONS[h.activation]
+        arr[j].out = outs[i].data_ptr() if outs is not None else None
+        arr[j].dL_dout = dOuts[i].data_ptr() if dOuts is not None and dOuts[i] is not None else None
+        arr[j].g = Gs[i].data_ptr() if Gs is not None else None
+    return arr
+
+
+def _group_output(lib, heads: Sequence[HeadSpec], ys):
+    """the heads' activated outputs: one launch for every head with an activation (sr_mlp_group_output); "none" is y itself"""
+    which = [i for i, h in enumerate(heads) if h.activation != "none"]
+    outs = [torch.empty_like(y) if i in which else y for i, y in enumerate(ys)]
+    if which:
+        dev = ys[0].device
+        with torch.cuda.device(dev):
+            _lib.check(lib.sr_mlp_group_output(ys[0].shape[0], len(which), _head_output_table(heads, which, ys, outs=outs), _lib.stream(dev)))
+    return outs
+
+
+def _group_top_gradient(lib, heads: Sequence[HeadSpec], ys, dOuts, slope: float, Gs):
+    """G = dOut o act'(.) o leaky'(y), zero-padded, for every head (zeros where dOut is None): one launch (sr_mlp_group_top_gradient)"""
+    dev = ys[0].device
+    table = _head_output_table(heads, list(range(len(heads))), ys, dOuts=dOuts, Gs=Gs)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sr_mlp_group_top_gradient(ys[0].shape[0], len(heads), table, slope, _lib.stream(dev)))
+
+
+class _GroupedHeadsFn(torch.autograd.Function):
+    """inputs: xyz, feat, time, spec, grad mode, then per head its weights and its biases; outputs: every head's activated output"""
+
+    @staticmethod
+    def forward(ctx, xyz, feat, time, spec: GroupSpec, grad_enabled: bool, *params):
+        lib = _lib.load()
+        heads_, weights, biases, k = spec.heads, [], [], 0
+        for h in heads_:
+            L = h.shape.n_layers
+            weights.append([_f32c(p) for p in params[k:k + L]])
+            biases.append([_f32c(p) for p in params[k + L:k + 2 * L]])
+            k += 2 * L
+        dev, n = xyz.device, xyz.shape[0]
+        x32 = _f32c(xyz)
+        f32 = _f32c(feat) if feat is not None else None
+        t32 = time.detach().to(torch.float32).reshape(-1).contiguous() if time is not None else None
+        x0s = [torch.empty(n, h.shape.mem_pad, dtype=torch.float32, device=dev) for h in heads_]
+        _group_input_forward(lib, heads_, spec.time_multires, x32, f32, t32, x0s)
+        need = grad_enabled and any(ctx.needs_input_grad)
+        ys = [torch.empty(n, h.shape.out_features, dtype=torch.float32, device=dev) for h in heads_]
+        acts = [torch.empty(h.shape.n_layers - 1, n, h.shape.hidden, dtype=torch.float32, device=dev) if need else None for h in heads_]
+        signs = [torch.empty(h.shape.n_layers - 1, n, 4, dtype=torch.int32, device=dev) if need else None for h in heads_]
+        for members in spec.groups:
+            shapes = [heads_[i].shape for i in members]
+            ptrs = []
+            for i, sh in zip(members, shapes):
+                H, L = sh.hidden, sh.n_layers
+                ptrs.append({"W": [w.data_ptr() for w in weights[i]], "B": [b.data_ptr() for b in biases[i]], "x0": (x0s[i].data_ptr(),),
+                             "y": (ys[i].data_ptr(),),
+                             "acts": [acts[i].data_ptr() + 4 * j * n * H for j in range(L - 1)] if need else (),
+                             "signs": [signs[i].data_ptr() + 16 * j * n for j in range(L - 1)] if need else ()})
+            with torch.cuda.device(dev):
+                _group_plan("fwd", shapes, need, spec.precisions[members[0]]).run(lib, ptrs, dev, n, shapes[0].ht, spec.slope, _lib.stream(dev))
+        outs = _group_output(lib, heads_, ys)
+        ctx.set_materialize_grads(False)      # a head nobody used arrives as None: its top gradient is written as zeros by the kernel
+        if need:
+            ctx.spec, ctx.n_feat = spec, 0 if f32 is None else f32.shape[1]
+            ctx.save_for_backward(x32, *x0s, *acts, *signs, *ys, *[w for ws in weights for w in ws])
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dOuts):
+        lib = _lib.load()
+        spec = ctx.spec
+        heads_, nh = spec.heads, len(spec.heads)
+        x32, *rest = ctx.saved_tensors
+        x0s, acts, signs, ys, flat = rest[:nh], rest[nh:2 * nh], rest[2 * nh:3 * nh], rest[3 * nh:4 * nh], rest[4 * nh:]
+        weights, k = [], 0
+        for h in heads_:
+            weights.append(flat[k:k + h.shape.n_layers])
+            k += h.shape.n_layers
+        dev, n = x32.device, x32.shape[0]
+        dOuts = [None if d is None else d.to(torch.float32).contiguous() for d in dOuts]
+        Gs = [torch.empty(n, h.shape.out_pad, dtype=torch.float32, device=dev) for h in heads_]
+        _group_top_gradient(lib, heads_, ys, dOuts, spec.slope, Gs)
+        need_xyz, need_feat = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.n_feat > 0
+        need_input = need_xyz or need_feat
+        dzs = [torch.empty(h.shape.n_layers - 1, n, h.shape.hidden, dtype=torch.float32, device=dev) for h in heads_]
+        dx0s = [torch.empty(n, h.shape.mem_pad, dtype=torch.float32, device=dev) if need_input else None for h in heads_]
+        for members in spec.groups:
+            shapes = [heads_[i].shape for i in members]
+            ptrs = []
+            for i, sh in zip(members, shapes):
+                H, L = sh.hidden, sh.n_layers
+                ptrs.append({"W": [w.data_ptr() for w in weights[i]], "G": (Gs[i].data_ptr(),), "dx0": (dx0s[i].data_ptr() if need_input else 0,),
+                             "acts": [acts[i].data_ptr() + 4 * j * n * H for j in range(L - 1)],
+                             "dz": [dzs[i].data_ptr() + 4 * j * n * H for j in range(L - 1)],
+                             "signs": [signs[i].data_ptr() + 16 * j * n for j in range(L - 1)]})
+            with torch.cuda.device(dev):
+                _group_plan("bwd", shapes, need_input, spec.precisions[members[0]]).run(lib, ptrs, dev, n, shapes[0].ht, spec.slope, _lib.stream(dev))
+        d_xyz = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_xyz else None
+        d_feat = torch.empty(n, ctx.n_feat, dtype=torch.float32, device=dev) if need_feat else None
+        if need_input:
+            _group_input_backward(lib, heads_, ctx.n_feat, x32, dx0s, d_xyz, d_feat)
+        grads, at = [], 5
+        for i, h in enumerate(heads_):       # weight and bias gradients: sr_mlp_weight_grad per net, unchanged
+            L = h.shape.n_layers
+            want = ctx.needs_input_grad[at:at + 2 * L]
+            if any(want):
+                dWs, dbs = _weight_grads(h.shape, x0s[i], acts[i], Gs[i], dzs[i], weights[i])
+                grads += [g if w else None for g, w in zip(list(dWs) + list(dbs), want)]
+            else:
+                grads += [None] * (2 * L)
+            at += 2 * L
+        return (d_xyz, d_feat, None, None, None, *grads)
+
+
+def fused_grouped_heads(spec: GroupSpec, xyz: torch.Tensor, feat: Optional[torch.Tensor], time: Optional[torch.Tensor],
+                        weights: Sequence[Sequence[torch.Tensor]], biases: Sequence[Sequence[torch.Tensor]]) -> Tuple[torch.Tensor, ...]:
+    """Every head of `spec` on (xyz [N, 3], feat [N, F] or None, time [N] or None) -> the heads' activated outputs, differentiable
+    with respect to xyz, feat and every weight and bias.  The caller has checked the inputs with `grouped_inputs_ok`."""
+    _lib.load()
+    n_feat = 0 if feat is None else feat.shape[1]
+    n_time = 0 if time is None else 1 + 2 * spec.time_multires
+    flat = []
+    for h, ws, bs in zip(spec.heads, weights, biases):
+        if h.shape.d_in != 3 * (1 + 2 * h.multires) + n_feat + n_time or len(ws) != h.shape.n_layers or len(bs) != h.shape.n_layers:
+            raise ValueError(f"head {h.name!r}: the inputs do not make the {h.shape.d_in} input channels its first layer reads")
+        flat += list(ws) + list(bs)
+    return _GroupedHeadsFn.apply(xyz, feat, time, spec, torch.is_grad_enabled(), *flat)

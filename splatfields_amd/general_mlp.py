@@ -27,6 +27,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import fused_mlp
 from .fused_mlp import _Shape, _checked_precision, fused_general_mlp, fused_general_mlp_points
 
 
@@ -206,6 +207,7 @@ class GeneralMLP(nn.Module):
         self.skips = list(skips)
         self.slope = _SLOPES[act]
         self.out_act = _OUT_ACTIVATIONS[out_activation]
+        self.out_activation = out_activation
         d_in = in_features - 3 + 3 * (1 + 2 * max(multires, 0))
         self.d_in = d_in
         # net[0], net[1 + i] for i < num_hidden_layers, net[-1]; layer ids 1 .. num_hidden_layers - 1 (= net[2:-1]) are
@@ -247,3 +249,70 @@ class GeneralMLP(nn.Module):
         h_in = torch.cat(parts, dim=-1) if len(parts) > 1 else h_in
         h = fused_general_mlp(h_in, weights, biases, skips=self.skips, negative_slope=self.slope, _shape=self._static_shape(), **pk)
         return self.out_act(h)
+
+
+def compose_group_weights(mlps: Sequence["GeneralMLP"], frame_id) -> list:
+    """effective weights of every layer of every net of a group, per net: the ResField layers of ALL nets composed by one launch
+    (`compose_resfield_weights` on the concatenated layer list; cut at SR_RESFIELD_MAX_JOBS residual layers)"""
+    out, chunk, n_res = [], [], 0
+
+    def flush():
+        nonlocal chunk, n_res
+        if chunk:
+            layers = [l for m in chunk for l in m.net]
+            composed = iter(compose_resfield_weights(layers, frame_id))
+            out.extend([next(composed) for _ in m.net] for m in chunk)
+        chunk, n_res = [], 0
+
+    for m in mlps:
+        r = sum(1 for l in m.net if l.has_residual)
+        if chunk and n_res + r > _lib.RESFIELD_MAX_JOBS:
+            flush()
+        chunk.append(m)
+        n_res += r
+    flush()
+    return out
+
+
+class HeadGroup:
+    """The head networks of a `SplatFields` step -- GeneralMLPs that read the same (xyz, features, time) -- run as groups
+    (`SplatFields(heads="grouped")`; splatfields_amd/fused_mlp.py: fused_grouped_heads).  Built at construction, so a network the
+    grouped path cannot run is refused there with the reason; the partition follows each net's chain precision at call time."""
+
+    def __init__(self, named_mlps, time_multires: int = 0):
+        self.names = [n for n, _ in named_mlps]
+        self.mlps = [m for _, m in named_mlps]
+        self.time_multires = int(time_multires)
+        self.specs = []
+        for name, m in named_mlps:
+            try:
+                shape = m._static_shape()
+            except ValueError as e:
+                raise ValueError(f"heads='grouped': {name} cannot run on the fused chains: {e}") from None
+            if m.out_activation not in fused_mlp.OUT_ACTIVATIONS:
+                raise ValueError(f"heads='grouped': {name} has the output activation {m.out_activation!r}; the grouped output kernel "
+                                 f"implements {tuple(fused_mlp.OUT_ACTIVATIONS)}")
+            self.specs.append(fused_mlp.HeadSpec(name, shape, m.multires, m.out_activation, m.slope))
+        self._by_precision: dict = {}
+        self.spec(tuple(fused_mlp.resolve_precision(m.precision) for m in self.mlps))      # limits are checked now
+
+    def spec(self, precisions) -> "fused_mlp.GroupSpec":
+        if precisions not in self._by_precision:
+            self._by_precision[precisions] = fused_mlp.GroupSpec(self.specs, precisions, self.time_multires)
+        return self._by_precision[precisions]
+
+    def partition(self, precisions=None):
+        """the groups as lists of head names"""
+        precisions = tuple(precisions) if precisions is not None else tuple(fused_mlp.resolve_precision(m.precision) for m in self.mlps)
+        return [[self.names[i] for i in g] for g in self.spec(precisions).groups]
+
+    def __call__(self, xyz, feat, frame_id=None, time=None) -> dict:
+        """-> {name: activated output}.  The caller has checked the inputs (fused_mlp.grouped_inputs_ok)."""
+        spec = self.spec(tuple(fused_mlp.resolve_precision(m.precision) for m in self.mlps))
+        weights = [None] * len(self.mlps)
+        for members in spec.groups:          # ResField composition: once per group
+            for i, ws in zip(members, compose_group_weights([self.mlps[i] for i in members], frame_id)):
+                weights[i] = ws
+        biases = [[layer.bias for layer in m.net] for m in self.mlps]
+        outs = fused_mlp.fused_grouped_heads(spec, xyz, feat, time, weights, biases)
+        return dict(zip(self.names, outs))
