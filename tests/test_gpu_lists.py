@@ -18,7 +18,7 @@ from tests.helpers import make_scene
 pytestmark = pytest.mark.gpu
 
 
-def hip_tile_lists(sp, st, dev):
+def hip_tile_lists(sp, st, dev, with_image=False):
     from splatfields_amd import _lib, rasterizer as rz
     from diff_gaussian_rasterization import GaussianRasterizationSettings
     lib = _lib.load()
@@ -40,7 +40,8 @@ def hip_tile_lists(sp, st, dev):
     tile_start = i32(geom, off[0], tiles + 1)
     total = i32(geom, off[2], 4)
     sorted_id = i32(binning, off[1], int(tile_start[-1]))      # list entries <= instances (tile_reached, csrc/common.h)
-    return tile_start, sorted_id, int(total[0]), int(rz.LAST_INSTANCES), radii.cpu()
+    res = (tile_start, sorted_id, int(total[0]), int(rz.LAST_INSTANCES), radii.cpu())
+    return res + (color.detach().cpu(),) if with_image else res
 
 
 @pytest.mark.parametrize("n,w,h,scale", [(20000, 320, 240, None), (3000, 200, 152, 0.06), (60000, 400, 304, None)])
@@ -59,12 +60,14 @@ def test_a_few_lists_between_2048_and_4096_entries(hip_device):
     idx = torch.randperm(n, generator=g)[:2600]
     sp["means3D"][idx] = 0.004 * torch.randn(2600, 3, generator=g)
     sp["scales"][idx] = sp["scales"][idx].clamp(max=0.01)
-    lengths = check_tile_lists(sp, st, n, w, h, hip_device)
+    lengths, _ = check_tile_lists(sp, st, n, w, h, hip_device)
     long = (lengths > 2048) & (lengths <= 4096)
     assert 1 <= int(long.sum()) <= 8 and int(lengths.max()) <= 4096, lengths.max()
 
 
-def check_tile_lists(sp, st, n, w, h, hip_device):
+def check_tile_lists(sp, st, n, w, h, hip_device, expect_missing=True):
+    """Returns (list length of every tile, number of neighbouring list entries with EQUAL float depths that were seen -- and
+    checked to be in splat order).  expect_missing=False: a scene built so that exact-support culling leaves nothing out."""
     tile_start, sorted_id, total, reported, radii = hip_tile_lists(sp, st, hip_device)
     # instances = tiles of every splat's rectangle (what the facade reports and sizes the per-instance buffers by); the lists hold
     # the instances whose tile the splat can reach
@@ -81,7 +84,7 @@ def check_tile_lists(sp, st, n, w, h, hip_device):
     gx, gy = (w + 15) // 16, (h + 15) // 16
     op = d64["opacities"].reshape(-1)
     A, B, Cc = pre.conic[:, 0], pre.conic[:, 1], pre.conic[:, 2]
-    checked_missing = 0
+    checked_missing = ties = 0
     for t in range(gx * gy):
         tx, ty = t % gx, t // gx
         hip = sorted_id[int(tile_start[t]):int(tile_start[t + 1])]
@@ -112,6 +115,7 @@ def check_tile_lists(sp, st, n, w, h, hip_device):
             f32 = dz.float()
             tie = f32[1:] == f32[:-1]
             assert (hip[1:][tie] > hip[:-1][tie]).all() or not stable[hip].all(), f"tile {t}: equal depths not in splat order"
+            ties += int(tie.sum())
     # the exact-support culling does leave entries out, and all of them were checked
-    assert checked_missing > 0
-    return tile_start[1:] - tile_start[:-1]
+    assert (checked_missing > 0) == expect_missing
+    return tile_start[1:] - tile_start[:-1], ties
