@@ -23,7 +23,7 @@
 // store; a slot with some visible rows stores the loaded bits back for the others.
 //
 // No LDS, no atomics, no scratch; every store is a vector store.
-#include "kernels.h"
+#include "host_api.h"
 
 namespace sr {
 
@@ -196,8 +196,6 @@ int cu_count() {   // of the current device; one query per device and process
     return cached[dev];
 }
 
-}  // namespace
-
 void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st) {
     AdamTable t = {};
     int n = 0;
@@ -220,4 +218,35 @@ void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible
     else hipLaunchKernelGGL(k_adam<false>, grid, dim3(kBlock), 0, st, t);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::any_unaligned4;
+
+extern "C" {
+
+int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, long long rows, void* hip_stream) {
+    if (n_jobs < 0 || n_jobs > SR_ADAM_MAX_TENSORS) return fail("bad arguments to sr_adam_step: n_jobs must be 0 .. SR_ADAM_MAX_TENSORS (32)");
+    if (n_jobs > 0 && !jobs) return fail("null pointer in sr_adam_step: jobs");
+    if (visible && rows < 0) return fail("bad arguments to sr_adam_step: negative row count");
+    bool work = false;
+    for (int i = 0; i < n_jobs; ++i) {
+        const SrAdamJob& j = jobs[i];
+        const std::string at = " (job " + std::to_string(i) + ")";
+        if (j.count < 0) return fail("bad arguments to sr_adam_step: negative element count" + at);
+        if (j.count > 0x7fffffffll) return fail("too many elements for sr_adam_step: at most 2^31 - 1 in one job" + at);
+        if (visible && (j.row <= 0 || j.count != rows * (long long)j.row))
+            return fail("sr_adam_step: with a row mask every job needs count == rows * row" + at);
+        if (j.count == 0) continue;
+        if (!j.param || !j.grad || !j.exp_avg || !j.exp_avg_sq) return fail("null pointer in sr_adam_step" + at);
+        if (any_unaligned4(j.param, j.grad, j.exp_avg, j.exp_avg_sq)) return fail("sr_adam_step: tensors must be 4-byte aligned" + at);
+        work = true;
+    }
+    if (!work) return 0;
+    sr::launch_adam(n_jobs, jobs, visible, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "adam_step");
+}
+
+}  // extern "C"

@@ -18,10 +18,12 @@
 // The kernels that walk channels are compiled per channel count (C / 8 = 1 .. 8): with constant bounds their loops unroll and
 // the LDS reads of a tile are in flight together; with a run-time bound every predicated multiply-add waited for its own read.
 // d to_k.bias is written as zeros: the softmax does not see a shift of a whole score row, so the sum over a row of dS is zero.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 
 namespace sr {
+
+constexpr int kAttentionBackwardSteps = 6;     // launch_attention_backward(step = 0 .. 5), in this order
 
 namespace {
 
@@ -610,8 +612,6 @@ AttnArgs make_args(int channels, int groups, int h, int w, float eps) {
     return a;
 }
 
-}  // namespace
-
 const char* attention_shape_error(int channels, int groups, int h, int w) {
     if (channels < 8 || channels > kAMaxC || channels % 8 != 0) return "channels must be a multiple of 8 in 8..64";
     if (groups < 1 || channels % groups != 0) return "groups must divide channels";
@@ -655,4 +655,62 @@ void launch_attention_backward(int step, int n, const SrAttentionJob* jobs, int 
     }
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::StageTimer;
+
+extern "C" {
+
+static int attention_check(const char* who, int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width) {
+    if (!jobs) return fail(std::string("null pointer in ") + who + ": jobs");
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS) return fail(std::string("bad arguments to ") + who + ": n_planes must be 1 .. SR_PLANE_MAX_JOBS (8)");
+    if (const char* why = sr::attention_shape_error(channels, groups, height, width)) return fail(std::string(who) + ": " + why);
+    return 0;
+}
+
+size_t sr_attention_saved_bytes(int n_planes, int channels, int groups, int height, int width) {
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS || sr::attention_shape_error(channels, groups, height, width)) return 0;
+    return sr::attention_saved_bytes(n_planes, channels, groups, height, width);
+}
+
+size_t sr_attention_backward_workspace(int n_planes, int channels, int groups, int height, int width) {
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS || sr::attention_shape_error(channels, groups, height, width)) return 0;
+    return sr::attention_backward_workspace(n_planes, channels, height, width);
+}
+
+int sr_attention_forward(int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width, float eps,
+                         void* hip_stream) {
+    SR_TRY(attention_check("sr_attention_forward", n_planes, jobs, channels, groups, height, width));
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrAttentionJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_attention_forward", j.x && j.gamma && j.beta && j.stats && j.wq && j.bq && j.wk && j.bk && j.wv && j.bv && j.wo && j.bo &&
+                      j.out && j.saved);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_attention_stats(n_planes, jobs, channels, groups, height, width, eps, st); }
+    { StageTimer t_(0, st); sr::launch_attention_qkv(n_planes, jobs, channels, groups, height, width, eps, st); }
+    { StageTimer t_(0, st); sr::launch_attention_softmax(n_planes, jobs, channels, groups, height, width, eps, st); }
+    return check_hip(hipGetLastError(), "attention_forward");
+}
+
+int sr_attention_backward(int n_planes, const SrAttentionJob* jobs, int channels, int groups, int height, int width, float eps,
+                          void* workspace, void* hip_stream) {
+    SR_TRY(attention_check("sr_attention_backward", n_planes, jobs, channels, groups, height, width));
+    if (!workspace) return fail("null pointer in sr_attention_backward: workspace");
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrAttentionJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_attention_backward", j.x && j.gamma && j.beta && j.wq && j.wk && j.wv && j.wo && j.saved && j.dy && j.dx);
+        SR_PLANE_NEED("sr_attention_backward", j.dgamma && j.dbeta && j.dwq && j.dbq && j.dwk && j.dbk && j.dwv && j.dbv && j.dwo && j.dbo);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    for (int step = 0; step < sr::kAttentionBackwardSteps; ++step) {
+        StageTimer t_(6, st);
+        sr::launch_attention_backward(step, n_planes, jobs, channels, groups, height, width, eps, workspace, st);
+    }
+    return check_hip(hipGetLastError(), "attention_backward");
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@
 // its backward are doubles with IEEE sqrt and division; every stored value is rounded to fp32 once.  The backward starts from
 // the forward's z, saved as doubles ([M][N], so that a wavefront's loads and stores of one z are contiguous), and multiplies the
 // unrounded dz with W for dL/dhidden.  No atomics, no host wait.
-#include "kernels.h"
+#include "host_api.h"
 #include "point_tile.h"
 #include "reduce.h"
 
@@ -403,6 +403,13 @@ void flow_launch(const FlowK& k, int m, hipStream_t st) {
     }
 }
 
+int flow_head_dz_row(int model, int n_basis) {
+    int rows[SR_FLOW_MAX_BRANCHES], m = 0;
+    const int nb = flow_rows(model, n_basis, rows);
+    for (int b = 0; b < nb; ++b) m += (rows[b] + 3) & ~3;
+    return m;
+}
+
 FlowK flow_params(int model, long long n, int width, int n_basis, int n_branches, const SrFlowBranch* branches) {
     FlowK k{};
     k.model = model; k.n = n; k.width = width; k.n_basis = n_basis; k.n_branches = n_branches;
@@ -410,8 +417,6 @@ FlowK flow_params(int model, long long n, int width, int n_basis, int n_branches
     for (int b = 0; b < n_branches; ++b) k.branch[b] = branches[b];
     return k;
 }
-
-}  // namespace
 
 const char* flow_head_shape_error(int model, long long n_points, int width, int n_basis) {
     int rows[SR_FLOW_MAX_BRANCHES];
@@ -426,13 +431,6 @@ int flow_head_outputs(int model, int n_basis) {
     int rows[SR_FLOW_MAX_BRANCHES], m = 0;
     const int nb = flow_rows(model, n_basis, rows);
     for (int b = 0; b < nb; ++b) m += rows[b];
-    return m;
-}
-
-int flow_head_dz_row(int model, int n_basis) {
-    int rows[SR_FLOW_MAX_BRANCHES], m = 0;
-    const int nb = flow_rows(model, n_basis, rows);
-    for (int b = 0; b < nb; ++b) m += (rows[b] + 3) & ~3;
     return m;
 }
 
@@ -470,4 +468,66 @@ void launch_flow_head_backward(int model, long long n, int width, int n_basis, i
     flow_launch<true>(k, flow_head_outputs(model, n_basis), st);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::any_unaligned4; using sr::StageTimer;
+
+extern "C" {
+
+static int flow_head_check(const char* who, int model, long long n_points, int width, int n_basis, int n_branches, const SrFlowBranch* branches,
+                           bool need_bias) {
+    if (const char* why = sr::flow_head_shape_error(model, n_points, width, n_basis)) return fail(std::string(who) + ": " + why);
+    if (const char* why = sr::flow_head_branch_error(model, n_basis, n_branches, branches)) return fail(std::string(who) + ": " + why);
+    for (int b = 0; b < n_branches; ++b) {
+        if (!branches[b].weight || (need_bias && !branches[b].bias)) return fail(std::string("null pointer in ") + who + ": a branch's weight or bias");
+        if ((reinterpret_cast<uintptr_t>(branches[b].weight) & 15u) || (reinterpret_cast<uintptr_t>(branches[b].bias) & 3u))
+            return fail(std::string(who) + ": branch weights must be 16-byte aligned, biases 4-byte");
+    }
+    return 0;
+}
+
+size_t sr_flow_head_saved_bytes(int model, long long n_points, int width, int n_basis) {
+    return sr::flow_head_shape_error(model, n_points, width, n_basis) ? 0 : sr::flow_head_saved_bytes(model, n_points, n_basis);
+}
+
+size_t sr_flow_head_workspace_bytes(int model, long long n_points, int width, int n_basis) {
+    return sr::flow_head_shape_error(model, n_points, width, n_basis) ? 0 : sr::flow_head_workspace_bytes(model, n_points, n_basis);
+}
+
+int sr_flow_head_dz_row(int model, int n_basis) { return sr::flow_head_dz_row(model, n_basis); }
+
+int sr_flow_head_forward(int model, long long n_points, int width, int n_basis, int n_branches, const SrFlowBranch* branches,
+                         const float* hidden, const float* pts, const float* bases, float* means3D, float* flow, void* saved,
+                         void* hip_stream) {
+    SR_TRY(flow_head_check("sr_flow_head_forward", model, n_points, width, n_basis, n_branches, branches, true));
+    if (n_points == 0) return 0;
+    if (!hidden || !pts || !means3D || !flow) return fail("null pointer in sr_flow_head_forward");
+    if (model == SR_FLOW_DCT && !bases) return fail("null pointer in sr_flow_head_forward: the DCT model reads bases");
+    if ((reinterpret_cast<uintptr_t>(hidden) & 15u) || (model == SR_FLOW_SE3 && (reinterpret_cast<uintptr_t>(flow) & 15u)) ||
+        (reinterpret_cast<uintptr_t>(saved) & 7u) || any_unaligned4(pts, bases, means3D, flow))
+        return fail("sr_flow_head_forward: hidden (and the 4x4 flow) must be 16-byte aligned, saved 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_flow_head_forward(model, n_points, width, n_basis, n_branches, branches, hidden, pts, bases, means3D, flow, saved, st); }
+    return check_hip(hipGetLastError(), "flow_head_forward");
+}
+
+int sr_flow_head_backward(int model, long long n_points, int width, int n_basis, int n_branches, const SrFlowBranch* branches,
+                          const float* pts, const float* bases, const void* saved, const float* dL_dmeans3D, const float* dL_dflow,
+                          float* dL_dpts, float* dL_dz, float* dL_dhidden, void* workspace, void* hip_stream) {
+    SR_TRY(flow_head_check("sr_flow_head_backward", model, n_points, width, n_basis, n_branches, branches, false));
+    if (n_points == 0) return 0;
+    if (!pts || !saved || !dL_dmeans3D || !dL_dz || !workspace) return fail("null pointer in sr_flow_head_backward");
+    if (model == SR_FLOW_DCT && !bases) return fail("null pointer in sr_flow_head_backward: the DCT model reads bases");
+    if ((reinterpret_cast<uintptr_t>(dL_dz) & 15u) || (reinterpret_cast<uintptr_t>(dL_dhidden) & 15u) || (reinterpret_cast<uintptr_t>(saved) & 7u) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 7u) || any_unaligned4(pts, bases, dL_dmeans3D, dL_dflow, dL_dpts))
+        return fail("sr_flow_head_backward: dL_dz and dL_dhidden must be 16-byte aligned, saved and workspace 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_flow_head_backward(model, n_points, width, n_basis, n_branches, branches, pts, bases, saved, dL_dmeans3D, dL_dflow,
+                                                          dL_dpts, dL_dz, dL_dhidden, workspace, st); }
+    return check_hip(hipGetLastError(), "flow_head_backward");
+}
+
+}  // extern "C"

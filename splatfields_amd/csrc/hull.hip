@@ -19,7 +19,7 @@
 // the host except for voxels whose pixel coordinate lies within ~1e-13 px of a rounding boundary (k + 1/2), where the order of
 // the four-term dot product inside the host's BLAS can decide.  About 20 fp64 operations per voxel and view: the pass is
 // bound by its byte gathers, not by the fp64 rate.
-#include "kernels.h"
+#include "host_api.h"
 
 namespace sr {
 
@@ -159,8 +159,6 @@ size_t carve_hull(void* base, long long n, HullCarve* out) {
     return align_up(c.off, 256);
 }
 
-}  // namespace
-
 size_t hull_workspace_bytes(long long n) { return carve_hull(nullptr, n, nullptr); }
 
 hipError_t launch_hull_carve(int n_views, const SrHullView* host_views, const uint8_t* masks, const double* grid, int G, const void* points,
@@ -188,4 +186,64 @@ void launch_hull_gather(const double* grid, int G, const void* points, long long
         hipLaunchKernelGGL(k_hull_gather, dim3((unsigned)blocks), dim3(kBlock), 0, st, it, c.words, c.counts, capacity, indices_out, points_out);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+// items of a hull call: G^3 or n_points; -1 with the message set when the pair is not acceptable
+static long long hull_items(const char* name, const double* grid, int G, const void* points, long long n_points) {
+    if ((grid != nullptr) == (points != nullptr)) {
+        fail(std::string(name) + ": exactly one of grid and points must be given");
+        return -1;
+    }
+    if (grid) {
+        if (G < 1) { fail(std::string(name) + ": G must be at least 1"); return -1; }
+        if (G > 1290) { fail(std::string(name) + ": G^3 must not exceed 2^31 - 1 (G <= 1290)"); return -1; }
+        return (long long)G * G * G;
+    }
+    if (n_points < 0 || n_points > 2147483647LL) { fail(std::string(name) + ": n_points must be in 0 .. 2^31 - 1"); return -1; }
+    return n_points;
+}
+
+size_t sr_hull_workspace_bytes(long long n_items) { return n_items < 0 || n_items > 2147483647LL ? 0 : sr::hull_workspace_bytes(n_items); }
+
+int sr_hull_carve(int n_views, const SrHullView* views, const unsigned char* masks, long long mask_bytes, const double* grid, int G,
+                  const void* points, long long n_points, int point_is_double, void* workspace, int* count_out, void* hip_stream) {
+    if (n_views <= 0 || n_views > SR_HULL_MAX_VIEWS) return fail("sr_hull_carve: n_views must be in 1 .. SR_HULL_MAX_VIEWS");
+    if (!views || !masks || !workspace || !count_out) return fail("null pointer in sr_hull_carve");
+    const long long n = hull_items("sr_hull_carve", grid, G, points, n_points);
+    if (n < 0) return 1;
+    for (int k = 0; k < n_views; ++k) {
+        const SrHullView& w = views[k];
+        const std::string at = "sr_hull_carve: view " + std::to_string(k);
+        if (w.height < 1 || w.width < 1) return fail(at + ": H and W must be at least 1");
+        if (w.convention != SR_HULL_KRT && w.convention != SR_HULL_NDC) return fail(at + ": unknown pixel-mapping convention");
+        if (w.outside != SR_HULL_OUTSIDE_CARVE && w.outside != SR_HULL_OUTSIDE_KEEP) return fail(at + ": unknown outside policy");
+        if (w.convention == SR_HULL_KRT && (w.height == 1 || w.width == 1))
+            return fail(at + ": H or W of 1 divides by zero in the krt normalisation (W - 1)");
+        if (w.mask_offset < 0 || w.mask_offset + (long long)w.height * w.width > mask_bytes)
+            return fail(at + ": the mask does not fit into mask_bytes");
+    }
+    SR_TRY(check_hip(sr::launch_hull_carve(n_views, views, masks, grid, G, points, n, point_is_double != 0, workspace, count_out,
+                                           static_cast<hipStream_t>(hip_stream)), "upload of the hull view table"));
+    return check_hip(hipGetLastError(), "hull_carve");
+}
+
+int sr_hull_gather(const double* grid, int G, const void* points, long long n_points, int point_is_double, const void* workspace,
+                   long long capacity, int* indices_out, float* points_out, void* hip_stream) {
+    const long long n = hull_items("sr_hull_gather", grid, G, points, n_points);
+    if (n < 0) return 1;
+    if (capacity < 0) return fail("sr_hull_gather: capacity must not be negative");
+    if (!workspace) return fail("null pointer in sr_hull_gather");
+    if (n == 0 || capacity == 0 || (!indices_out && !points_out)) return 0;
+    sr::launch_hull_gather(grid, G, points, n, point_is_double != 0, workspace, capacity, indices_out, points_out,
+                           static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "hull_gather");
+}
+
+}  // extern "C"

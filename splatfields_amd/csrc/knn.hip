@@ -9,7 +9,7 @@
 //
 // Second half of the file: the K-nearest-neighbour GRAPH (2 <= K <= 8, self included) of the Moran's I regulariser on the same
 // grid -- the counterpart of [EXT] pytorch3d.ops.knn.knn_points at reference extract_geo.py:101-103.
-#include "kernels.h"
+#include "host_api.h"
 
 namespace sr {
 
@@ -161,12 +161,12 @@ __global__ void k_knn_search(int n, const float* __restrict__ pts, const float* 
     out[i] = sum / 3.0f;
 }
 
-size_t knn_workspace_bytes(int n) {
+static size_t knn_workspace_bytes(int n) {
     const size_t cells = (size_t)(n > 2 ? n : 2);  // max_cells = n
     return align_up(8 * sizeof(float), 256) + 3 * align_up((cells + 1) * sizeof(uint32_t), 256) + align_up((size_t)(n > 0 ? n : 1) * sizeof(uint32_t), 256);
 }
 
-void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream_t st) {
+static void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream_t st) {
     if (n <= 0) return;
     Carver c{static_cast<char*>(workspace), 0};
     const int max_cells = n > 2 ? n : 2;
@@ -282,7 +282,7 @@ __global__ void k_rev_fill(int edges, const int* __restrict__ nn_ix, const uint3
     unordered[start[t] + atomicAdd(&cursor[t], 1u)] = (uint32_t)e;
 }
 
-size_t knn_graph_workspace_bytes(int n, int k) {
+static size_t knn_graph_workspace_bytes(int n, int k) {
     if (n <= 0 || k < kKnnMinK || k > kKnnMaxK) return 0;
     const size_t cells = (size_t)(n > 2 ? n : 2);
     return align_up(8 * sizeof(float), 256) + 3 * align_up((cells + 1) * sizeof(uint32_t), 256) + align_up((size_t)n * sizeof(uint32_t), 256) +
@@ -295,8 +295,8 @@ static void launch_search_k(int nb, int n, const float* pts, const float* bounds
     hipLaunchKernelGGL(k_knn_search_k<K>, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, order, nn_ix);
 }
 
-void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* order, uint32_t* rev_start, uint32_t* rev_edges, void* workspace,
-                      hipStream_t st) {
+static void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* order, uint32_t* rev_start, uint32_t* rev_edges, void* workspace,
+                             hipStream_t st) {
     Carver c{static_cast<char*>(workspace), 0};
     const int max_cells = n > 2 ? n : 2;
     float* bounds = c.take<float>(8);
@@ -330,3 +330,31 @@ void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* orde
 }
 
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+size_t sr_knn_workspace_bytes(int n) { return sr::knn_workspace_bytes(n); }
+
+int sr_knn3_mean_dist2(int n, const float* points, float* mean_dist2, void* workspace, void* hip_stream) {
+    if (n < 0 || (n > 0 && (!points || !mean_dist2 || !workspace))) return fail("bad arguments to sr_knn3_mean_dist2");
+    sr::launch_knn3(n, points, mean_dist2, workspace, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "knn3");
+}
+
+size_t sr_knn_graph_workspace_bytes(int n, int k) { return sr::knn_graph_workspace_bytes(n, k); }
+
+int sr_knn_graph(int n, int k, const float* points, int* nn_ix, unsigned* order, unsigned* rev_start, unsigned* rev_edges, void* workspace,
+                 void* hip_stream) {
+    if (n <= 0) return fail("bad arguments to sr_knn_graph: sizes must be positive");
+    if (k < sr::kKnnMinK || k > sr::kKnnMaxK) return fail("bad arguments to sr_knn_graph: k must be 2 .. 8");
+    if (n < k) return fail("bad arguments to sr_knn_graph: fewer points than neighbours (n < k)");
+    if (n > 0x7fffffff / (3 * sr::kKnnMaxK)) return fail("too many points for sr_knn_graph");
+    if (!points || !nn_ix || !order || !rev_start || !rev_edges || !workspace) return fail("null pointer in sr_knn_graph");
+    sr::launch_knn_graph(n, k, points, nn_ix, order, rev_start, rev_edges, workspace, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "knn_graph");
+}
+
+}  // extern "C"

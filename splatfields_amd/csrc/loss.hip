@@ -21,7 +21,7 @@
 //           with the upstream gradient g read from device memory.
 //
 // No floating-point atomics anywhere: values and gradients are bit-identical from call to call.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 #include "window11.h"
 
@@ -309,8 +309,6 @@ LossDims loss_dims(int batch, int channels, int H, int W) {
     return d;
 }
 
-}  // namespace
-
 bool loss_shape_ok(int batch, int channels, int H, int W) {
     return batch > 0 && channels > 0 && (long long)batch * channels <= 0x7fffffffll && loss_blocks(batch * channels, H, W) > 0;
 }
@@ -351,4 +349,46 @@ void launch_loss_backward(int batch, int channels, int H, int W, const float* im
                        g_per_item, dL_dimage, dL_dalpha);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+size_t sr_loss_workspace_bytes(int planes, int height, int width) { return sr::loss_workspace_bytes(planes, height, width); }
+
+size_t sr_loss_maps_bytes(int planes, int height, int width) { return sr::loss_maps_bytes(planes, height, width); }
+
+int sr_photometric_forward(int batch, int channels, int height, int width, const float* image, const float* gt, const float* alpha,
+                           const float* gt_mask, float lambda_dssim, float lambda_mask, void* workspace, float* maps, float* loss,
+                           float* l1, float* ssim, float* mask_l1, void* hip_stream) {
+    if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_photometric_forward: sizes must be positive");
+    if (!sr::loss_shape_ok(batch, channels, height, width)) return fail("image too large for sr_photometric_forward");
+    if (!image || !gt || !workspace || !loss || !l1) return fail("null pointer in sr_photometric_forward");
+    if ((alpha == nullptr) != (gt_mask == nullptr)) return fail("sr_photometric_forward: alpha and gt_mask go together (both or neither)");
+    if (alpha && !mask_l1) return fail("null pointer in sr_photometric_forward: mask_l1 is written when alpha is given");
+    if (!alpha && lambda_mask != 0.0f) return fail("sr_photometric_forward: lambda_mask without alpha and gt_mask");
+    if (!ssim && (lambda_dssim != 0.0f || maps)) return fail("sr_photometric_forward: the ssim output may be omitted only with lambda_dssim = 0 and no maps");
+    sr::launch_loss_forward(batch, channels, height, width, image, gt, alpha, gt_mask, lambda_dssim, lambda_mask, workspace, maps, loss, l1,
+                            ssim, mask_l1, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "photometric_forward");
+}
+
+int sr_photometric_backward(int batch, int channels, int height, int width, const float* image, const float* gt, const float* alpha,
+                            const float* gt_mask, const float* maps, float w_l1, float w_ssim, float w_mask, const float* upstream,
+                            int upstream_per_item, float* dL_dimage, float* dL_dalpha, void* hip_stream) {
+    if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_photometric_backward: sizes must be positive");
+    if (!sr::loss_shape_ok(batch, channels, height, width)) return fail("image too large for sr_photometric_backward");
+    if (!image || !gt || !upstream || !dL_dimage) return fail("null pointer in sr_photometric_backward");
+    if ((alpha == nullptr) != (gt_mask == nullptr)) return fail("sr_photometric_backward: alpha and gt_mask go together (both or neither)");
+    if (dL_dalpha && !alpha) return fail("sr_photometric_backward: dL_dalpha without alpha and gt_mask");
+    if (w_ssim != 0.0f && !maps) return fail("sr_photometric_backward: a structural-similarity weight needs the maps of the forward");
+    sr::launch_loss_backward(batch, channels, height, width, image, gt, alpha, gt_mask, w_ssim != 0.0f ? maps : nullptr, w_l1, w_ssim, w_mask,
+                             upstream, upstream_per_item != 0, dL_dimage, dL_dalpha, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "photometric_backward");
+}
+
+}  // extern "C"

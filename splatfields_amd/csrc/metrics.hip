@@ -23,7 +23,7 @@
 // k_metrics_reduce  one workgroup; a wavefront per item adds that item's partial sums in a fixed order and writes the results.
 //
 // No floating-point atomics and no host wait: results are bit-identical from call to call.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 #include "window11.h"
 
@@ -296,8 +296,6 @@ void launch_metrics_quant(int quantize, unsigned nb, hipStream_t st, const Metri
         hipLaunchKernelGGL((k_metrics<kMasked, SR_QUANT_NONE>), dim3(nb), dim3(kBlock), 0, st, d, pred, gt, mask, frames, partial);
 }
 
-}  // namespace
-
 bool metrics_shape_ok(int batch, int H, int W) { return metric_blocks(batch, H, W) > 0; }
 
 size_t metrics_workspace_bytes(int batch, int H, int W) {
@@ -327,4 +325,34 @@ void launch_image_metrics(int batch, int H, int W, const float* pred, const long
                        3.0 * (double)d.out_h * (double)d.out_w, partial, psnr, ssim, psnr_channels);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+size_t sr_metrics_workspace_bytes(int batch, int height, int width) { return sr::metrics_workspace_bytes(batch, height, width); }
+
+int sr_image_metrics(int batch, int height, int width, const float* pred, const long long* pred_strides4, const float* gt,
+                     const long long* gt_strides4, const float* mask, long long mask_item_stride, int quantize, void* workspace,
+                     float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, void* hip_stream) {
+    if (batch <= 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_image_metrics: sizes must be positive");
+    if (height < 11 || width < 11) return fail("bad arguments to sr_image_metrics: the 11-tap valid window needs height and width >= 11");
+    if (!sr::metrics_shape_ok(batch, height, width)) return fail("image too large for sr_image_metrics");
+    if (!pred || !gt || !pred_strides4 || !gt_strides4 || !workspace || !psnr || !ssim || !psnr_channels) return fail("null pointer in sr_image_metrics");
+    if (quantize != SR_QUANT_NONE && quantize != SR_QUANT_PNG && quantize != SR_QUANT_TO8B)
+        return fail("bad arguments to sr_image_metrics: unknown quantisation mode (SR_QUANT_NONE, SR_QUANT_PNG, SR_QUANT_TO8B)");
+    if (frames && quantize == SR_QUANT_NONE) return fail("sr_image_metrics: frames are the quantised prediction and need a quantisation mode");
+    for (int k = 0; k < 4; ++k)
+        if (pred_strides4[k] < 0 || gt_strides4[k] < 0) return fail("bad arguments to sr_image_metrics: negative stride");
+    if (mask && mask_item_stride != 0 && mask_item_stride < (long long)height * width)
+        return fail("bad arguments to sr_image_metrics: mask_item_stride must be 0 or at least height * width");
+    sr::launch_image_metrics(batch, height, width, pred, pred_strides4, gt, gt_strides4, mask, mask_item_stride, quantize, workspace, psnr,
+                             ssim, psnr_channels, frames, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "image_metrics");
+}
+
+}  // extern "C"

@@ -25,7 +25,7 @@
 // Packed matrix with MT output tiles and KT input tiles (host side: splatfields_amd/fused_mlp.py):
 //   float index ((((c * MT + mt) * 2 + tl) * 64 + lane) * 4 + i)  =  A[16 mt + (lane & 15)][16 (2 c + tl) + 4 (lane >> 4) + i]
 // (zero beyond the matrix's true sizes), bias padded to 16 MT floats.
-#include "kernels.h"
+#include "host_api.h"
 
 namespace sr {
 
@@ -651,8 +651,6 @@ static void grad_slabs(int n_points, int* slab, int* n_slabs) {
     *n_slabs = max(1, (n_points + *slab - 1) / *slab);
 }
 
-}  // namespace
-
 size_t mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs) {
     const int nt = grad_tasks(n_points, n_jobs, jobs, nullptr);
     if (nt < 0 || n_points < 0) return 0;
@@ -765,6 +763,8 @@ const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, c
     else hipLaunchKernelGGL((k_mlp_chain_group<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
     return nullptr;
 }
+
+}  // namespace
 
 }  // namespace sr
 
@@ -884,7 +884,7 @@ static int resfield_check(int n_jobs, const SrResFieldJob* jobs, bool backward, 
     return 0;
 }
 
-int launch_resfield_compose(int n_jobs, const SrResFieldJob* jobs, const long long* frame, hipStream_t st) {
+static int launch_resfield_compose(int n_jobs, const SrResFieldJob* jobs, const long long* frame, hipStream_t st) {
     int mc;
     if (!frame || resfield_check(n_jobs, jobs, false, &mc)) return 1;
     ResFieldK P;
@@ -894,13 +894,13 @@ int launch_resfield_compose(int n_jobs, const SrResFieldJob* jobs, const long lo
     return 0;
 }
 
-size_t resfield_backward_workspace(int n_jobs, const SrResFieldJob* jobs) {
+static size_t resfield_backward_workspace(int n_jobs, const SrResFieldJob* jobs) {
     int mc;
     if (resfield_check(n_jobs, jobs, true, &mc)) return 0;
     return (size_t)n_jobs * ((mc + kRfPerBlock - 1) / kRfPerBlock) * SR_RESFIELD_MAX_RANK * sizeof(float);
 }
 
-int launch_resfield_backward(int n_jobs, const SrResFieldJob* jobs, const long long* frame, void* workspace, size_t workspace_bytes, hipStream_t st) {
+static int launch_resfield_backward(int n_jobs, const SrResFieldJob* jobs, const long long* frame, void* workspace, size_t workspace_bytes, hipStream_t st) {
     int mc;
     if (!frame || !workspace || resfield_check(n_jobs, jobs, true, &mc)) return 1;
     if (workspace_bytes < resfield_backward_workspace(n_jobs, jobs)) return 1;
@@ -982,8 +982,8 @@ __global__ void __launch_bounds__(kBlock) k_mlp_input_backward(int N, int L, int
     }
 }
 
-int launch_mlp_input_forward(int N, int L, int F, int TL, int row, const float* xyz, const float* feat, const float* time, float* x0,
-                             hipStream_t st) {
+static int launch_mlp_input_forward(int N, int L, int F, int TL, int row, const float* xyz, const float* feat, const float* time, float* x0,
+                                    hipStream_t st) {
     if (N < 0 || L < 0 || L > 16 || F < 0 || TL < 0 || TL > 16 || (row & 3) || row < 3 + 6 * L + F + (time ? 1 + 2 * TL : 0) ||
         (F > 0 && !feat) || !xyz || !x0) return 1;
     if (N == 0) return 0;
@@ -1009,7 +1009,7 @@ __global__ void __launch_bounds__(kBlock) k_mlp_top_gradient(int N, int out, int
     reinterpret_cast<float4*>(G)[t] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-int launch_mlp_top_gradient(int N, int out, int row, const float* y, const float* dy, float slope, float* G, hipStream_t st) {
+static int launch_mlp_top_gradient(int N, int out, int row, const float* y, const float* dy, float slope, float* G, hipStream_t st) {
     if (N < 0 || out < 1 || (row & 3) || row < out || !y || !dy || !G) return 1;
     if (N == 0) return 0;
     const long long threads = (long long)N * (row >> 2);
@@ -1017,7 +1017,7 @@ int launch_mlp_top_gradient(int N, int out, int row, const float* y, const float
     return 0;
 }
 
-int launch_mlp_input_backward(int N, int L, int F, int row, const float* xyz, const float* g, float* d_xyz, float* d_feat, hipStream_t st) {
+static int launch_mlp_input_backward(int N, int L, int F, int row, const float* xyz, const float* g, float* d_xyz, float* d_feat, hipStream_t st) {
     if (N < 0 || L < 0 || L > 16 || F < 0 || row < 3 + 6 * L + F || !xyz || !g) return 1;
     if (N == 0) return 0;
     const long long threads = (long long)N * (1 + (F + 3) / 4);
@@ -1209,8 +1209,8 @@ static const char* group_input_check(int N, int n_heads, const SrMlpHeadInput* h
     return nullptr;
 }
 
-const char* launch_mlp_group_input_forward(int N, int n_heads, const SrMlpHeadInput* heads, int F, int TL, const float* xyz, const float* feat,
-                                           const float* time, hipStream_t st) {
+static const char* launch_mlp_group_input_forward(int N, int n_heads, const SrMlpHeadInput* heads, int F, int TL, const float* xyz, const float* feat,
+                                                  const float* time, hipStream_t st) {
     if (const char* why = group_input_check(N, n_heads, heads, F, TL, time != nullptr, false)) return why;
     if (N == 0 || n_heads == 0) return nullptr;
     if (!xyz || (F > 0 && !feat)) return "null pointer (xyz, or features with n_features > 0)";
@@ -1227,8 +1227,8 @@ const char* launch_mlp_group_input_forward(int N, int n_heads, const SrMlpHeadIn
     return nullptr;
 }
 
-const char* launch_mlp_group_input_backward(int N, int n_heads, const SrMlpHeadInput* heads, int F, const float* xyz, float* d_xyz, float* d_feat,
-                                            hipStream_t st) {
+static const char* launch_mlp_group_input_backward(int N, int n_heads, const SrMlpHeadInput* heads, int F, const float* xyz, float* d_xyz, float* d_feat,
+                                                   hipStream_t st) {
     if (const char* why = group_input_check(N, n_heads, heads, F, 0, false, true)) return why;
     if (N == 0 || n_heads == 0 || (!d_xyz && !d_feat)) return nullptr;
     if (!xyz) return "null pointer (xyz)";
@@ -1262,7 +1262,7 @@ static const char* group_output_check(int N, int n_heads, const SrMlpHeadOutput*
     return nullptr;
 }
 
-const char* launch_mlp_group_output(int N, int n_heads, const SrMlpHeadOutput* heads, hipStream_t st) {
+static const char* launch_mlp_group_output(int N, int n_heads, const SrMlpHeadOutput* heads, hipStream_t st) {
     if (const char* why = group_output_check(N, n_heads, heads, false)) return why;
     if (N == 0 || n_heads == 0) return nullptr;
     GroupOutK P;
@@ -1274,7 +1274,7 @@ const char* launch_mlp_group_output(int N, int n_heads, const SrMlpHeadOutput* h
     return nullptr;
 }
 
-const char* launch_mlp_group_top_gradient(int N, int n_heads, const SrMlpHeadOutput* heads, float slope, hipStream_t st) {
+static const char* launch_mlp_group_top_gradient(int N, int n_heads, const SrMlpHeadOutput* heads, float slope, hipStream_t st) {
     if (const char* why = group_output_check(N, n_heads, heads, true)) return why;
     if (N == 0 || n_heads == 0) return nullptr;
     GroupOutK P;
@@ -1290,3 +1290,137 @@ const char* launch_mlp_group_top_gradient(int N, int n_heads, const SrMlpHeadOut
 }
 
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+static int mlp_chain_entry(const char* name, bool bf16, int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    if (n_points < 0 || !ops) return fail(std::string("bad arguments to ") + name);
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail(std::string(name) + ": negative_slope must be in [0, 1)");
+    if (sr::launch_mlp_chain(n_points, hidden_tiles, n_ops, ops, negative_slope, bf16, static_cast<hipStream_t>(hip_stream)))
+        return fail(std::string(name) + ": unsupported op list (hidden_tiles 4 or 8, <= SR_MLP_MAX_OPS ops, even input tile counts, "
+                    "16-byte aligned rows wide enough for the tiles read)");
+    return check_hip(hipGetLastError(), bf16 ? "mlp_chain_bf16" : "mlp_chain");
+}
+
+static int mlp_pack_entry(const char* name, bool bf16, int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return fail(std::string("bad arguments to ") + name);
+    if (sr::launch_mlp_pack(n_jobs, jobs, bf16, static_cast<hipStream_t>(hip_stream)))
+        return fail(std::string(name) + ": unsupported job (<= SR_MLP_MAX_PACK_JOBS jobs; mem_pad multiple of 32, reg_width of 16, even tile "
+                    "count; counts within their padded sizes; 16-byte aligned destination)");
+    return check_hip(hipGetLastError(), bf16 ? "mlp_pack_bf16" : "mlp_pack");
+}
+
+int sr_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    return mlp_chain_entry("sr_mlp_chain", false, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+}
+
+int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    return mlp_chain_entry("sr_mlp_chain_bf16", true, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+}
+
+// `empty`: the call was valid and launched nothing (no device is needed for that)
+static int mlp_group_entry(const char* name, const char* why, const char* kernel, bool empty) {
+    if (why) return fail(std::string(name) + ": " + why);
+    if (empty) return 0;
+    return check_hip(hipGetLastError(), kernel);
+}
+
+int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_chain_group", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, false,
+                                                                            static_cast<hipStream_t>(hip_stream)), "mlp_chain_group", n_points == 0 || n_nets == 0);
+}
+
+int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_chain_group_bf16", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, true,
+                                                                                 static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16", n_points == 0 || n_nets == 0);
+}
+
+int sr_mlp_group_input_forward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, int time_multires, const float* xyz,
+                               const float* features, const float* time, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_input_forward", sr::launch_mlp_group_input_forward(n_points, n_heads, heads, n_features, time_multires, xyz,
+                           features, time, static_cast<hipStream_t>(hip_stream)), "mlp_group_input_forward", n_points == 0 || n_heads == 0);
+}
+
+int sr_mlp_group_input_backward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, const float* xyz, float* dL_dxyz,
+                                float* dL_dfeatures, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_input_backward", sr::launch_mlp_group_input_backward(n_points, n_heads, heads, n_features, xyz, dL_dxyz,
+                           dL_dfeatures, static_cast<hipStream_t>(hip_stream)), "mlp_group_input_backward", n_points == 0 || n_heads == 0 || (!dL_dxyz && !dL_dfeatures));
+}
+
+int sr_mlp_group_output(int n_points, int n_heads, const SrMlpHeadOutput* heads, void* hip_stream) {
+    return mlp_group_entry("sr_mlp_group_output", sr::launch_mlp_group_output(n_points, n_heads, heads, static_cast<hipStream_t>(hip_stream)),
+                           "mlp_group_output", n_points == 0 || n_heads == 0);
+}
+
+int sr_mlp_group_top_gradient(int n_points, int n_heads, const SrMlpHeadOutput* heads, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_group_top_gradient: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_group_top_gradient", sr::launch_mlp_group_top_gradient(n_points, n_heads, heads, negative_slope,
+                           static_cast<hipStream_t>(hip_stream)), "mlp_group_top_gradient", n_points == 0 || n_heads == 0);
+}
+
+int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    return mlp_pack_entry("sr_mlp_pack", false, n_jobs, jobs, hip_stream);
+}
+
+int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    return mlp_pack_entry("sr_mlp_pack_bf16", true, n_jobs, jobs, hip_stream);
+}
+
+size_t sr_mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs) {
+    if (!jobs) return 0;
+    return sr::mlp_weight_grad_workspace(n_points, n_jobs, jobs);
+}
+
+int sr_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!jobs || n_points < 1) return fail("bad arguments to sr_mlp_weight_grad");
+    if (sr::launch_mlp_weight_grad(n_points, n_jobs, jobs, workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream)))
+        return fail("sr_mlp_weight_grad: unsupported job list (<= SR_MLP_MAX_GRAD_JOBS jobs, <= SR_MLP_MAX_GRAD_TASKS 64x64 blocks, "
+                    "16-byte aligned rows with strides that are multiples of 4) or workspace too small");
+    return check_hip(hipGetLastError(), "mlp_weight_grad");
+}
+
+int sr_mlp_input_forward(int n_points, int multires, int n_features, int time_multires, int row, const float* xyz, const float* features,
+                         const float* time, float* x0, void* hip_stream) {
+    if (sr::launch_mlp_input_forward(n_points, multires, n_features, time_multires, row, xyz, features, time, x0, static_cast<hipStream_t>(hip_stream)))
+        return fail("bad arguments to sr_mlp_input_forward (row a multiple of 4 and >= 3 + 6 multires + n_features [+ 1 + 2 time_multires "
+                    "with a time], both multires <= 16)");
+    return check_hip(hipGetLastError(), "mlp_input_forward");
+}
+
+int sr_mlp_top_gradient(int n_points, int out_features, int row, const float* y, const float* dL_dy, float negative_slope, float* g,
+                        void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_top_gradient: negative_slope must be in [0, 1)");
+    if (sr::launch_mlp_top_gradient(n_points, out_features, row, y, dL_dy, negative_slope, g, static_cast<hipStream_t>(hip_stream)))
+        return fail("bad arguments to sr_mlp_top_gradient (row a multiple of 4 and >= out_features)");
+    return check_hip(hipGetLastError(), "mlp_top_gradient");
+}
+
+int sr_mlp_input_backward(int n_points, int multires, int n_features, int row, const float* xyz, const float* dL_dx0, float* dL_dxyz,
+                          float* dL_dfeatures, void* hip_stream) {
+    if (sr::launch_mlp_input_backward(n_points, multires, n_features, row, xyz, dL_dx0, dL_dxyz, dL_dfeatures, static_cast<hipStream_t>(hip_stream)))
+        return fail("bad arguments to sr_mlp_input_backward");
+    return check_hip(hipGetLastError(), "mlp_input_backward");
+}
+
+int sr_resfield_compose(int n_jobs, const SrResFieldJob* jobs, const long long* frame, void* hip_stream) {
+    if (sr::launch_resfield_compose(n_jobs, jobs, frame, static_cast<hipStream_t>(hip_stream)))
+        return fail("sr_resfield_compose: unsupported job list (<= SR_RESFIELD_MAX_JOBS jobs, count a multiple of 4, 16-byte aligned "
+                    "arrays, 1 <= rank <= SR_RESFIELD_MAX_RANK) or null frame pointer");
+    return check_hip(hipGetLastError(), "resfield_compose");
+}
+
+size_t sr_resfield_backward_workspace(int n_jobs, const SrResFieldJob* jobs) { return sr::resfield_backward_workspace(n_jobs, jobs); }
+
+int sr_resfield_backward(int n_jobs, const SrResFieldJob* jobs, const long long* frame, void* workspace, size_t workspace_bytes,
+                         void* hip_stream) {
+    if (sr::launch_resfield_backward(n_jobs, jobs, frame, workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream)))
+        return fail("sr_resfield_backward: unsupported job list, null frame pointer or workspace too small");
+    return check_hip(hipGetLastError(), "resfield_backward");
+}
+
+}  // extern "C"

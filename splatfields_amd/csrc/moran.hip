@@ -24,11 +24,23 @@
 //           from the means of the forward on the device.
 //
 // No floating-point atomics anywhere: values and gradients are bit-identical from call to call.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 #include <type_traits>
 
 namespace sr {
+
+constexpr int kMoranMaxTensors = SR_MORAN_MAX_TENSORS;
+// the feature tensors of one call: x[t] is [rows, width[t]]; dx[t] (backward) may be NULL; offset[] are the running widths,
+// edge_offset[] the running widths of the tensors with a dx: only those have columns in the per-edge buffer
+struct MoranTensors {
+    int count, channels, edge_channels;
+    const float* x[kMoranMaxTensors]; float* dx[kMoranMaxTensors];
+    int width[kMoranMaxTensors], offset[kMoranMaxTensors], edge_offset[kMoranMaxTensors];
+};
+// where the K x K spatial weights of item p come from: `points` (c_ab from the distances of the K gathered positions) or
+// `weight` [n, K, K] given; nn_ix NULL: item p's rows are p K .. p K + K - 1; order NULL: items in index order
+struct MoranSource { int n, k; float eps; const float* points; const float* weight; const int* nn_ix; const uint32_t* order; };
 
 namespace {
 
@@ -360,8 +372,6 @@ float* edge_q_of(void* edges, int n, int k, int channels) {
     return reinterpret_cast<float*>(static_cast<char*>(edges) + align_up((size_t)n * k * channels * sizeof(float), 256));
 }
 
-}  // namespace
-
 size_t moran_workspace_bytes(int n, int n_tensors) {
     if (n <= 0 || n_tensors <= 0 || n_tensors > kMoranMaxTensors) return 0;
     return align_up(moran_blocks(n) * n_tensors * sizeof(float), 256);
@@ -417,4 +427,101 @@ void launch_moran_weights_backward(const MoranSource& s, const uint32_t* rev_sta
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, edge_q, d_points);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+namespace {
+
+// the checks that sr_moran_forward and sr_moran_backward share; fills the kernel-side descriptions
+int open_moran(const char* who, int n, int k, float eps, const float* points, const float* weight, const int* nn_ix, const unsigned* order,
+               int n_tensors, const float* const* features, const int* widths, sr::MoranSource* s, sr::MoranTensors* t) {
+    const std::string name(who);
+    if (n <= 0) return fail("bad arguments to " + name + ": sizes must be positive");
+    if ((points == nullptr) == (weight == nullptr)) return fail(name + ": points or weight (exactly one of them)");
+    if (k < (points ? sr::kKnnMinK : 1) || k > sr::kKnnMaxK) return fail("bad arguments to " + name + ": k must be 2 .. 8 (1 .. 8 with weight)");
+    if (points && n < k) return fail("bad arguments to " + name + ": fewer points than neighbours (n < k)");
+    if (points && !nn_ix) return fail("null pointer in " + name + ": points need nn_ix");
+    if (n_tensors < 1) return fail(name + ": at least one feature tensor");
+    if (n_tensors > sr::kMoranMaxTensors) return fail(name + ": at most 8 feature tensors in one call");
+    if (!features || !widths) return fail("null pointer in " + name);
+    *s = sr::MoranSource{n, k, eps, points, weight, nn_ix, order};
+    *t = sr::MoranTensors{};
+    t->count = n_tensors;
+    long long channels = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (widths[i] <= 0) return fail("bad arguments to " + name + ": sizes must be positive");
+        if (!features[i]) return fail("null pointer in " + name);
+        t->x[i] = features[i]; t->width[i] = widths[i]; t->offset[i] = (int)channels;
+        channels += widths[i];
+        if (channels > 0x7fffffff / sr::kKnnMaxK) return fail("too many channels for " + name);
+    }
+    if ((long long)n > 0x7fffffff / (3 * sr::kKnnMaxK)) return fail("too many items for " + name);
+    t->channels = (int)channels;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sr_moran_workspace_bytes(int n, int n_tensors) { return sr::moran_workspace_bytes(n, n_tensors); }
+
+size_t sr_moran_edges_bytes(int n, int k, int channels) { return sr::moran_edges_bytes(n, k, channels); }
+
+int sr_moran_forward(int n, int k, float eps, const float* points, const float* weight, const int* nn_ix, const unsigned* order, int n_tensors,
+                     const float* const* features, const int* widths, void* workspace, float* out, void* hip_stream) {
+    sr::MoranSource s; sr::MoranTensors t;
+    SR_TRY(open_moran("sr_moran_forward", n, k, eps, points, weight, nn_ix, order, n_tensors, features, widths, &s, &t));
+    if (!workspace || !out) return fail("null pointer in sr_moran_forward");
+    sr::launch_moran_forward(s, t, workspace, out, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "moran_forward");
+}
+
+int sr_moran_backward(int n, int k, float eps, const float* points, const float* weight, const int* nn_ix, const unsigned* order,
+                      const unsigned* rev_start, const unsigned* rev_edges, int n_tensors, const float* const* features, const int* widths,
+                      const float* out, const float* upstream, void* edges, float* const* dL_dfeatures, float* dL_dpoints, float* dL_dweight,
+                      void* hip_stream) {
+    sr::MoranSource s; sr::MoranTensors t;
+    SR_TRY(open_moran("sr_moran_backward", n, k, eps, points, weight, nn_ix, order, n_tensors, features, widths, &s, &t));
+    if (!upstream || !edges || !dL_dfeatures) return fail("null pointer in sr_moran_backward");
+    if (dL_dpoints && !points) return fail("sr_moran_backward: dL_dpoints without points");
+    if (dL_dweight && !weight) return fail("sr_moran_backward: dL_dweight without weight");
+    if ((rev_start == nullptr) != (rev_edges == nullptr)) return fail("sr_moran_backward: rev_start and rev_edges go together (both or neither)");
+    if (nn_ix && !rev_start) return fail("null pointer in sr_moran_backward: nn_ix needs the reverse adjacency");
+    if (!nn_ix && rev_start) return fail("sr_moran_backward: a reverse adjacency without nn_ix");
+    for (int i = 0; i < n_tensors; ++i) {
+        t.dx[i] = dL_dfeatures[i];
+        t.edge_offset[i] = t.edge_channels;
+        if (t.dx[i]) t.edge_channels += t.width[i];
+    }
+    sr::launch_moran_backward(s, t, rev_start, rev_edges, out, upstream, edges, dL_dpoints, dL_dweight, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "moran_backward");
+}
+
+int sr_moran_weights(int n, int k, float eps, const float* points, const int* nn_ix, float* weights, void* hip_stream) {
+    if (n <= 0) return fail("bad arguments to sr_moran_weights: sizes must be positive");
+    if (k < sr::kKnnMinK || k > sr::kKnnMaxK) return fail("bad arguments to sr_moran_weights: k must be 2 .. 8");
+    if (n < k) return fail("bad arguments to sr_moran_weights: fewer points than neighbours (n < k)");
+    if (n > 0x7fffffff / (3 * sr::kKnnMaxK)) return fail("too many points for sr_moran_weights");
+    if (!points || !nn_ix || !weights) return fail("null pointer in sr_moran_weights");
+    sr::launch_moran_weights(sr::MoranSource{n, k, eps, points, nullptr, nn_ix, nullptr}, weights, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "moran_weights");
+}
+
+int sr_moran_weights_backward(int n, int k, float eps, const float* points, const int* nn_ix, const unsigned* rev_start, const unsigned* rev_edges,
+                              const float* dL_dweights, void* edges, float* dL_dpoints, void* hip_stream) {
+    if (n <= 0) return fail("bad arguments to sr_moran_weights_backward: sizes must be positive");
+    if (k < sr::kKnnMinK || k > sr::kKnnMaxK) return fail("bad arguments to sr_moran_weights_backward: k must be 2 .. 8");
+    if (n < k) return fail("bad arguments to sr_moran_weights_backward: fewer points than neighbours (n < k)");
+    if (n > 0x7fffffff / (3 * sr::kKnnMaxK)) return fail("too many points for sr_moran_weights_backward");
+    if (!points || !nn_ix || !rev_start || !rev_edges || !dL_dweights || !edges || !dL_dpoints) return fail("null pointer in sr_moran_weights_backward");
+    sr::launch_moran_weights_backward(sr::MoranSource{n, k, eps, points, nullptr, nn_ix, nullptr}, rev_start, rev_edges, dL_dweights, edges,
+                                      dL_dpoints, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "moran_weights_backward");
+}
+
+}  // extern "C"

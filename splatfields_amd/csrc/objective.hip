@@ -25,7 +25,7 @@
 // The centred norm needs the mean before its pass: every workgroup of that pass adds the coordinate partials itself, in the
 // same order, which saves the launch a separate mean kernel would take.  Forward: 2 launches, 3 with the centred norm; depth
 // L1: 2.  Backward: 1 each.  No floating-point atomics, no host wait: identical bits from call to call.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 
 namespace sr {
@@ -382,8 +382,6 @@ DepthDims depth_dims(int batch, int H, int W, const float* depth, const float* g
     return d;
 }
 
-}  // namespace
-
 size_t splat_reg_workspace_bytes(long long n) {
     return n > 0 ? align_up(sizeof(double) * kSumCount * kObjMaxBlocks, 256) : 0;
 }
@@ -434,4 +432,72 @@ void launch_depth_l1_backward(int batch, int H, int W, const float* depth, const
                        per_item ? 1 : 0, grad);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::any_unaligned4;
+
+extern "C" {
+
+size_t sr_splat_reg_workspace_bytes(int n_splats) { return sr::splat_reg_workspace_bytes(n_splats); }
+
+int sr_splat_reg_forward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                         double lambda_opacity, void* workspace, float* out, void* hip_stream) {
+    if (n_splats < 0) return fail("bad arguments to sr_splat_reg_forward: negative splat count");
+    if (!(lambda_norm == lambda_norm) || !(lambda_norm_mean == lambda_norm_mean) || !(lambda_opacity == lambda_opacity))
+        return fail("bad arguments to sr_splat_reg_forward: a weight is NaN");
+    if (n_splats == 0) return 0;
+    if (!workspace || !out) return fail("null pointer in sr_splat_reg_forward");
+    if ((lambda_norm != 0.0 || lambda_norm_mean != 0.0) && !means3D) return fail("null pointer in sr_splat_reg_forward: means3D is read by the norm terms");
+    if (lambda_opacity != 0.0 && !opacity) return fail("null pointer in sr_splat_reg_forward: opacity is read by the opacity term");
+    if (any_unaligned4(means3D, opacity)) return fail("sr_splat_reg_forward: tensors must be 4-byte aligned");
+    sr::launch_splat_reg_forward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, workspace, out,
+                                 static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "splat_reg_forward");
+}
+
+int sr_splat_reg_backward(int n_splats, const float* means3D, const float* opacity, double lambda_norm, double lambda_norm_mean,
+                          double lambda_opacity, const float* out, const float* upstream, float* dL_dmeans3D, float* dL_dopacity,
+                          void* hip_stream) {
+    if (n_splats < 0) return fail("bad arguments to sr_splat_reg_backward: negative splat count");
+    if (!(lambda_norm == lambda_norm) || !(lambda_norm_mean == lambda_norm_mean) || !(lambda_opacity == lambda_opacity))
+        return fail("bad arguments to sr_splat_reg_backward: a weight is NaN");
+    if (n_splats == 0 || (!dL_dmeans3D && !dL_dopacity)) return 0;
+    if (!upstream) return fail("null pointer in sr_splat_reg_backward");
+    if (dL_dmeans3D && !means3D) return fail("null pointer in sr_splat_reg_backward: dL_dmeans3D without means3D");
+    if (dL_dopacity && !opacity) return fail("null pointer in sr_splat_reg_backward: dL_dopacity without opacity");
+    if (dL_dmeans3D && lambda_norm_mean != 0.0 && !out) return fail("null pointer in sr_splat_reg_backward: the centred norm needs the mean in `out` of the forward");
+    if (any_unaligned4(means3D, opacity, dL_dmeans3D, dL_dopacity)) return fail("sr_splat_reg_backward: tensors must be 4-byte aligned");
+    sr::launch_splat_reg_backward(n_splats, means3D, opacity, lambda_norm, lambda_norm_mean, lambda_opacity, out, upstream, dL_dmeans3D,
+                                  dL_dopacity, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "splat_reg_backward");
+}
+
+size_t sr_depth_l1_workspace_bytes(int batch, int height, int width) { return sr::depth_l1_workspace_bytes(batch, height, width); }
+
+int sr_depth_l1_forward(int batch, int height, int width, const float* depth, const float* gt_depth, void* workspace, float* out,
+                        void* hip_stream) {
+    if (batch < 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_depth_l1_forward: the image size must be positive and the batch not negative");
+    if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_forward");
+    if (batch == 0) return 0;
+    if (!depth || !gt_depth || !workspace || !out) return fail("null pointer in sr_depth_l1_forward");
+    if (any_unaligned4(depth, gt_depth)) return fail("sr_depth_l1_forward: tensors must be 4-byte aligned");
+    sr::launch_depth_l1_forward(batch, height, width, depth, gt_depth, workspace, out, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "depth_l1_forward");
+}
+
+int sr_depth_l1_backward(int batch, int height, int width, const float* depth, const float* gt_depth, const float* upstream,
+                         int upstream_per_item, float* dL_ddepth, void* hip_stream) {
+    if (batch < 0 || height <= 0 || width <= 0) return fail("bad arguments to sr_depth_l1_backward: the image size must be positive and the batch not negative");
+    if (!sr::depth_l1_shape_ok(batch, height, width)) return fail("too many items for sr_depth_l1_backward");
+    if (batch == 0) return 0;
+    if (!depth || !gt_depth || !upstream || !dL_ddepth) return fail("null pointer in sr_depth_l1_backward");
+    if (any_unaligned4(depth, gt_depth, dL_ddepth)) return fail("sr_depth_l1_backward: tensors must be 4-byte aligned");
+    sr::launch_depth_l1_backward(batch, height, width, depth, gt_depth, upstream, upstream_per_item != 0, dL_ddepth,
+                                 static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "depth_l1_backward");
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 // Activations are never stored: SiLU(gamma (x - mean) rstd + beta) is recomputed where it is an operand.  Out-of-range taps are
 // zero AFTER the activation (the padding belongs to the activated, upsampled tensor).
 // No floating-point atomics; reductions are LDS trees and fixed-order loops over partials.
-#include "kernels.h"
+#include "host_api.h"
 #include "reduce.h"
 
 namespace sr {
@@ -490,8 +490,6 @@ ConvArgs make_conv_args(int cin, int cout, int hin, int win, int groups, int fla
 
 int gn_chunks(long long elems) { return (int)((elems + kGnChunk - 1) / kGnChunk); }
 
-}  // namespace
-
 bool plane_channels_ok(int c) { return c >= 8 && c <= kMaxCh && c % 8 == 0; }
 bool plane_conv_shape_ok(int cin, int cout, int hin, int win, int flags) {
     if (!plane_channels_ok(cin) || !plane_channels_ok(cout) || hin <= 0 || win <= 0 || hin > 4096 || win > 4096) return false;
@@ -575,4 +573,115 @@ void launch_gn_silu_backward_apply(int n, const SrPlaneJob* jobs, int channels, 
                        static_cast<const double*>(ws));
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::StageTimer;
+
+extern "C" {
+
+static int plane_jobs_ok(const char* who, int n_planes, const SrPlaneJob* jobs) {
+    if (!jobs) return fail(std::string("null pointer in ") + who + ": jobs");
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS) return fail(std::string("bad arguments to ") + who + ": n_planes must be 1 .. SR_PLANE_MAX_JOBS (8)");
+    return 0;
+}
+
+size_t sr_groupnorm_stats_workspace(int n_planes, int channels, int groups, int height, int width) {
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS || !sr::plane_gn_shape_ok(channels, groups, height, width)) return 0;
+    return sr::gn_stats_workspace(n_planes, channels, groups, height, width);
+}
+
+int sr_groupnorm_stats(int n_planes, const SrPlaneJob* jobs, int channels, int groups, int height, int width, float eps, void* workspace,
+                       void* hip_stream) {
+    SR_TRY(plane_jobs_ok("sr_groupnorm_stats", n_planes, jobs));
+    if (!sr::plane_gn_shape_ok(channels, groups, height, width))
+        return fail("sr_groupnorm_stats: channels in 1..64, groups must divide channels, height * width < 2^24");
+    if (!workspace) return fail("null pointer in sr_groupnorm_stats: workspace");
+    for (int i_ = 0; i_ < n_planes; ++i_) { const SrPlaneJob& j = jobs[i_]; SR_PLANE_NEED("sr_groupnorm_stats", j.x && j.stats); }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_gn_stats_partial(n_planes, jobs, channels, groups, height, width, workspace, st); }
+    { StageTimer t_(0, st); sr::launch_gn_stats_final(n_planes, jobs, channels, groups, height, width, eps, workspace, st); }
+    return check_hip(hipGetLastError(), "groupnorm_stats");
+}
+
+static int conv_shape_check(const char* who, int cin, int cout, int h_in, int w_in, int groups, int flags) {
+    if (!sr::plane_conv_shape_ok(cin, cout, h_in, w_in, flags))
+        return fail(std::string(who) + ": cin and cout must be multiples of 8 in 8..64, the output below 2^24 pixels, flags SR_CONV_* bits");
+    if ((flags & SR_CONV_PROLOGUE) && (groups < 1 || cin % groups != 0)) return fail(std::string(who) + ": groups must divide cin");
+    return 0;
+}
+
+int sr_conv3x3_forward(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags, void* hip_stream) {
+    SR_TRY(plane_jobs_ok("sr_conv3x3_forward", n_planes, jobs));
+    SR_TRY(conv_shape_check("sr_conv3x3_forward", cin, cout, h_in, w_in, groups, flags));
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrPlaneJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_conv3x3_forward", j.x && j.weight && j.out);
+        if (flags & SR_CONV_PROLOGUE) SR_PLANE_NEED("sr_conv3x3_forward", j.gamma && j.beta && j.stats);
+        if (flags & SR_CONV_RESIDUAL) SR_PLANE_NEED("sr_conv3x3_forward", j.residual);
+        if (flags & SR_CONV_SILU_OUT) SR_PLANE_NEED("sr_conv3x3_forward", j.pre);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_conv3x3_forward(n_planes, jobs, cin, cout, h_in, w_in, groups, flags, st); }
+    return check_hip(hipGetLastError(), "conv3x3_forward");
+}
+
+int sr_conv3x3_backward_data(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int flags, void* hip_stream) {
+    SR_TRY(plane_jobs_ok("sr_conv3x3_backward_data", n_planes, jobs));
+    SR_TRY(conv_shape_check("sr_conv3x3_backward_data", cin, cout, h_in, w_in, 1, flags & ~SR_CONV_PROLOGUE));
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrPlaneJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_conv3x3_backward_data", j.dy && j.weight && j.dx);
+        if (flags & SR_CONV_SILU_OUT) SR_PLANE_NEED("sr_conv3x3_backward_data", j.pre);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_conv3x3_backward_data(n_planes, jobs, cin, cout, h_in, w_in, flags, st); }
+    return check_hip(hipGetLastError(), "conv3x3_backward_data");
+}
+
+size_t sr_groupnorm_silu_backward_workspace(int n_planes, int channels, int height, int width) {
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS || !sr::plane_gn_shape_ok(channels, 1, height, width)) return 0;
+    return sr::gn_silu_backward_workspace(n_planes, channels, height, width);
+}
+
+int sr_groupnorm_silu_backward(int n_planes, const SrPlaneJob* jobs, int channels, int groups, int height, int width, float eps,
+                               void* workspace, void* hip_stream) {
+    SR_TRY(plane_jobs_ok("sr_groupnorm_silu_backward", n_planes, jobs));
+    if (!sr::plane_gn_shape_ok(channels, groups, height, width))
+        return fail("sr_groupnorm_silu_backward: channels in 1..64, groups must divide channels, height * width < 2^24");
+    if (!workspace) return fail("null pointer in sr_groupnorm_silu_backward: workspace");
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrPlaneJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_groupnorm_silu_backward", j.dx && j.x && j.gamma && j.beta && j.stats && j.dx_out && j.dgamma && j.dbeta);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_gn_silu_backward_partial(n_planes, jobs, channels, groups, height, width, eps, workspace, st); }
+    { StageTimer t_(6, st); sr::launch_gn_silu_backward_apply(n_planes, jobs, channels, groups, height, width, eps, workspace, st); }
+    return check_hip(hipGetLastError(), "groupnorm_silu_backward");
+}
+
+size_t sr_conv3x3_weight_grad_workspace(int n_planes, int cin, int cout, int h_in, int w_in, int flags) {
+    if (n_planes < 1 || n_planes > SR_PLANE_MAX_JOBS || !sr::plane_conv_shape_ok(cin, cout, h_in, w_in, flags)) return 0;
+    return sr::conv3x3_weight_grad_workspace(n_planes, cin, cout, h_in, w_in, flags);
+}
+
+int sr_conv3x3_weight_grad(int n_planes, const SrPlaneJob* jobs, int cin, int cout, int h_in, int w_in, int groups, int flags, void* workspace,
+                           void* hip_stream) {
+    SR_TRY(plane_jobs_ok("sr_conv3x3_weight_grad", n_planes, jobs));
+    SR_TRY(conv_shape_check("sr_conv3x3_weight_grad", cin, cout, h_in, w_in, groups, flags));
+    if (!workspace) return fail("null pointer in sr_conv3x3_weight_grad: workspace");
+    for (int i_ = 0; i_ < n_planes; ++i_) {
+        const SrPlaneJob& j = jobs[i_];
+        SR_PLANE_NEED("sr_conv3x3_weight_grad", j.dy && j.x && j.dweight);
+        if (flags & SR_CONV_PROLOGUE) SR_PLANE_NEED("sr_conv3x3_weight_grad", j.gamma && j.beta && j.stats);
+        if (flags & SR_CONV_SILU_OUT) SR_PLANE_NEED("sr_conv3x3_weight_grad", j.pre);
+    }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_conv3x3_wgrad_partial(n_planes, jobs, cin, cout, h_in, w_in, groups, flags, workspace, st); }
+    { StageTimer t_(6, st); sr::launch_conv3x3_wgrad_reduce(n_planes, jobs, cin, cout, h_in, w_in, flags, workspace, st); }
+    return check_hip(hipGetLastError(), "conv3x3_weight_grad");
+}
+
+}  // extern "C"

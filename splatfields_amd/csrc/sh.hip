@@ -8,7 +8,7 @@
 //
 // Semantics = the SH part of the rasterizer's preprocess (reference utils/sh_utils.py:57-112,
 // extract_geo.py:40-44): dir = normalize(mean - campos), colour = max(sum_k basis_k sh_k + 0.5, 0), gradient zero where clamped.
-#include "kernels.h"
+#include "host_api.h"
 #include "sh_stage.h"
 
 namespace sr {
@@ -179,8 +179,8 @@ __global__ void __launch_bounds__(kBlock) k_sh_backward(int N, int K, int deg, i
     }
 }
 
-void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
-                       unsigned char* clamped, hipStream_t st) {
+static void launch_sh_forward(int N, int K, int deg, const float* means3D, const float* shs, const float* campos, float* colors,
+                              unsigned char* clamped, hipStream_t st) {
     if (N <= 0) return;
     if (K == 16 && deg >= 2)  // below degree 2 only <= 48 of a splat's 192 bytes are needed
         hipLaunchKernelGGL(k_sh_forward<true>, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, N, K, deg, means3D, shs, campos, colors, clamped);
@@ -188,8 +188,8 @@ void launch_sh_forward(int N, int K, int deg, const float* means3D, const float*
         hipLaunchKernelGGL(k_sh_forward<false>, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, N, K, deg, means3D, shs, campos, colors, clamped);
 }
 
-void launch_sh_forward_views(int N, int K, int deg, int V, const float* means3D, const float* shs, const float* campos, float* colors,
-                             float* keep, hipStream_t st) {
+static void launch_sh_forward_views(int N, int K, int deg, int V, const float* means3D, const float* shs, const float* campos, float* colors,
+                                    float* keep, hipStream_t st) {
     if (N <= 0 || V <= 0) return;
     if (K == 16)
         hipLaunchKernelGGL(k_sh_forward_views<true>, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, N, K, deg, V, means3D, shs, campos, colors, keep);
@@ -197,8 +197,8 @@ void launch_sh_forward_views(int N, int K, int deg, int V, const float* means3D,
         hipLaunchKernelGGL(k_sh_forward_views<false>, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, N, K, deg, V, means3D, shs, campos, colors, keep);
 }
 
-void launch_sh_backward(int N, int K, int deg, int V, const float* means3D, const float* shs, const float* campos, const float* dcol,
-                        float scale, float* d_shs, float* d_means, int accumulate_means, hipStream_t st) {
+static void launch_sh_backward(int N, int K, int deg, int V, const float* means3D, const float* shs, const float* campos, const float* dcol,
+                               float scale, float* d_shs, float* d_means, int accumulate_means, hipStream_t st) {
     if (N <= 0) return;
     if (d_shs && K == 16)
         hipLaunchKernelGGL(k_sh_backward<true>, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, st, N, K, deg, V, means3D, shs, campos, dcol,
@@ -209,3 +209,35 @@ void launch_sh_backward(int N, int K, int deg, int V, const float* means3D, cons
 }
 
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+int sr_sh_forward(int n, int sh_coeffs, int sh_degree, const float* means3D, const float* shs, const float* campos,
+                  float* colors, unsigned char* clamped, void* hip_stream) {
+    if (n < 0 || sh_degree < 0 || sh_degree > 3 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1)) return fail("bad arguments to sr_sh_forward");
+    if (n > 0 && (!means3D || !shs || !campos || !colors || !clamped)) return fail("null pointer in sr_sh_forward");
+    sr::launch_sh_forward(n, sh_coeffs, sh_degree, means3D, shs, campos, colors, clamped, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "sh_forward");
+}
+
+int sr_sh_forward_views(int n, int sh_coeffs, int sh_degree, int n_views, const float* means3D, const float* shs, const float* campos,
+                        float* colors, float* keep, void* hip_stream) {
+    if (n < 0 || n_views < 0 || sh_degree < 0 || sh_degree > 3 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1)) return fail("bad arguments to sr_sh_forward_views");
+    if (n > 0 && n_views > 0 && (!means3D || !shs || !campos || !colors)) return fail("null pointer in sr_sh_forward_views");
+    sr::launch_sh_forward_views(n, sh_coeffs, sh_degree, n_views, means3D, shs, campos, colors, keep, static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "sh_forward_views");
+}
+
+int sr_sh_backward(int n, int sh_coeffs, int sh_degree, int n_views, const float* means3D, const float* shs, const float* campos,
+                   const float* dL_dcolors, float scale, float* dL_dshs, float* dL_dmeans3D, int accumulate_means, void* hip_stream) {
+    if (n < 0 || n_views < 0 || sh_degree < 0 || sh_degree > 3 || sh_coeffs < (sh_degree + 1) * (sh_degree + 1)) return fail("bad arguments to sr_sh_backward");
+    if (n > 0 && n_views > 0 && (!means3D || !shs || !campos || !dL_dcolors)) return fail("null pointer in sr_sh_backward");
+    sr::launch_sh_backward(n, sh_coeffs, sh_degree, n_views, means3D, shs, campos, dL_dcolors, scale, dL_dshs, dL_dmeans3D, accumulate_means,
+                           static_cast<hipStream_t>(hip_stream));
+    return check_hip(hipGetLastError(), "sh_backward");
+}
+
+}  // extern "C"

@@ -21,7 +21,7 @@
 // tile of 64-bit accumulators in LDS (ds_add_u64) and writes the tile's gradient out.  The 19 M atomics of a step stay inside
 // the CUs (they were 0.43 ms of device-scope atomics on a 39 MB accumulator, plus its clearing and conversion passes), and
 // because the sums are integer the arbitrary order of a tile's list never reaches the result.
-#include "kernels.h"
+#include "host_api.h"
 
 namespace sr {
 
@@ -277,8 +277,6 @@ __global__ void __launch_bounds__(kBlock) k_tp_backward_points(int N, int C, int
     if (n < N && s == 0) { d_pts[3 * (size_t)n] = d[0]; d_pts[3 * (size_t)n + 1] = d[1]; d_pts[3 * (size_t)n + 2] = d[2]; }
 }
 
-}  // namespace
-
 int launch_triplane_forward(int N, int C, int H, int W, const float* planes_chw, float* planes_hwc, const float* pts, float* out,
                             hipStream_t st) {
     if (C <= 0 || (C & 3) || H <= 0 || W <= 0 || (size_t)H * W > (1u << 30)) return 1;
@@ -349,4 +347,39 @@ int launch_triplane_backward(int N, int C, int H, int W, const float* planes_hwc
     return 0;
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip;
+
+extern "C" {
+
+size_t sr_triplane_backward_workspace(int n_points, int channels, int height, int width) {
+    return sr::triplane_backward_workspace(n_points, channels, height, width);
+}
+
+int sr_triplane_forward(int n_points, int channels, int height, int width, const float* planes, float* planes_texel_major,
+                        const float* points, float* out, void* hip_stream) {
+    if (n_points < 0 || !planes || !planes_texel_major || (n_points > 0 && (!points || !out))) return fail("bad arguments to sr_triplane_forward");
+    if (sr::launch_triplane_forward(n_points, channels, height, width, planes, planes_texel_major, points, out, static_cast<hipStream_t>(hip_stream)))
+        return fail("sr_triplane_forward: channels must be a positive multiple of 4, height * width <= 2^30");
+    return check_hip(hipGetLastError(), "triplane_forward");
+}
+
+int sr_triplane_backward(int n_points, int channels, int height, int width, const float* planes_texel_major, const float* points,
+                         const float* dL_dout, float* dL_dplanes, float* dL_dpoints, void* workspace, void* hip_stream) {
+    if (n_points < 0 || !planes_texel_major || (n_points > 0 && (!points || !dL_dout)))
+        return fail("bad arguments to sr_triplane_backward");
+    // the size limits are checked before the workspace: a caller that sized it with sr_triplane_backward_workspace has none
+    // (0 bytes) exactly when the sizes are unsupported, and is told which limit it hit
+    const int rc = sr::launch_triplane_backward(n_points, channels, height, width, planes_texel_major, points, dL_dout, dL_dplanes, dL_dpoints,
+                                                workspace, static_cast<hipStream_t>(hip_stream));
+    if (rc == 1) return fail("sr_triplane_backward: channels must be a positive multiple of 4 (with dL_dplanes: in 4..128), height * width <= 2^30, 12 n_points < 2^32");
+    if (rc == 3) return fail("sr_triplane_backward: dL_dplanes needs a workspace of sr_triplane_backward_workspace bytes");
+    if (rc) return fail("sr_triplane_backward: clearing the tile counters failed");
+    return check_hip(hipGetLastError(), "triplane_backward");
+}
+
+}  // extern "C"

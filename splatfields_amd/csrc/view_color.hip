@@ -18,7 +18,7 @@
 // re-derives r_v and z[v] from it with the same three FMAs instead of a second pass over W feature.  The only sums over points
 // are the nine entries of dW[:, F:] and the three of db, one block_sum (reduce.h) each per workgroup, left in `workspace` as
 // doubles for the caller to add in workgroup order (dW[:, :F] is sr_mlp_weight_grad's).  No atomics, no host wait.
-#include "kernels.h"
+#include "host_api.h"
 #include "point_tile.h"
 #include "reduce.h"
 
@@ -198,8 +198,6 @@ void view_launch(const ViewColorK& k, hipStream_t st) {
     else hipLaunchKernelGGL(k_view_color_forward, dim3(blocks), dim3(kBlock), lds, st, k);
 }
 
-}  // namespace
-
 const char* view_color_shape_error(int mode, long long n_points, int width, int n_views) {
     if (mode != SR_VIEW_FROM_CAMERAS && mode != SR_VIEW_DIRS_GIVEN) return "unknown mode";
     if (width < 4 || (width & 3) || width > SR_VIEW_MAX_WIDTH) return "width must be a multiple of 4 in 4 .. SR_VIEW_MAX_WIDTH";
@@ -233,4 +231,52 @@ void launch_view_color_backward(int mode, long long n, int width, int n_views, c
     view_launch<true>(k, st);
 }
 
+}  // namespace
+
 }  // namespace sr
+
+// ---- C entry points (include/splatraster.h): what is refused on the host, then the launchers above --------------------
+using sr::fail; using sr::check_hip; using sr::any_unaligned4; using sr::StageTimer;
+
+extern "C" {
+
+size_t sr_view_color_saved_bytes(long long n_points, int width, int n_views) {
+    return sr::view_color_shape_error(SR_VIEW_FROM_CAMERAS, n_points, width, n_views) ? 0 : sr::view_color_saved_bytes(n_points);
+}
+
+size_t sr_view_color_workspace_bytes(long long n_points, int width, int n_views) {
+    return sr::view_color_shape_error(SR_VIEW_FROM_CAMERAS, n_points, width, n_views) ? 0 : sr::view_color_workspace_bytes(n_points);
+}
+
+int sr_view_color_forward(int mode, long long n_points, int width, int n_views, const float* feature, const float* means3D,
+                          const float* campos_or_dirs, const float* weight, const float* bias, float* colours, void* saved,
+                          void* hip_stream) {
+    if (const char* why = sr::view_color_shape_error(mode, n_points, width, n_views)) return fail(std::string("sr_view_color_forward: ") + why);
+    if (n_points == 0) return 0;
+    if (!feature || !campos_or_dirs || !weight || !bias || !colours) return fail("null pointer in sr_view_color_forward");
+    if (mode == SR_VIEW_FROM_CAMERAS && !means3D) return fail("null pointer in sr_view_color_forward: the camera mode reads means3D");
+    if (((reinterpret_cast<uintptr_t>(feature) | reinterpret_cast<uintptr_t>(weight)) & 15u) || (reinterpret_cast<uintptr_t>(saved) & 7u) ||
+        any_unaligned4(means3D, campos_or_dirs, bias, colours))
+        return fail("sr_view_color_forward: feature and weight must be 16-byte aligned, saved 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(0, st); sr::launch_view_color_forward(mode, n_points, width, n_views, feature, means3D, campos_or_dirs, weight, bias, colours, saved, st); }
+    return check_hip(hipGetLastError(), "view_color_forward");
+}
+
+int sr_view_color_backward(int mode, long long n_points, int width, int n_views, const float* means3D, const float* campos_or_dirs,
+                           const float* weight, const void* saved, const float* dL_dcolours, float* dL_dfeature, float* dL_dpos,
+                           float* dL_dzsum, void* workspace, void* hip_stream) {
+    if (const char* why = sr::view_color_shape_error(mode, n_points, width, n_views)) return fail(std::string("sr_view_color_backward: ") + why);
+    if (n_points == 0) return 0;
+    if (!campos_or_dirs || !weight || !saved || !dL_dcolours || !dL_dzsum || !workspace) return fail("null pointer in sr_view_color_backward");
+    if (mode == SR_VIEW_FROM_CAMERAS && !means3D) return fail("null pointer in sr_view_color_backward: the camera mode reads means3D");
+    if (((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(dL_dfeature) | reinterpret_cast<uintptr_t>(dL_dzsum)) & 15u) ||
+        ((reinterpret_cast<uintptr_t>(saved) | reinterpret_cast<uintptr_t>(workspace)) & 7u) || any_unaligned4(means3D, campos_or_dirs, dL_dcolours, dL_dpos))
+        return fail("sr_view_color_backward: weight, dL_dfeature and dL_dzsum must be 16-byte aligned, saved and workspace 8-byte, the others 4-byte");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    { StageTimer t_(6, st); sr::launch_view_color_backward(mode, n_points, width, n_views, means3D, campos_or_dirs, weight, saved, dL_dcolours, dL_dfeature,
+                                                           dL_dpos, dL_dzsum, workspace, st); }
+    return check_hip(hipGetLastError(), "view_color_backward");
+}
+
+}  // extern "C"

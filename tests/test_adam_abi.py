@@ -8,6 +8,8 @@ import re
 import pytest
 import torch
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -28,15 +30,11 @@ def make_job(p, count=16, row=4, **over):
 
 def test_symbol_struct_and_constant_match_the_header(lib):
     from splatfields_amd import _lib, build
-    header = open(os.path.join(ROOT, "include", "splatraster.h")).read()
+    header = abi_text.header()
     assert "sr_adam_step" in _lib.SYMBOLS and hasattr(lib, "sr_adam_step") and re.search(r"\bsr_adam_step\s*\(", header)
     assert int(re.search(r"#define\s+SR_ADAM_MAX_TENSORS\s+(\d+)", header).group(1)) == _lib.ADAM_MAX_TENSORS
     assert "adam.hip" in build.SOURCES
     assert lib.sr_version() == 4     # additions only: no existing struct or contract changed
-    # the fields of the header's struct, in order, are the binding's
-    body = re.search(r"typedef struct SrAdamJob \{(.*?)\} SrAdamJob;", header, re.S).group(1)
-    names = [n for decl in body.split(";") for n in re.findall(r"\**\s*([a-z_0-9]+)\s*(?:,|$)", decl.strip())]
-    assert names == [f[0] for f in _lib.SrAdamJob._fields_]
     assert C.sizeof(_lib.SrAdamJob) == 4 * 8 + 8 + 4 + 5 * 4      # four pointers, count, row, five floats: no padding
     assert C.sizeof(_lib.SrAdamJob) * _lib.ADAM_MAX_TENSORS < 4096   # the table travels as a kernel argument
 
@@ -78,16 +76,9 @@ def test_nothing_to_do_launches_nothing(lib):
     assert lib.sr_adam_step(1, table, C.c_void_p(C.addressof(mask)), 0, None) == 0      # 0 rows of 4 elements
 
 
-def entry_point_text():
-    api = open(os.path.join(ROOT, "splatfields_amd", "csrc", "api.hip")).read()
-    m = re.search(r"^int sr_adam_step\(.*?^}$", api, re.S | re.M)
-    assert m
-    return m.group(0)
-
-
 def test_the_step_never_waits_and_uses_no_lds_and_no_atomics():
     from splatfields_amd.build import strip_comments
-    text = strip_comments(open(os.path.join(ROOT, "splatfields_amd", "csrc", "adam.hip")).read()) + "\n" + entry_point_text()
+    text = strip_comments(abi_text.source("adam.hip"))        # the kernel, its launcher and sr_adam_step
     assert "k_adam" in text and "sr_adam_step" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMalloc", "atomic", "__shared__",
                  "__syncthreads"):

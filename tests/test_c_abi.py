@@ -7,6 +7,8 @@ import re
 import pytest
 import torch
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -18,9 +20,7 @@ def lib():
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "splatraster.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sr_[a-z_0-9]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(sr_[a-z_0-9]+)\s*\(", abi_text.header())))
 
 
 def test_every_declared_symbol_is_exported_and_bound(lib):
@@ -114,20 +114,62 @@ def test_product_never_imports_the_oracle():
                     assert "import oracle" not in src and "from oracle" not in src and "raster_ref" not in src, f
 
 
-def test_header_constants_match_the_binding():
-    """#define values of include/splatraster.h == the Python binding's constants."""
+SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+           "unsigned": C.c_uint, "unsigned int": C.c_uint, "unsigned char": C.c_ubyte, "unsigned long long": C.c_ulonglong}
+
+
+def bound_as(decl):
+    """the ctypes a declaration of the header (`const SrView* view`, `long long r`, a return type) may be bound as"""
     from splatfields_amd import _lib
-    text = open(os.path.join(ROOT, "include", "splatraster.h")).read()
-    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SR_[A-Z_]+)\s+(\d+)\b", text, re.M)}
-    assert defs["SR_NEED_CAPACITY"] == _lib.SR_NEED_CAPACITY
-    assert defs["SR_VERSION"] == _lib.SR_VERSION
-    assert (defs["SR_RAW_SCALES"], defs["SR_RAW_OPACITY"], defs["SR_RAW_ROTATIONS"], defs["SR_FORWARD_ONLY"]) == \
-        (_lib.SR_RAW_SCALES, _lib.SR_RAW_OPACITY, _lib.SR_RAW_ROTATIONS, _lib.SR_FORWARD_ONLY)
-    assert defs["SR_PROFILE_STAGES"] == _lib.PROFILE_STAGES
-    assert defs["SR_MLP_MAX_PACK_JOBS"] == _lib.MLP_MAX_PACK_JOBS
-    assert (defs["SR_MLP_MAX_GRAD_JOBS"], defs["SR_MLP_MAX_GRAD_TASKS"]) == (_lib.MLP_MAX_GRAD_JOBS, _lib.MLP_MAX_GRAD_TASKS)
-    assert (defs["SR_MLP_MAX_OPS"], defs["SR_MLP_NONE"], defs["SR_MLP_LEAKY"], defs["SR_MLP_MASK"]) == \
-        (_lib.MLP_MAX_OPS, _lib.MLP_NONE, _lib.MLP_LEAKY, _lib.MLP_MASK)
+    words = decl.replace("*", " * ").split()
+    if len(words) > 1 and words[-1] not in ("*", "int", "long", "char", "float", "double", "unsigned", "size_t", "void"):
+        words = words[:-1]                                   # the argument's name
+    stars = words.count("*")
+    base = " ".join(w for w in words if w not in ("*", "const"))
+    if stars == 0:
+        return (SCALARS[base],)
+    if base in abi_text.structs():                           # a table of the header's structs: never an anonymous pointer
+        assert stars == 1, decl
+        return (C.POINTER(getattr(_lib, base)),)
+    if decl.split() == ["const", "char*"]:
+        return (C.c_char_p,)
+    pointee = C.c_void_p if stars > 1 or base in ("void", "char") else SCALARS[base]
+    return (C.c_void_p, C.POINTER(pointee))
+
+
+def test_every_prototype_matches_the_binding():
+    """argument count, return type and every argument's ctype of _lib.SYMBOLS against the header's prototype: a pointer is a
+    c_void_p, or a POINTER of what the header says it points to (of the struct, where it names one)"""
+    from splatfields_amd import _lib
+    protos = abi_text.prototypes()
+    assert sorted(protos) == sorted(_lib.SYMBOLS) == declared_symbols() and len(protos) >= 100
+    for name, (ret, args) in protos.items():
+        restype, argtypes = _lib.SYMBOLS[name]
+        assert restype in bound_as(ret)[:1], (name, ret, restype)
+        assert len(argtypes) == len(args), (name, len(argtypes), args)
+        for arg, ctype in zip(args, argtypes):
+            assert ctype in bound_as(arg), (name, arg, ctype)
+
+
+def test_every_struct_lists_the_fields_of_the_header_in_order():
+    from splatfields_amd import _lib
+    structs = abi_text.structs()
+    assert len(structs) >= 15
+    for name, fields in structs.items():
+        assert [f[1] for f in fields] == [f[0] for f in getattr(_lib, name)._fields_], name
+
+
+def test_every_integer_constant_of_the_header_has_its_binding_constant():
+    """#define SR_X n of include/splatraster.h == _lib.SR_X or _lib.X"""
+    from splatfields_amd import _lib
+    no_twin = {"SR_TILE", "SR_BWD_SLOT_SPEC_BELOW"}           # read by the kernels and the host code only
+    defs = {k: int(v) for k, v in abi_text.defines().items() if k.startswith("SR_") and re.fullmatch(r"\d+", v)}
+    assert len(defs) >= 54 and no_twin <= set(defs)
+    for name, value in defs.items():
+        if name in no_twin:
+            continue
+        twins = [getattr(_lib, n) for n in (name, name[3:]) if hasattr(_lib, n)]
+        assert twins and all(t == value for t in twins), (name, value, twins)
 
 
 def test_mlp_entry_points_refuse_bad_descriptions_without_touching_a_device():

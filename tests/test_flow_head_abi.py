@@ -10,6 +10,8 @@ import sys
 import pytest
 import torch
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_flow_head_saved_bytes", "sr_flow_head_workspace_bytes", "sr_flow_head_dz_row", "sr_flow_head_forward", "sr_flow_head_backward")
 OFFSET, SE3, SE3_AFFINE, SE3_SCALED, AFFINE, DCT = range(6)
@@ -23,30 +25,12 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
     from splatfields_amd import _lib, build
-    header = header_text()
+    header = abi_text.header()
     assert "flow_head.hip" in build.SOURCES
-    for name in NEW:
-        m = re.search(r"^(size_t|int) %s\((.*?)\);" % name, header, re.S | re.M)
-        assert m, f"{name} is not declared in the header"
-        declared = [a.strip() for a in m.group(2).split(",") if a.strip()]
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        restype, argtypes = _lib.SYMBOLS[name]
-        assert len(argtypes) == len(declared), (name, len(argtypes), declared)
-        assert restype is (C.c_size_t if m.group(1) == "size_t" else C.c_int), name
-        for arg, ctype in zip(declared, argtypes):
-            if "SrFlowBranch*" in arg:
-                want = C.POINTER(_lib.SrFlowBranch)
-            elif "*" in arg:
-                want = C.c_void_p
-            else:
-                want = C.c_longlong if arg.startswith("long long") else C.c_int
-            assert ctype is want, (name, arg, ctype)
+    for name in NEW:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4 and re.search(r"#define SR_VERSION 4\b", header)
     defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SR_FLOW_[A-Z0-9_]+)\s+(\d+)\b", header, re.M)}
     assert defs == {"SR_FLOW_OFFSET": _lib.FLOW_OFFSET, "SR_FLOW_SE3": _lib.FLOW_SE3, "SR_FLOW_SE3_AFFINE": _lib.FLOW_SE3_AFFINE,
@@ -57,8 +41,6 @@ def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
     assert 3 * _lib.FLOW_MAX_BASIS <= _lib.FLOW_MAX_OUT and (_lib.FLOW_MAX_WIDTH, _lib.FLOW_MAX_BASIS) == (256, 10)
     # struct SrFlowBranch: two pointers and an int, padded to 24 bytes
     assert C.sizeof(_lib.SrFlowBranch) == 24 and [f[0] for f in _lib.SrFlowBranch._fields_] == ["weight", "bias", "rows"]
-    fields = re.search(r"typedef struct SrFlowBranch \{(.*?)\} SrFlowBranch;", header, re.S).group(1)
-    assert re.findall(r"(\w+);", fields) == ["weight", "bias", "rows"]
     import splatfields_amd
     for name in ("set_flow_head", "flow_head_path", "fused_flow_head"):
         assert callable(getattr(splatfields_amd, name)), name
@@ -134,15 +116,8 @@ def test_bad_calls_are_refused_on_the_host_and_empty_ones_launch_nothing(lib):
 
 def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    code = strip_comments(open(os.path.join(csrc, "flow_head.hip")).read())
-    api = open(os.path.join(csrc, "api.hip")).read()
-    entries = []
-    for name in NEW:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        entries.append(m.group(0))
-    entries = "\n".join(entries)
+    code = strip_comments(abi_text.source("flow_head.hip"))
+    entries = "\n".join(abi_text.entry_point(name) for name in NEW)
     assert "k_flow_head_forward" in code and "k_flow_head_backward" in code and "block_sum" in code and "launch_flow_head_backward" in entries
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMalloc", "atomic", "bf16", "__half"):
         assert word not in code and word not in entries, word

@@ -7,6 +7,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_mlp_chain_group", "sr_mlp_chain_group_bf16", "sr_mlp_group_input_forward", "sr_mlp_group_input_backward", "sr_mlp_group_output",
        "sr_mlp_group_top_gradient")
@@ -19,30 +21,11 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
     from splatfields_amd import _lib
-    header = header_text()
-    structs = {"SrMlpNet*": _lib.SrMlpNet, "SrMlpHeadInput*": _lib.SrMlpHeadInput, "SrMlpHeadOutput*": _lib.SrMlpHeadOutput}
-    for name in NEW:
-        m = re.search(r"^int %s\((.*?)\);" % name, header, re.S | re.M)
-        assert m, f"{name} is not declared in the header"
-        declared = [a.strip() for a in m.group(1).split(",") if a.strip()]
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        restype, argtypes = _lib.SYMBOLS[name]
-        assert restype is C.c_int and len(argtypes) == len(declared), (name, declared)
-        for arg, ctype in zip(declared, argtypes):
-            table = [v for k, v in structs.items() if k in arg]
-            if table:
-                want = C.POINTER(table[0])
-            elif "*" in arg:
-                want = C.c_void_p
-            else:
-                want = C.c_float if arg.startswith("float") else C.c_int
-            assert ctype is want, (name, arg, ctype)
+    header = abi_text.header()
+    for name in NEW:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4 and re.search(r"#define SR_VERSION 4\b", header)
     defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SR_MLP_(?:GROUP|OUT)_[A-Z0-9_]+)\s+(\d+)\b", header, re.M)}
     assert defs == {"SR_MLP_GROUP_MAX_NETS": _lib.MLP_GROUP_MAX_NETS, "SR_MLP_GROUP_MAX_OPS": _lib.MLP_GROUP_MAX_OPS,
@@ -52,13 +35,9 @@ def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
     # the op table of a group is a kernel argument: n_nets, first[], the ops, n_points and the slope stay under 4 KB
     assert C.sizeof(_lib.SrMlpOp) == 96
     assert 4 * (2 + _lib.MLP_GROUP_MAX_NETS) + _lib.MLP_GROUP_MAX_OPS * C.sizeof(_lib.SrMlpOp) + 8 < 4096
-    code = open(os.path.join(ROOT, "splatfields_amd", "csrc", "mlp.hip")).read()
-    assert re.search(r"static_assert\(sizeof\(MlpGroupK\)[^;]*4096", code)
-    for cls, size in ((_lib.SrMlpNet, 16), (_lib.SrMlpHeadInput, 24), (_lib.SrMlpHeadOutput, 48)):
-        assert C.sizeof(cls) == size
-        fields = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cls.__name__, cls.__name__), header, re.S).group(1)
-        fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
-        assert re.findall(r"(\w+);", fields) == [f[0] for f in cls._fields_], cls.__name__
+    assert re.search(r"static_assert\(sizeof\(MlpGroupK\)[^;]*4096", abi_text.source("mlp.hip"))
+    for cls, size in ((_lib.SrMlpNet, 16), (_lib.SrMlpHeadInput, 24), (_lib.SrMlpHeadOutput, 48)):      # the field order: test_c_abi.py
+        assert C.sizeof(cls) == size and cls.__name__ in abi_text.structs()
     import splatfields_amd
     assert callable(splatfields_amd.set_heads) and callable(splatfields_amd.heads)
 
@@ -66,7 +45,7 @@ def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
 def test_additions_only():
     """the structs and limits of the existing chain entry points are what they were"""
     from splatfields_amd import _lib
-    header = header_text()
+    header = abi_text.header()
     assert re.search(r"#define SR_MLP_MAX_OPS 24\b", header) and re.search(r"#define SR_MLP_MAX_PACK_JOBS 32\b", header)
     assert (_lib.MLP_MAX_OPS, _lib.MLP_MAX_PACK_JOBS, _lib.RESFIELD_MAX_JOBS) == (24, 32, 16)
     assert C.sizeof(_lib.SrMlpPackJob) == 80
@@ -216,8 +195,7 @@ def test_group_output_kernels_refuse_bad_calls_and_launch_nothing(lib):
 
 def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    code = strip_comments(open(os.path.join(csrc, "mlp.hip")).read())
+    code = strip_comments(abi_text.source("mlp.hip"))
     start = code.index("struct GroupInK")
     small = code[start:]
     for kernel in ("k_mlp_group_input_forward", "k_mlp_group_input_backward", "k_mlp_group_output", "k_mlp_group_top_gradient"):

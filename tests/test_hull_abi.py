@@ -7,13 +7,11 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("sr_hull_workspace_bytes", "sr_hull_carve", "sr_hull_gather")
 BLOCK, WAVE = 256, 64          # csrc/common.h: kBlock, kWave
-
-
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "splatraster.h")).read(), flags=re.S)
 
 
 @pytest.fixture(scope="module")
@@ -23,45 +21,23 @@ def lib():
     return _lib.load()
 
 
-def ctype_of(decl):
-    """the ctypes type the binding must use for one C parameter declaration of the header"""
-    from splatfields_amd import _lib
-    decl = " ".join(decl.replace("const", " ").split())
-    kind = decl.rsplit(" ", 1)[0] if not decl.endswith("*") else decl       # drop the parameter name
-    kind = kind.replace(" *", "*")
-    if kind == "SrHullView*":
-        return C.POINTER(_lib.SrHullView)
-    if kind.endswith("*"):
-        return C.c_void_p
-    return {"int": C.c_int, "long long": C.c_longlong, "size_t": C.c_size_t}[kind]
-
-
 def test_symbols_are_declared_exported_and_bound_with_the_headers_signatures(lib):
     from splatfields_amd import _lib, build
-    text = header_text()
-    for name in NAMES:
-        m = re.search(r"(\w[\w ]*?)\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, f"{name} is not declared in include/splatraster.h"
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        res, args = _lib.SYMBOLS[name]
-        assert res is ctype_of(m.group(1).strip() + " f"), name
-        want = [ctype_of(p) for p in m.group(2).split(",")]
-        assert len(args) == len(want), (name, len(args), len(want))
-        for k, (a, w) in enumerate(zip(args, want)):
-            assert a is w or (w is C.POINTER(_lib.SrHullView) and a == w), (name, k, a, w)
+    for name in NAMES:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert "hull.hip" in build.SOURCES
 
 
 def test_version_is_still_4_everywhere(lib):
     from splatfields_amd import _lib
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4
-    assert re.search(r"#define\s+SR_VERSION\s+4\b", header_text())
+    assert re.search(r"#define\s+SR_VERSION\s+4\b", abi_text.header())
 
 
 def test_view_record_and_constants_match_the_header():
     from splatfields_amd import _lib
     V = _lib.SrHullView
-    text = header_text()
+    text = abi_text.header()
     body = re.search(r"typedef struct SrHullView \{(.*?)\} SrHullView;", text, flags=re.S).group(1)
     fields = [f.strip() for f in body.split(";") if f.strip()]
     assert fields == ["double m[12]", "long long mask_offset", "int height, width", "int convention", "int outside"]

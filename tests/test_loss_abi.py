@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_loss_workspace_bytes", "sr_loss_maps_bytes", "sr_photometric_forward", "sr_photometric_backward")
 
@@ -69,21 +71,9 @@ def test_bad_calls_are_refused_on_the_host(lib):
     assert fwd(batch=1 << 20, channels=1 << 20) != 0 and b"too large" in err()
 
 
-def entry_point_text():
-    api = open(os.path.join(ROOT, "splatfields_amd", "csrc", "api.hip")).read()
-    out = []
-    for name in NEW:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        out.append(m.group(0))
-    return "\n".join(out)
-
-
 def test_the_loss_never_waits_for_the_device_and_has_no_float_atomics():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    text = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("loss.hip", "reduce.h", "window11.h"))
-    text += "\n" + entry_point_text()
+    text = "\n".join(strip_comments(abi_text.source(f)) for f in ("loss.hip", "reduce.h", "window11.h"))   # loss.hip ends with its entry points
     assert "block_sum" in text and "win_filter_column" in text      # the sums and the window it is built from
     assert "sr_photometric_backward" in text and "k_loss_forward" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy(", "hipMemcpyAsync", "atomicAdd",

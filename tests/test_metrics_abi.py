@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_metrics_workspace_bytes", "sr_image_metrics")
 
@@ -74,21 +76,9 @@ def test_bad_calls_are_refused_on_the_host(lib):
     assert call(mask=p, mask_item=5) != 0 and b"mask_item_stride" in err()
 
 
-def entry_point_text():
-    api = open(os.path.join(ROOT, "splatfields_amd", "csrc", "api.hip")).read()
-    out = []
-    for name in NEW:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        out.append(m.group(0))
-    return "\n".join(out)
-
-
 def test_the_metrics_never_wait_for_the_device_and_have_no_float_atomics():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    text = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("metrics.hip", "reduce.h", "window11.h"))
-    text += "\n" + entry_point_text()
+    text = "\n".join(strip_comments(abi_text.source(f)) for f in ("metrics.hip", "reduce.h", "window11.h"))   # metrics.hip ends with its entry points
     assert "block_sum" in text and "win_filter_column" in text      # the sums and the window it is built from
     assert "sr_image_metrics" in text and "k_metrics" in text and "k_metrics_reduce" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMemset", "hipMalloc",

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_knn_graph_workspace_bytes", "sr_knn_graph", "sr_moran_workspace_bytes", "sr_moran_edges_bytes", "sr_moran_forward",
        "sr_moran_backward", "sr_moran_weights", "sr_moran_weights_backward")
@@ -107,22 +109,11 @@ def test_bad_calls_are_refused_on_the_host(lib):
             assert call(**{name: None}) != 0 and b"null pointer" in err(), (call.__name__, name)
 
 
-def entry_point_text():
-    api = open(os.path.join(ROOT, "splatfields_amd", "csrc", "api.hip")).read()
-    out = []
-    for name in NEW + ("open_moran",):
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        out.append(m.group(0))
-    return "\n".join(out)
-
-
 def test_nothing_waits_for_the_device_and_no_float_is_added_atomically():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    moran = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("moran.hip", "reduce.h"))   # with its sums
-    knn = strip_comments(open(os.path.join(csrc, "knn.hip")).read())
-    entries = entry_point_text()
+    moran = "\n".join(strip_comments(abi_text.source(f)) for f in ("moran.hip", "reduce.h"))   # with its sums
+    knn = strip_comments(abi_text.source("knn.hip"))
+    entries = "\n".join(abi_text.entry_point(name) for name in NEW + ("open_moran",))
     assert "sr_moran_backward" in entries and "k_moran_forward" in moran and "block_sum" in moran and "k_knn_search_k" in knn
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy(", "hipMemcpyAsync"):
         assert word not in moran and word not in knn and word not in entries, word

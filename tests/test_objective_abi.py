@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_splat_reg_workspace_bytes", "sr_splat_reg_forward", "sr_splat_reg_backward", "sr_depth_l1_workspace_bytes",
        "sr_depth_l1_forward", "sr_depth_l1_backward")
@@ -18,25 +20,12 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_declared_exported_and_bound_with_matching_argument_counts(lib):
     from splatfields_amd import _lib, build
-    header = header_text()
+    header = open(os.path.join(ROOT, "include", "splatraster.h")).read()      # with its comments: the "replaces" map below
     assert "objective.hip" in build.SOURCES
-    for name in NEW:
-        m = re.search(r"^(size_t|int) %s\((.*?)\);" % name, header, re.S | re.M)
-        assert m, f"{name} is not declared in the header"
-        declared = [a for a in m.group(2).split(",") if a.strip()]
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        restype, argtypes = _lib.SYMBOLS[name]
-        assert len(argtypes) == len(declared), (name, len(argtypes), declared)
-        assert restype is (C.c_size_t if m.group(1) == "size_t" else C.c_int), name
-        for arg, ctype in zip(declared, argtypes):      # doubles travel as doubles, pointers as pointers
-            want = C.c_void_p if "*" in arg else (C.c_double if arg.split()[0] == "double" else C.c_int)
-            assert ctype is want, (name, arg, ctype)
+    for name in NEW:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4 and re.search(r"#define SR_VERSION 4\b", header)
     for lines in ("train.py:195-197", "train.py:198-201", "train.py:244-246", "train.py:224-229"):    # the "replaces" map
         assert lines in header, lines
@@ -98,15 +87,8 @@ def test_bad_calls_are_refused_on_the_host_and_empty_ones_launch_nothing(lib):
 
 def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    code = "\n".join(strip_comments(open(os.path.join(csrc, f)).read()) for f in ("objective.hip", "reduce.h"))   # with its sums
-    api = open(os.path.join(csrc, "api.hip")).read()
-    entries = []
-    for name in NEW:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        entries.append(m.group(0))
-    entries = "\n".join(entries)
+    code = "\n".join(strip_comments(abi_text.source(f)) for f in ("objective.hip", "reduce.h"))   # with its sums
+    entries = "\n".join(abi_text.entry_point(name) for name in NEW)
     assert "k_splat_reg_backward" in code and "block_sum" in code and "k_depth_l1_backward" in code and "launch_depth_l1_backward" in entries
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMalloc", "atomic"):
         assert word not in code and word not in entries, word

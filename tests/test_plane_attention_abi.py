@@ -8,11 +8,12 @@ import os
 import re
 
 import pytest
+
+import abi_text
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("sr_attention_saved_bytes", "sr_attention_backward_workspace", "sr_attention_forward", "sr_attention_backward")
-CTYPES = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "void*": C.c_void_p, "const SrAttentionJob*": "jobs"}
 
 
 @pytest.fixture(scope="module")
@@ -22,35 +23,18 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_exported_with_the_headers_signatures(lib):
     from splatfields_amd import _lib, build
-    header = header_text()
-    for name in NAMES:
-        m = re.search(r"(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, name
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        res, args = _lib.SYMBOLS[name]
-        assert res is CTYPES[m.group(1)], name
-        declared = []
-        for a in m.group(2).split(","):
-            words = a.replace("*", "* ").split()
-            ty = " ".join(words[:-1]).replace(" *", "*")
-            declared.append(C.POINTER(_lib.SrAttentionJob) if CTYPES[ty] == "jobs" else CTYPES[ty])
-        assert declared == list(args), (name, declared, args)
+    header = abi_text.header()
+    for name in NAMES:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert "attention.hip" in build.SOURCES
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4 and re.search(r"#define SR_VERSION 4\b", header)
 
 
 def test_job_struct_matches_the_header():
     from splatfields_amd import _lib
-    body = re.search(r"typedef struct SrAttentionJob \{(.*?)\} SrAttentionJob;", header_text(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [f.split()[-1].lstrip("*") for f in body.split(";") if f.strip()]
-    assert fields == [n for n, _ in _lib.SrAttentionJob._fields_]
+    fields = [f[1] for f in abi_text.structs()["SrAttentionJob"]]      # in the binding's order: test_c_abi.py
     assert C.sizeof(_lib.SrAttentionJob) == 8 * len(fields)
     wanted = {"x", "gamma", "beta", "stats", "out", "saved", "dy", "dx"}
     assert wanted <= set(fields) and len(fields) == len(wanted) + 8 + 10       # + the eight projection tensors + ten parameter gradients

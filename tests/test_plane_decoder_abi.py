@@ -1,15 +1,14 @@
 """The C ABI of the plane generator's kernels (include/splatraster.h: sr_groupnorm_*, sr_conv3x3_*): exported and bound with
 the header's signatures, the workspace queries work without a GPU, and every bad call is refused on the host before any launch."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_text
+
 NAMES = ("sr_groupnorm_stats_workspace", "sr_groupnorm_stats", "sr_conv3x3_forward", "sr_conv3x3_backward_data",
          "sr_groupnorm_silu_backward_workspace", "sr_groupnorm_silu_backward", "sr_conv3x3_weight_grad_workspace", "sr_conv3x3_weight_grad")
-CTYPES = {"int": C.c_int, "float": C.c_float, "size_t": C.c_size_t, "void*": C.c_void_p, "const SrPlaneJob*": "jobs"}
 
 
 @pytest.fixture(scope="module")
@@ -19,39 +18,22 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_exported_with_the_headers_signatures(lib):
     from splatfields_amd import _lib, build
-    header = header_text()
-    for name in NAMES:
-        m = re.search(r"(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, header)
-        assert m, name
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        res, args = _lib.SYMBOLS[name]
-        assert res is CTYPES[m.group(1)], name
-        declared = []
-        for a in m.group(2).split(","):
-            words = a.replace("*", "* ").split()
-            ty = " ".join(words[:-1]).replace(" *", "*")
-            declared.append(C.POINTER(_lib.SrPlaneJob) if CTYPES[ty] == "jobs" else CTYPES[ty])
-        assert declared == list(args), (name, declared, args)
+    header = abi_text.header()
+    for name in NAMES:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert "planegen.hip" in build.SOURCES
     assert lib.sr_version() == 4 and re.search(r"#define SR_VERSION 4\b", header)
 
 
 def test_job_struct_matches_the_header():
     from splatfields_amd import _lib
-    body = re.search(r"typedef struct SrPlaneJob \{(.*?)\} SrPlaneJob;", header_text(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [f.split()[-1].lstrip("*") for f in body.split(";") if f.strip()]
-    assert fields == [n for n, _ in _lib.SrPlaneJob._fields_]
+    fields = [f[1] for f in abi_text.structs()["SrPlaneJob"]]      # in the binding's order: test_c_abi.py
     assert C.sizeof(_lib.SrPlaneJob) == 8 * len(fields)
-    assert _lib.PLANE_MAX_JOBS == int(re.search(r"#define SR_PLANE_MAX_JOBS (\d+)", header_text()).group(1))
+    assert _lib.PLANE_MAX_JOBS == int(re.search(r"#define SR_PLANE_MAX_JOBS (\d+)", abi_text.header()).group(1))
     for name, value in (("PROLOGUE", _lib.CONV_PROLOGUE), ("UPSAMPLE", _lib.CONV_UPSAMPLE), ("RESIDUAL", _lib.CONV_RESIDUAL), ("SILU_OUT", _lib.CONV_SILU_OUT)):
-        assert value == int(re.search(r"#define SR_CONV_%s (\d+)" % name, header_text()).group(1))
+        assert value == int(re.search(r"#define SR_CONV_%s (\d+)" % name, abi_text.header()).group(1))
 
 
 def test_workspaces_are_monotone_in_planes_and_size(lib):

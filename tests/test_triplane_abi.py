@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("sr_triplane_backward_workspace", "sr_triplane_forward", "sr_triplane_backward")
 COPIES = 32          # counters per tile (csrc/triplane.hip: kTpCopies)
@@ -75,19 +77,9 @@ def test_bad_calls_are_refused_on_the_host(lib):
     assert bwd(c=128, work=None, d_pts=None) != 0 and b"dL_dplanes needs a workspace" in err()
 
 
-def entry_point_text():
-    api = open(os.path.join(ROOT, "splatfields_amd", "csrc", "api.hip")).read()
-    out = []
-    for name in NAMES:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        out.append(m.group(0))
-    return "\n".join(out)
-
-
 def test_the_lookup_never_waits_for_the_device_and_has_no_float_atomics():
     from splatfields_amd.build import strip_comments
-    text = strip_comments(open(os.path.join(ROOT, "splatfields_amd", "csrc", "triplane.hip")).read()) + "\n" + entry_point_text()
+    text = strip_comments(abi_text.source("triplane.hip"))      # the kernels, their launchers and the entry points
     assert "sr_triplane_backward" in text and "k_tp_accumulate" in text
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy(", "hipMemcpyAsync", "atomicAdd_f",
                  "unsafeAtomicAdd", "atomicAdd(float", "atomicExch"):

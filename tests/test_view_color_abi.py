@@ -10,6 +10,8 @@ import sys
 import pytest
 import torch
 
+import abi_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sr_view_color_saved_bytes", "sr_view_color_workspace_bytes", "sr_view_color_forward", "sr_view_color_backward")
 CAMERAS, DIRS = 0, 1
@@ -22,25 +24,12 @@ def lib():
     return _lib.load()
 
 
-def header_text():
-    return open(os.path.join(ROOT, "include", "splatraster.h")).read()
-
-
 def test_symbols_are_declared_exported_and_bound_with_matching_signatures(lib):
     from splatfields_amd import _lib, build
-    header = header_text()
+    header = abi_text.header()
     assert "view_color.hip" in build.SOURCES and "point_tile.h" in build.HEADERS
-    for name in NEW:
-        m = re.search(r"^(size_t|int) %s\((.*?)\);" % name, header, re.S | re.M)
-        assert m, f"{name} is not declared in the header"
-        declared = [a.strip() for a in m.group(2).split(",") if a.strip()]
-        assert name in _lib.SYMBOLS and hasattr(lib, name), name
-        restype, argtypes = _lib.SYMBOLS[name]
-        assert len(argtypes) == len(declared), (name, len(argtypes), declared)
-        assert restype is (C.c_size_t if m.group(1) == "size_t" else C.c_int), name
-        for arg, ctype in zip(declared, argtypes):
-            want = C.c_void_p if "*" in arg else (C.c_longlong if arg.startswith("long long") else C.c_int)
-            assert ctype is want, (name, arg, ctype)
+    for name in NEW:                  # the signatures: test_c_abi.py::test_every_prototype_matches_the_binding
+        assert name in abi_text.prototypes() and name in _lib.SYMBOLS and hasattr(lib, name), name
     assert lib.sr_version() == 4 and _lib.SR_VERSION == 4 and re.search(r"#define SR_VERSION 4\b", header)      # functions are added, none changes
     defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SR_VIEW_[A-Z0-9_]+)\s+(\d+)\b", header, re.M)}
     assert defs == {"SR_VIEW_FROM_CAMERAS": _lib.VIEW_FROM_CAMERAS, "SR_VIEW_DIRS_GIVEN": _lib.VIEW_DIRS_GIVEN,
@@ -107,15 +96,8 @@ def test_bad_calls_are_refused_on_the_host_and_empty_ones_launch_nothing(lib):
 
 def test_nothing_waits_for_the_device_and_nothing_is_added_atomically():
     from splatfields_amd.build import strip_comments
-    csrc = os.path.join(ROOT, "splatfields_amd", "csrc")
-    code = strip_comments(open(os.path.join(csrc, "view_color.hip")).read()) + strip_comments(open(os.path.join(csrc, "point_tile.h")).read())
-    api = open(os.path.join(csrc, "api.hip")).read()
-    entries = []
-    for name in NEW:
-        m = re.search(r"^[a-z_]+ %s\(.*?^}$|^[a-z_]+ %s\([^\n]*\}$" % (name, name), api, re.S | re.M)
-        assert m, name
-        entries.append(m.group(0))
-    entries = "\n".join(entries)
+    code = strip_comments(abi_text.source("view_color.hip")) + strip_comments(abi_text.source("point_tile.h"))
+    entries = "\n".join(abi_text.entry_point(name) for name in NEW)
     assert "k_view_color_forward" in code and "k_view_color_backward" in code and "block_sum" in code and "launch_view_color_backward" in entries
     for word in ("hipDeviceSynchronize", "hipStreamSynchronize", "hipEventSynchronize", "hipMemcpy", "hipMalloc", "atomic", "bf16", "__half"):
         assert word not in code and word not in entries, word
