@@ -545,6 +545,22 @@ int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
 int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
 int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream);
 
+/* The same chains with split-bfloat16 matrix operands, "bf16x3" (opt-in).  Every operand v is split into hi(v) = bf(v) and
+ * lo(v) = bf(v - hi(v)) (the fp32 subtraction is exact) and a product spends three bf16 MFMAs, lo . lo is dropped:
+ *   forward ops   acc = bias + hi(W) . hi(x) + hi(W) . lo(x) + lo(W) . hi(x)
+ *   backward ops  acc = hi(W^T) . hi(dZ) + hi(W^T) . lo(dZ) + lo(W^T) . hi(dZ)
+ * About 16 significant bits per operand instead of 8.  The three MFMAs of one (chunk, output tile, point tile) go into the same
+ * fp32 accumulator in that order; everything outside the MFMA is as for sr_mlp_chain_bf16 (fp32 bias, state, epilogues, sign bits
+ * and stores; the state is split once per op and state tile, channels read from `src` as they are loaded); results are
+ * bit-identical from run to run.  A non-finite operand has lo = NaN, a finite one that bfloat16 rounds to +-inf has lo = -+inf: what
+ * such an operand reaches is not finite.
+ * sr_mlp_pack_bf16x3 takes the job table of sr_mlp_pack: `dst` receives 2 * 16 * out_tiles * (mem_pad + reg_width) bfloat16 values
+ * (4 bytes per weight; 16-byte aligned; per 32-column chunk the hi block, then the lo block, each in the layout of
+ * sr_mlp_pack_bf16: csrc/mlp.hip), `bias_dst` stays fp32.  sr_mlp_chain_bf16x3 takes the op table of sr_mlp_chain with `w_packed`
+ * pointing at what sr_mlp_pack_bf16x3 wrote.  Arguments are validated as by the fp32 entry points. */
+int sr_mlp_pack_bf16x3(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream);
+int sr_mlp_chain_bf16x3(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream);
+
 /* Several networks of the SAME hidden width over the SAME points in one launch (the heads of a SplatFields step: reference
  * utils/time_utils.py:466-503 evaluates five GeneralMLPs on one input): net y of `nets` is an op list in the format of
  * sr_mlp_chain, the grid is (ceil(n_points / 128), n_nets) and workgroup (x, y) does for its 128 points exactly what
@@ -553,7 +569,7 @@ int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* 
  * workgroups of net y + 1 start in the tail of net y's last round of resident workgroups.  Nets may differ in depth, skips and
  * output tiles.  At most SR_MLP_GROUP_MAX_NETS nets and SR_MLP_GROUP_MAX_OPS ops in total (the table is a kernel argument:
  * < 4 KB); every op is validated as by sr_mlp_chain.  n_points == 0 or n_nets == 0: nothing is launched, success.
- * sr_mlp_chain_group_bf16: the same for sr_mlp_chain_bf16. */
+ * sr_mlp_chain_group_bf16: the same for sr_mlp_chain_bf16; sr_mlp_chain_group_bf16x3: for sr_mlp_chain_bf16x3. */
 #define SR_MLP_GROUP_MAX_NETS 8
 #define SR_MLP_GROUP_MAX_OPS 40
 typedef struct SrMlpNet {
@@ -562,6 +578,7 @@ typedef struct SrMlpNet {
 } SrMlpNet;
 int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream);
 int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream);
+int sr_mlp_chain_group_bf16x3(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream);
 
 /* Weight and bias gradients of the layers of a fused MLP: for every job
  *   dw[m * dw_row + dw_col0 + c] = sum over points p of dz[p * dz_row + m] * x[p * x_row + c],   m < job.m, c < job.k

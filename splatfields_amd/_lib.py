@@ -200,8 +200,11 @@ SYMBOLS = {
     "sr_mlp_chain": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpOp), C.c_float, C.c_void_p]),
     "sr_mlp_pack_bf16": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
     "sr_mlp_chain_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpOp), C.c_float, C.c_void_p]),
+    "sr_mlp_pack_bf16x3": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
+    "sr_mlp_chain_bf16x3": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpOp), C.c_float, C.c_void_p]),
     "sr_mlp_chain_group": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpNet), C.c_float, C.c_void_p]),
     "sr_mlp_chain_group_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpNet), C.c_float, C.c_void_p]),
+    "sr_mlp_chain_group_bf16x3": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrMlpNet), C.c_float, C.c_void_p]),
     "sr_mlp_group_input_forward": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadInput), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
     "sr_mlp_group_input_backward": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpHeadInput), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 // Fused MLP kernels of the SplatFields deform network for gfx950: the layer chain (forward, and the
 // activation-gradient chain of the backward), the weight packer, and the weight-gradient kernel.  The chain and the packer exist
-// twice: exact fp32 (the default, described here) and, opt-in, with bf16 matrix operands (k_mlp_chain_bf16 below).
+// three times: exact fp32 (the default, described here) and, opt-in, with bf16 matrix operands (k_mlp_chain_bf16 below) or with
+// operands split into two bf16 values, three MFMAs per product (k_mlp_chain_bf16x3, mlp_bf16x3.h).
 //
 // What it replaces: reference utils/time_utils.py:123-191 (`GeneralMLP`: Linear -> activation for every layer, the
 // input concatenated back in front of the hidden state after the `skips` layers), which PyTorch-ROCm runs as one GEMM +
@@ -505,6 +506,9 @@ __global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16(const MlpPackK jobs) {
         for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
 }
 
+// the split-bf16 ("bf16x3") chains and their packer: k_mlp_chain_bf16x3, k_mlp_chain_group_bf16x3, k_mlp_pack_bf16x3
+#include "mlp_bf16x3.h"
+
 // ---- weight gradients: dW[m][c] = sum over points of dZ[p][m] X[p][c], db[m] = sum over points of dZ[p][m] -------------------------
 // The contraction runs over the POINTS (10^5), the result is tiny (128 x 222): library GEMMs serialise it (0.27 ms for one
 // 128 x 128 x 100k product on MI355X, 12 TFLOP/s; eight of them were 2.7 of the 3.9 ms of a GeneralMLP training step).  Here
@@ -673,7 +677,10 @@ int launch_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, v
     return 0;
 }
 
-int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, bool bf16, hipStream_t st) {
+// chain precision of a launch: which packer / chain kernel runs (validation is the same for all three)
+enum MlpMode { kMlpFp32 = 0, kMlpBf16 = 1, kMlpBf16x3 = 2 };
+
+int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, MlpMode mode, hipStream_t st) {
     if (n_jobs < 0 || n_jobs > SR_MLP_MAX_PACK_JOBS) return 1;
     if (n_jobs == 0) return 0;
     MlpPackK k;
@@ -687,9 +694,14 @@ int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, bool bf16, hipStream_t
         k.job[j] = s;
         most = max(most, 16 * s.out_tiles * (s.mem_pad + s.reg_width));
     }
-    if (bf16) {           // two elements per thread step
+    if (mode == kMlpBf16) {           // two elements per thread step
         const int bx = min(64, (most / 2 + kBlock * 4 - 1) / (kBlock * 4));
         hipLaunchKernelGGL(k_mlp_pack_bf16, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
+        return 0;
+    }
+    if (mode == kMlpBf16x3) {         // two elements per thread step, two parts
+        const int bx = min(64, (most + kBlock * 4 - 1) / (kBlock * 4));
+        hipLaunchKernelGGL(k_mlp_pack_bf16x3, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
         return 0;
     }
     const int bx = min(64, (most + kBlock * 4 - 1) / (kBlock * 4));
@@ -710,7 +722,7 @@ static bool mlp_op_ok(const SrMlpOp& s, int hidden_tiles) {
     return true;
 }
 
-int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, bool bf16, hipStream_t st) {
+int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float slope, MlpMode mode, hipStream_t st) {
     if (n_ops < 1 || n_ops > kMlpMaxOps) return 1;
     MlpK net;
     net.n_ops = n_ops;
@@ -720,9 +732,15 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
     }
     if (n_points <= 0) return 0;
     const int blocks = (n_points + 127) / 128;
-    if (bf16) {
+    if (mode == kMlpBf16) {
         if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_bf16<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
         else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain_bf16<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
+        else return 1;
+        return 0;
+    }
+    if (mode == kMlpBf16x3) {
+        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_bf16x3<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
+        else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain_bf16x3<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
         else return 1;
         return 0;
     }
@@ -733,7 +751,7 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
 }
 
 // -> nullptr, or why the group is refused (nothing is launched then)
-const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float slope, bool bf16, hipStream_t st) {
+const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float slope, MlpMode mode, hipStream_t st) {
     if (n_points < 0) return "n_points must not be negative";
     if (hidden_tiles != 4 && hidden_tiles != 8) return "hidden_tiles must be 4 or 8, the same for all nets of a group";
     if (n_nets < 0 || n_nets > SR_MLP_GROUP_MAX_NETS) return "between 0 and SR_MLP_GROUP_MAX_NETS nets per group";
@@ -754,9 +772,14 @@ const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, c
     for (int y = n_nets; y <= SR_MLP_GROUP_MAX_NETS; ++y) grp.first[y] = total;
     if (n_points == 0 || n_nets == 0) return nullptr;
     const dim3 grid((n_points + 127) / 128, n_nets);
-    if (bf16) {
+    if (mode == kMlpBf16) {
         if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group_bf16<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
         else hipLaunchKernelGGL((k_mlp_chain_group_bf16<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+        return nullptr;
+    }
+    if (mode == kMlpBf16x3) {
+        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group_bf16x3<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+        else hipLaunchKernelGGL((k_mlp_chain_group_bf16x3<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
         return nullptr;
     }
     if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
@@ -1296,29 +1319,33 @@ using sr::fail; using sr::check_hip;
 
 extern "C" {
 
-static int mlp_chain_entry(const char* name, bool bf16, int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+static int mlp_chain_entry(const char* name, sr::MlpMode mode, int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
     if (n_points < 0 || !ops) return fail(std::string("bad arguments to ") + name);
     if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail(std::string(name) + ": negative_slope must be in [0, 1)");
-    if (sr::launch_mlp_chain(n_points, hidden_tiles, n_ops, ops, negative_slope, bf16, static_cast<hipStream_t>(hip_stream)))
+    if (sr::launch_mlp_chain(n_points, hidden_tiles, n_ops, ops, negative_slope, mode, static_cast<hipStream_t>(hip_stream)))
         return fail(std::string(name) + ": unsupported op list (hidden_tiles 4 or 8, <= SR_MLP_MAX_OPS ops, even input tile counts, "
                     "16-byte aligned rows wide enough for the tiles read)");
-    return check_hip(hipGetLastError(), bf16 ? "mlp_chain_bf16" : "mlp_chain");
+    return check_hip(hipGetLastError(), name + 3);      // the kernel's label: the entry's name without "sr_"
 }
 
-static int mlp_pack_entry(const char* name, bool bf16, int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+static int mlp_pack_entry(const char* name, sr::MlpMode mode, int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
     if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return fail(std::string("bad arguments to ") + name);
-    if (sr::launch_mlp_pack(n_jobs, jobs, bf16, static_cast<hipStream_t>(hip_stream)))
+    if (sr::launch_mlp_pack(n_jobs, jobs, mode, static_cast<hipStream_t>(hip_stream)))
         return fail(std::string(name) + ": unsupported job (<= SR_MLP_MAX_PACK_JOBS jobs; mem_pad multiple of 32, reg_width of 16, even tile "
                     "count; counts within their padded sizes; 16-byte aligned destination)");
-    return check_hip(hipGetLastError(), bf16 ? "mlp_pack_bf16" : "mlp_pack");
+    return check_hip(hipGetLastError(), name + 3);      // the kernel's label: the entry's name without "sr_"
 }
 
 int sr_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
-    return mlp_chain_entry("sr_mlp_chain", false, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+    return mlp_chain_entry("sr_mlp_chain", sr::kMlpFp32, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
 }
 
 int sr_mlp_chain_bf16(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
-    return mlp_chain_entry("sr_mlp_chain_bf16", true, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+    return mlp_chain_entry("sr_mlp_chain_bf16", sr::kMlpBf16, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
+}
+
+int sr_mlp_chain_bf16x3(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* ops, float negative_slope, void* hip_stream) {
+    return mlp_chain_entry("sr_mlp_chain_bf16x3", sr::kMlpBf16x3, n_points, hidden_tiles, n_ops, ops, negative_slope, hip_stream);
 }
 
 // `empty`: the call was valid and launched nothing (no device is needed for that)
@@ -1330,14 +1357,20 @@ static int mlp_group_entry(const char* name, const char* why, const char* kernel
 
 int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
     if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group: negative_slope must be in [0, 1)");
-    return mlp_group_entry("sr_mlp_chain_group", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, false,
+    return mlp_group_entry("sr_mlp_chain_group", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpFp32,
                                                                             static_cast<hipStream_t>(hip_stream)), "mlp_chain_group", n_points == 0 || n_nets == 0);
 }
 
 int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
     if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16: negative_slope must be in [0, 1)");
-    return mlp_group_entry("sr_mlp_chain_group_bf16", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, true,
+    return mlp_group_entry("sr_mlp_chain_group_bf16", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpBf16,
                                                                                  static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16", n_points == 0 || n_nets == 0);
+}
+
+int sr_mlp_chain_group_bf16x3(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16x3: negative_slope must be in [0, 1)");
+    return mlp_group_entry("sr_mlp_chain_group_bf16x3", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpBf16x3,
+                                                                                   static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16x3", n_points == 0 || n_nets == 0);
 }
 
 int sr_mlp_group_input_forward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, int time_multires, const float* xyz,
@@ -1364,11 +1397,15 @@ int sr_mlp_group_top_gradient(int n_points, int n_heads, const SrMlpHeadOutput* 
 }
 
 int sr_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
-    return mlp_pack_entry("sr_mlp_pack", false, n_jobs, jobs, hip_stream);
+    return mlp_pack_entry("sr_mlp_pack", sr::kMlpFp32, n_jobs, jobs, hip_stream);
 }
 
 int sr_mlp_pack_bf16(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
-    return mlp_pack_entry("sr_mlp_pack_bf16", true, n_jobs, jobs, hip_stream);
+    return mlp_pack_entry("sr_mlp_pack_bf16", sr::kMlpBf16, n_jobs, jobs, hip_stream);
+}
+
+int sr_mlp_pack_bf16x3(int n_jobs, const SrMlpPackJob* jobs, void* hip_stream) {
+    return mlp_pack_entry("sr_mlp_pack_bf16x3", sr::kMlpBf16x3, n_jobs, jobs, hip_stream);
 }
 
 size_t sr_mlp_weight_grad_workspace(int n_points, int n_jobs, const SrMlpGradJob* jobs) {

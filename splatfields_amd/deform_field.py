@@ -226,7 +226,7 @@ class ViewColor:
 
 class SplatFields(nn.Module):
     def __init__(self, radius=None, n_frames: int = 0, encoder: Optional[nn.Module] = None, mlp_precision: Optional[str] = None, **kwargs):
-        """`mlp_precision`: "fp32", "bf16" or None (the process default, splatfields_amd.set_mlp_precision) for the fused layer
+        """`mlp_precision`: "fp32", "bf16", "bf16x3" or None (the process default, splatfields_amd.set_mlp_precision) for the fused layer
         chains of every GeneralMLP built here.  `flow_head="torch" | "fused"` (a keyword, so it also arrives through
         `SplatFieldsModel`'s hyper_args): the path of the flow head, None = the process default (splatfields_amd.set_flow_head).
         `view_color="torch" | "fused"`, likewise: the path of the view-dependent colour head of `use_view_dep_rgb`

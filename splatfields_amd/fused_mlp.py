@@ -14,7 +14,10 @@ module-style wrapper.  No CPU path.
 `precision="bf16"` (opt-in; `set_mlp_precision` / SPLATFIELDS_MLP_PRECISION set the process default, "fp32") runs the two layer
 chains on the bf16 MFMA: weights and the chains' inputs are rounded to bfloat16 where they enter a matrix product, products and
 sums, biases, the running state, the epilogues and everything stored stay fp32, and the weight gradients come from the fp32
-kernel on those stored values (include/splatraster.h: sr_mlp_chain_bf16).
+kernel on those stored values (include/splatraster.h: sr_mlp_chain_bf16).  `precision="bf16x3"` (opt-in the
+same way) splits every such operand into two bfloat16 values, hi = bf(v) and lo = bf(v - hi), and spends three bf16 MFMAs per
+product (hi hi + hi lo + lo hi): about 16 significant bits instead of 8, everything else as for "bf16" (sr_mlp_chain_bf16x3; DESIGN.md
+section 21).
 
 `fused_grouped_heads` (opt-in; `set_heads` / SPLATFIELDS_HEADS set the process default, "separate") evaluates several such networks
 that read the same points, features and time through one autograd function: the networks of one hidden width and precision in one
@@ -35,11 +38,12 @@ from . import _lib
 
 
 PRECISIONS = ("fp32", "bf16")
+SPLIT_PRECISIONS = ("bf16x3",)      # bf16 MFMAs on operands split into two bfloat16 values: accepted wherever a precision name is
 
 
 def _checked_precision(name) -> str:
-    if name not in PRECISIONS:
-        raise ValueError(f"unknown MLP precision {name!r}: expected one of {PRECISIONS}")
+    if name not in PRECISIONS and name not in SPLIT_PRECISIONS:
+        raise ValueError(f"unknown MLP precision {name!r}: expected one of {PRECISIONS + SPLIT_PRECISIONS}")
     return name
 
 
@@ -49,8 +53,8 @@ _MLP_PRECISION = _checked_precision(os.environ.get("SPLATFIELDS_MLP_PRECISION") 
 
 
 def set_mlp_precision(name: str) -> str:
-    """Process default of the fused MLP chains: "fp32" (exact fp32 MFMA) or "bf16" (bf16 operands, fp32 accumulation).
-    Returns the previous setting."""
+    """Process default of the fused MLP chains: "fp32" (exact fp32 MFMA), "bf16" (bf16 operands, fp32 accumulation) or "bf16x3"
+    (operands split into two bf16 values, three bf16 MFMAs per product).  Returns the previous setting."""
     global _MLP_PRECISION
     prev, _MLP_PRECISION = _MLP_PRECISION, _checked_precision(name)
     return prev
@@ -95,6 +99,24 @@ def pack_layer_weight_bf16(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width:
         Wp[:M, mem_pad:mem_pad + n_reg] = W[:, n_mem:]
     v = Wp.to(torch.bfloat16).view(out_tiles, 16, (mem_pad + reg_width) // 32, 2, 4, 4)     # (mt, m, c, j >> 2, k, j & 3)
     return v.permute(2, 0, 4, 1, 3, 5).contiguous().reshape(-1)                          # (c, mt, k, m, j >> 2, j & 3)
+
+
+def pack_layer_weight_bf16x3(W: torch.Tensor, n_mem: int, mem_pad: int, reg_width: int, out_tiles: int) -> torch.Tensor:
+    """PyTorch statement of the bf16x3 packing (the device packer sr_mlp_pack_bf16x3 is tested against it): the same padded matrix
+    W' as `pack_layer_weight`, split into hi = bf(W') and lo = bf(W' - hi), per 32-column chunk the hi block and then the lo block,
+    each in the K order of `pack_layer_weight_bf16` (csrc/mlp_bf16x3.h):
+    bf16 ((((2 c + part) MT + mt) 64 + 16 k + m) 8 + j) = part(W'[16 mt + m][32 c + 16 (j >> 2) + 4 k + (j & 3)]), part 0 = hi, 1 = lo."""
+    M, K = W.shape
+    n_reg = K - n_mem
+    Wp = W.new_zeros(16 * out_tiles, mem_pad + reg_width, dtype=torch.float32)
+    if n_mem:
+        Wp[:M, :n_mem] = W[:, :n_mem]
+    if n_reg:
+        Wp[:M, mem_pad:mem_pad + n_reg] = W[:, n_mem:]
+    hi = Wp.to(torch.bfloat16)
+    lo = (Wp - hi.to(torch.float32)).to(torch.bfloat16)
+    v = torch.stack([hi, lo]).view(2, out_tiles, 16, (mem_pad + reg_width) // 32, 2, 4, 4)     # (part, mt, m, c, j >> 2, k, j & 3)
+    return v.permute(3, 0, 1, 5, 2, 4, 6).contiguous().reshape(-1)                          # (c, part, mt, k, m, j >> 2, j & 3)
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -148,7 +170,9 @@ class _Plan:
     Python cost ~0.6 ms of host time per network; patching ~60 pointers costs a few tens of microseconds)."""
 
     def __init__(self, precision: str = "fp32"):
-        self.bf16 = _checked_precision(precision) == "bf16"      # packed matrices are bfloat16 (biases stay fp32)
+        self.mode = _checked_precision(precision)                # which packer / chain kernel runs
+        self.bf16 = self.mode == "bf16"                          # packed matrices are plain bfloat16 (biases stay fp32)
+        self.wsize = 2 if self.bf16 else 4                       # bytes per packed weight; "bf16x3": two bfloat16, hi and lo
         self.jobs: List[dict] = []
         self.ops: List[dict] = []
         self.sizes: List[Tuple[int, int]] = []
@@ -165,7 +189,7 @@ class _Plan:
         """writes this plan's static fields into jobs[start:] / ops[start:] (its own arrays, or a group's: _GroupPlan) with its
         packed matrices from byte `at` of the buffer on; -> (binds (struct, field, symbol, index, byte offset), next free byte)"""
         binds = []            # `at`: bytes, every piece a multiple of 16
-        wsize = 2 if self.bf16 else 4
+        wsize = self.wsize
         for j, (job, op, (wf, bf)) in enumerate(zip(self.jobs, self.ops, self.sizes)):
             J, O = jobs[start + j], ops[start + j]
             J.ld, J.transposed, J.row0, J.n_rows = job["ld"], job["transposed"], job["row0"], job["n_rows"]
@@ -206,10 +230,16 @@ class _Plan:
             ptrs = dict(ptrs, buf=(buf.data_ptr(),))
             for obj, field, sym, idx, off in binds:
                 setattr(obj, field, ptrs[sym][idx] + off)
-            pack, chain = (lib.sr_mlp_pack_bf16, lib.sr_mlp_chain_bf16) if self.bf16 else (lib.sr_mlp_pack, lib.sr_mlp_chain)
+            pack, chain = _entries(lib, self.mode, group=False)
             _lib.check(pack(len(jobs), jobs, stream))
             _lib.check(chain(n_points, ht, len(ops), ops, slope, stream))
         return buf      # alive until the caller drops it; the stream orders its reuse
+
+
+def _entries(lib, mode: str, group: bool):
+    """(pack entry, chain entry) of a chain precision; a name without kernels is an error, never another precision's kernels"""
+    suffix = {"fp32": "", "bf16": "_bf16", "bf16x3": "_bf16x3"}[mode]
+    return getattr(lib, "sr_mlp_pack" + suffix), getattr(lib, ("sr_mlp_chain_group" if group else "sr_mlp_chain") + suffix)
 
 
 def _forward_plan(shape: _Shape, save: bool, precision: str = "fp32") -> _Plan:
@@ -463,7 +493,7 @@ def fused_general_mlp_points(xyz: torch.Tensor, feat: Optional[torch.Tensor], mu
                              precision: Optional[str] = None) -> torch.Tensor:
     """`fused_general_mlp(cat([positional_encoding(xyz, multires), feat, positional_encoding(time, time_multires)]), ...)` with the
     input matrix built on the device in one kernel: xyz [N, 3], feat [N, F] or None, time [N] / [N, 1] or None (one time per point,
-    no gradient), float32 on a HIP device.  `precision`: "fp32", "bf16" or None (the process default, set_mlp_precision)."""
+    no gradient), float32 on a HIP device.  `precision`: "fp32", "bf16", "bf16x3" or None (the process default, set_mlp_precision)."""
     _lib.load()
     precision = resolve_precision(precision)
     if not xyz.is_cuda:
@@ -492,7 +522,8 @@ def fused_general_mlp(h_in: torch.Tensor, weights: Sequence[torch.Tensor], biase
     """h_in [N, d_in] (positional encoding ++ features, as the reference builds it) -> [N, out_features]; differentiable with
     respect to h_in, the weights and the biases.  weights[j]: [out_j, in_j] on the device, biases[j]: [out_j]; in_0 = d_in,
     in_j = hidden (+ d_in when j - 1 is in `skips`); hidden width 64 or 128.  `precision`: "fp32" (exact fp32 MFMA), "bf16" (bf16
-    matrix operands, fp32 accumulation and fp32 everything else) or None: the process default (set_mlp_precision)."""
+    matrix operands, fp32 accumulation and fp32 everything else), "bf16x3" (the same with every operand split into two bf16 values,
+    three MFMAs per product) or None: the process default (set_mlp_precision)."""
     _lib.load()
     precision = resolve_precision(precision)
     if not h_in.is_cuda:
@@ -680,8 +711,8 @@ class _GroupPlan:
 
     def __init__(self, plans: Sequence[_Plan]):
         self.plans = list(plans)
-        self.bf16 = self.plans[0].bf16
-        if any(p.bf16 != self.bf16 for p in self.plans):
+        self.mode, self.bf16 = self.plans[0].mode, self.plans[0].bf16
+        if any(p.mode != self.mode for p in self.plans):
             raise ValueError("the nets of a group share one chain precision")
         self._arrays = None
         self._lock = threading.Lock()
@@ -715,7 +746,7 @@ class _GroupPlan:
             base = buf.data_ptr()
             for obj, field, y, sym, idx, off in binds:
                 setattr(obj, field, (base if y is None else ptrs_per_net[y][sym][idx]) + off)
-            pack, chain = (lib.sr_mlp_pack_bf16, lib.sr_mlp_chain_group_bf16) if self.bf16 else (lib.sr_mlp_pack, lib.sr_mlp_chain_group)
+            pack, chain = _entries(lib, self.mode, group=True)
             step = _lib.MLP_MAX_PACK_JOBS
             for lo in range(0, len(jobs), step):          # all nets' matrices: 32 jobs per pack launch
                 part = C.cast(C.byref(jobs, lo * C.sizeof(_lib.SrMlpPackJob)), C.POINTER(_lib.SrMlpPackJob))

@@ -196,7 +196,7 @@ class GeneralMLP(nn.Module):
                  skips: Sequence[int] = (4,), multires: int = 6, out_activation: str = "none", act: str = "relu",
                  composition_rank: int = 0, n_frames: int = 100, precision: Optional[str] = None):
         super().__init__()
-        # precision of the fused layer chains: "fp32", "bf16" or None = the process default at call time (set_mlp_precision);
+        # precision of the fused layer chains: "fp32", "bf16", "bf16x3" or None = the process default at call time (set_mlp_precision);
         # a plain attribute that may be set later, not part of the state dict
         self.precision = None if precision is None else _checked_precision(precision)
         if act not in _SLOPES:
