@@ -200,6 +200,15 @@ int sr_ticket_wait(void* ticket, long long* instances_out, long long* longest_li
 /* the longest tile list of the calling thread's most recent sr_forward (-1 before the first): the hint of a later
  * sr_forward_async of the same view */
 long long sr_last_longest_list(void);
+/* How many tiles of the view can hold a list of more than 2048 entries (an upper bound from the coarse length classes of the
+ * launch order; 0 when the longest list has at most 2048): the figure of the calling thread's most recent sr_forward or
+ * sr_ticket_wait (-1 before the first).  Next to the longest list it is what a caller learns about a camera. */
+long long sr_last_long_tiles(void);
+/* What the caller expects that figure to be for the NEXT sr_forward_async of the calling thread (consumed by that call; < 0 or
+ * never called: no expectation).  With at most 8 expected, and a longest_list_expected of at most 4096, the separate sort
+ * launch for lists of 2049..4096 entries is left out and the forward blend sorts whatever such lists the view turns out to
+ * have: a wrong expectation costs time, never a result.  Returns 0. */
+int sr_expect_long_tiles(long long tiles);
 int sr_ticket_release(void* ticket);
 
 /* Backward of both stages.  dL_ddepth / dL_dalpha may be NULL (treated as zero).  `instances` is the capacity the binning
@@ -243,6 +252,16 @@ int sr_backward_splats(const SrView* view, const SrSplats* splats, const void* g
  * variable SPLATRASTER_BWD ("wave" = 1, "quads" = 2), read once when the library is loaded.  Process-wide; returns the
  * previous setting, or -1 for an unknown value (nothing changes). */
 int sr_set_backward_kernel(int which);
+
+/* Who sorts the tile lists of up to 4096 entries, for A/B measurements and for the tests that compare the paths: 0 = the product
+ * choice (default): the workgroup of the forward blend that blends the list sorts it first, inside the same launch -- lists of
+ * up to 2048 entries always, lists of 2049..4096 entries on views that have at most 8 tiles that long and nothing longer (other
+ * views keep the separate launch of that class); 1 = standalone kernels in launches of their own in front of the forward blend;
+ * 2 = the forward blend sorts the lists of up to 2048 entries only.  Lists, images and gradients are bit-identical.
+ * The initial value comes from the environment variable SPLATRASTER_SORT ("standalone" = 1, "short" = 2), read once when the
+ * library is loaded.  Process-wide; applies to forwards launched afterwards; returns the previous setting, or -1 for an unknown value
+ * (nothing changes). */
+int sr_set_sort_kernel(int which);
 
 /* present[i] = 1 iff splat i passes the near-plane test (view z > 0.2). */
 int sr_mark_visible(int n_splats, const float* means3D, const float* viewmatrix,
@@ -1010,6 +1029,12 @@ int sr_debug_backward_stats(unsigned long long* out16, int reset);
  *            tickets that were redeemed while stage 1 of their forward was still running (the host waited in sr_ticket_wait),
  *            tickets ever created (the pool's size) }. */
 int sr_debug_counters(long long* out4, int reset);
+
+/* Launch counters of the separate per-tile sort kernels in front of the forward blend (process-wide, since load or the last
+ * reset; one count per forward that launched the class):
+ *   out4 = { the kernel for lists of up to 2048 entries (never under the product setting, where the forward blend sorts those
+ *            lists itself: sr_set_sort_kernel),  the class of 2049..4096 entries,  4097..8192,  longer lists }. */
+int sr_debug_sort_counters(long long* out4, int reset);
 
 /* debug = true (SrView.debug): every stage is followed by a stream synchronisation + error check, and a FAILED stage writes
  * the call's arguments to snapshot_fw.dump / snapshot_bw.dump in the working directory before the error is returned -- what

@@ -138,7 +138,10 @@ SYMBOLS = {
     "sr_ticket_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sr_ticket_release": (C.c_int, [C.c_void_p]),
     "sr_last_longest_list": (C.c_longlong, []),
+    "sr_last_long_tiles": (C.c_longlong, []),
+    "sr_expect_long_tiles": (C.c_int, [C.c_longlong]),
     "sr_debug_counters": (C.c_int, [C.POINTER(C.c_longlong), C.c_int]),
+    "sr_debug_sort_counters": (C.c_int, [C.POINTER(C.c_longlong), C.c_int]),
     "sr_backward": (C.c_int, [C.POINTER(SrView), C.POINTER(SrSplats), C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SrGrads),
                               C.c_void_p]),
@@ -148,6 +151,7 @@ SYMBOLS = {
                                      C.c_void_p, C.POINTER(SrGrads), C.c_int, C.c_int, C.c_void_p]),
     "sr_debug_snapshot": (C.c_int, [C.POINTER(SrView), C.POINTER(SrSplats), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "sr_set_backward_kernel": (C.c_int, [C.c_int]),
+    "sr_set_sort_kernel": (C.c_int, [C.c_int]),
     "sr_sh_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_sh_forward_views": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_sh_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,

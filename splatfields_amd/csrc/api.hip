@@ -65,7 +65,8 @@ namespace {
 
 // ---- status blocks: how the instance count of a forward reaches the host ------------------------------------------------
 // A pinned, COHERENT 64-byte block of host memory: k_scan_small stores the instance count and the longest list into words 0 / 1
-// and then -- system-scope release stores -- the block's current sequence number into words 2 / 3.  The host polls those two
+// (and the number of tiles that can hold a list of more than 2048 entries into word 4)
+// and then -- system-scope release stores -- the block's current sequence number into words 2 / 3 (and 5).  The host polls those two
 // words: nothing is enqueued in the stream for the read-back (rounds 1-3: a copy command; round 4: an event record, which still
 // cost the stream ~8 us between k_scan_small and the scatter -- rocprofv3 kernel trace, profiles/r05_v1_*).
 // sr_forward keeps one block per (host thread, device); sr_forward_async hands one out per forward in flight (a "ticket",
@@ -77,6 +78,9 @@ std::vector<StatusBlock*> g_ticket_free[64];
 // diagnostics (sr_debug_counters): [0] host waits inside sr_forward, [1] sr_forward_async calls, [2] ticket redemptions that
 // found stage 1 still running (the host had to wait), [3] tickets ever created
 std::atomic<long long> g_counters[4];
+// diagnostics (sr_debug_sort_counters): launches of the separate per-tile sort classes in front of the forward blend:
+// [0] k_sort_tiles_regs (lists up to 2048 entries: the standalone switch only), [1] 2049..4096, [2] 4097..8192, [3] longer
+std::atomic<long long> g_sort_counters[4];
 
 int status_block_init(StatusBlock& b, int dev) {
     // coherent (fine-grained) host memory: the kernel's stores become visible to the host while the stream keeps running
@@ -99,7 +103,7 @@ uint32_t status_block_arm(StatusBlock& b, hipStream_t st) {
 // while the stream runs); after two seconds without it falls back to draining the stream, which also surfaces a failed launch.
 int status_block_wait(StatusBlock& b, bool* waited) {
     volatile uint32_t* p = b.pinned;
-    auto ready = [&] { return p[2] == b.seq && p[3] == b.seq; };
+    auto ready = [&] { return p[2] == b.seq && p[3] == b.seq && p[5] == b.seq; };
     if (waited) *waited = false;
     if (!ready()) {
         if (waited) *waited = true;
@@ -153,6 +157,15 @@ std::atomic<int> g_bwd_kernel{[] {
     return !sel ? 0 : (std::string(sel) == "wave" ? 1 : (std::string(sel) == "quads" ? 2 : 0));
 }()};
 
+// Who sorts the tile lists of up to 4096 entries.  0 = the product choice: the workgroup of k_render_forward that blends the
+// list (lists of 2049..4096 entries only on views with few of them); 1 = sort kernels in launches of their own in front of the
+// forward; 2 = the forward sorts the lists of up to 2048 entries only (sr_set_sort_kernel)
+std::atomic<int> g_sort_kernel{[] {
+    const char* sel = getenv("SPLATRASTER_SORT");
+    return !sel ? 0 : (std::string(sel) == "standalone" ? 1 : (std::string(sel) == "short" ? 2 : 0));
+}()};
+thread_local long long g_last_long_tiles = -1;     // sr_last_long_tiles
+thread_local long long g_expect_long_tiles = -1;   // sr_expect_long_tiles: consumed by the thread's next sr_forward_async
 
 // ---- debug = true: input snapshot on a failed launch ------------------------------------------------------------------
 // [EXT] with `debug` set synchronises after every kernel and, when one fails, dumps the call's arguments to
@@ -328,20 +341,32 @@ int launch_stage1(const SrView* view, const sr::ViewK& v, const sr::SplatsK& s, 
 // hs != nullptr: k_scan_small stores the instance count / longest list into hs->pinned (status block above); the host waits for
 // them after launching the scatter (the GPU keeps working) and then launches only the sort classes that are needed.
 // hs == nullptr: nobody waits; `max_len` = the longest list the sort classes must cover (< 0: launch every class).
-int launch_stage2(const SrView* view, const sr::ViewK& v, const sr::SplatsK& s, const sr::Geom& g, const sr::Binning& b,
+// Sort: the forward blend sorts every list of up to 2048 entries itself (stage 4), and the lists of 2049..4096 entries of a view
+// that has few of them; the other classes that max_len asks for are launched in front of it (stage 3, empty on most views).
+// long_tiles (< 0: unknown): how many tiles can hold a list of more than 2048 entries, known or expected -- with few of them the
+// launch of that class is left out (launch_sort_tiles).  The standalone switch restores a launch per class.  Either way
+// Binning::sorted_up_to means what it always did: lists longer than the classes that ran have no result.
+int launch_stage2(const SrView* view, const sr::ViewK& v, const sr::SplatsK& s, const sr::Geom& g, const sr::Binning& b_in,
                   const sr::Image& im, float* out_color, float* out_depth, float* out_alpha, StatusBlock* hs, long long max_len,
-                  long long expected_len, hipStream_t st) {
+                  long long expected_len, long long long_tiles, hipStream_t st) {
+    sr::Binning b = b_in;
+    const int who = g_sort_kernel.load(std::memory_order_relaxed);   // one read: the launches below must agree
+    b.sort_in_blend = who == 1 ? 0u : (who == 2 ? 2048u : 4096u);
     { StageTimer t_(2, st); sr::launch_emit(v, s.N, g, b, st); }
     SR_TRY(after_launch(view, st, "emit"));
     if (hs) {
         g_counters[0].fetch_add(1, std::memory_order_relaxed);
         SR_TRY(status_block_wait(*hs, nullptr));
         max_len = (long long)hs->pinned[1];
+        long_tiles = (long long)hs->pinned[4];   // tiles that can hold a list of more than 2048 entries
         // the binning buffer is too small: the scatter just launched exits on its own, and nothing else of stage 2 is worth
         // launching -- the caller re-runs it with a buffer that fits (SR_NEED_CAPACITY)
         if ((long long)hs->pinned[0] > (long long)b.capacity) return 0;
     }
-    { StageTimer t_(3, st); sr::launch_sort_tiles(v, g, b, max_len, expected_len, st); }
+    int classes = 0;
+    { StageTimer t_(3, st); classes = sr::launch_sort_tiles(v, g, b, max_len, expected_len, long_tiles, st); }
+    b.long_class_launched = (classes & 2) ? 1u : 0u;
+    for (int k = 0; k < 4; ++k) if (classes & (1 << k)) g_sort_counters[k].fetch_add(1, std::memory_order_relaxed);
     SR_TRY(after_launch(view, st, "sort_tiles"));
     { StageTimer t_(4, st); sr::launch_render_forward(v, g, b, im, out_color, out_depth, out_alpha, st); }
     SR_TRY(after_launch(view, st, "render_forward"));
@@ -377,10 +402,11 @@ int sr_forward(const SrView* view, const SrSplats* splats, void* geom, int* radi
     StatusBlock* hs = nullptr;
     SR_TRY(thread_block(&hs));
     SR_TRY(launch_stage1(view, c.v, c.s, c.g, radii, hs->pinned_dev, status_block_arm(*hs, c.st), c.st));   // k_scan_small stores the counters into hs->pinned
-    SR_TRY(launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, hs, -1, -1, c.st));  // waits inside, GPU busy
+    SR_TRY(launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, hs, -1, -1, -1, c.st));  // waits inside, GPU busy
     const long long total = (long long)hs->pinned[0];
     *instances_out = total;
     g_last_longest = (long long)hs->pinned[1];
+    g_last_long_tiles = (long long)hs->pinned[4];
     return total > binning_capacity ? SR_NEED_CAPACITY : 0;
 }
 
@@ -392,7 +418,7 @@ int sr_forward_render(const SrView* view, const SrSplats* splats, void* geom, vo
     if (!geom || !binning || !image || !out_color || !out_depth) return fail("null buffer");
     if (!capacity_in_range(instances)) return fail("instance count out of range");
     c.carve(geom, binning, instances, image);
-    return launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, nullptr, -1, -1, c.st);
+    return launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, nullptr, -1, -1, -1, c.st);
 }
 
 int sr_forward_async(const SrView* view, const SrSplats* splats, void* geom, int* radii, void* binning,
@@ -406,11 +432,14 @@ int sr_forward_async(const SrView* view, const SrSplats* splats, void* geom, int
     c.carve(geom, binning, binning_capacity, image);
     const long long covered = covered_by_hint(longest_list_hint);
     c.b.sorted_up_to = covered < 0 ? 0xffffffffu : (uint32_t)covered;
+    const long long long_tiles = g_expect_long_tiles;   // this call's, whether it succeeds or not
+    g_expect_long_tiles = -1;
     StatusBlock* t = nullptr;
     SR_TRY(ticket_acquire(&t));
     int rc = launch_stage1(view, c.v, c.s, c.g, radii, t->pinned_dev, status_block_arm(*t, c.st), c.st);
     if (!rc) rc = launch_stage2(view, c.v, c.s, c.g, c.b, c.im, out_color, out_depth, out_alpha, nullptr, covered,
-                                longest_list_expected >= 0 && longest_list_expected <= longest_list_hint ? longest_list_expected : -1, c.st);
+                                longest_list_expected >= 0 && longest_list_expected <= longest_list_hint ? longest_list_expected : -1,
+                                long_tiles, c.st);
     if (rc) {   // nothing of this call may still write the block when it is handed out again
         (void)hipStreamSynchronize(c.st);
         ticket_recycle(t);
@@ -435,17 +464,26 @@ int sr_ticket_wait(void* ticket, long long* instances_out, long long* longest_li
     }
     if (instances_out) *instances_out = (long long)t->pinned[0];
     if (longest_list_out) *longest_list_out = (long long)t->pinned[1];
+    g_last_long_tiles = (long long)t->pinned[4];
     ticket_recycle(t);
     return 0;
 }
 
 long long sr_last_longest_list(void) { return g_last_longest; }
+long long sr_last_long_tiles(void) { return g_last_long_tiles; }
+int sr_expect_long_tiles(long long tiles) { g_expect_long_tiles = tiles < 0 ? -1 : tiles; return 0; }
 
 int sr_ticket_release(void* ticket) { return sr_ticket_wait(ticket, nullptr, nullptr); }
 
 int sr_debug_counters(long long* out4, int reset) {
     if (!out4) return fail("null pointer in sr_debug_counters");
     for (int i = 0; i < 4; ++i) out4[i] = reset ? g_counters[i].exchange(0, std::memory_order_relaxed) : g_counters[i].load(std::memory_order_relaxed);
+    return 0;
+}
+
+int sr_debug_sort_counters(long long* out4, int reset) {
+    if (!out4) return fail("null pointer in sr_debug_sort_counters");
+    for (int i = 0; i < 4; ++i) out4[i] = reset ? g_sort_counters[i].exchange(0, std::memory_order_relaxed) : g_sort_counters[i].load(std::memory_order_relaxed);
     return 0;
 }
 
@@ -533,6 +571,11 @@ int sr_backward_splats(const SrView* view, const SrSplats* splats, const void* g
 int sr_set_backward_kernel(int which) {
     if (which < 0 || which > 2) return -1;
     return g_bwd_kernel.exchange(which, std::memory_order_relaxed);
+}
+
+int sr_set_sort_kernel(int which) {
+    if (which < 0 || which > 2) return -1;
+    return g_sort_kernel.exchange(which, std::memory_order_relaxed);
 }
 
 int sr_mark_visible(int n, const float* means3D, const float* viewmatrix, const float*, unsigned char* present, void* hip_stream) {

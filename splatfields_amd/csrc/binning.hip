@@ -8,7 +8,10 @@
 //  * Each tile's list -- ~900 entries at 1 M splats / 800x800, thousands in dense scenes -- is sorted by one workgroup on
 //    the 64-bit key (depth bits << 32 | splat index), whose low half is also the payload: a key-only bitonic network held
 //    in registers (lane exchanges by DPP / v_permlane swaps, 3 LDS stages) for runs of <= 1024 entries, and pairwise
-//    merge-path passes in LDS for longer lists.  A splat appears once per tile, so the key is unique and the order is exactly
+//    merge-path passes in LDS for longer lists.  The bodies live in sort_tile.h.  WHO runs them: lists of up to 2048 entries
+//    (and, on views with at most kInlineLongTiles of them, lists of up to 4096) are sorted by the workgroup of
+//    k_render_forward that blends the tile (render.hip) -- no launch of their own; the kernels of this file sort the longer
+//    classes in front of the forward (launch_sort_tiles), and k_sort_tiles_regs is kept behind the standalone switch.  A splat appears once per tile, so the key is unique and the order is exactly
 //    the published "stable sort by depth, ties by splat index": a total order, independent of the arrival order of the
 //    scatter (bit-reproducible).
 // HBM traffic per instance: 8 B scatter write + 8 B sort read + 4 B sorted write, versus 6 radix passes x 24 B for a
@@ -16,6 +19,7 @@
 #include <atomic>
 #include "kernels.h"
 #include "expand.h"
+#include "sort_tile.h"
 
 namespace sr {
 
@@ -245,6 +249,9 @@ __global__ void __launch_bounds__(1024) k_scan_small(const Geom g, int n_sub, in
                 cand = cls >= 255u ? (uint32_t)n : s_hist[cls + 1u];   // exclusive prefix = tiles in classes 0 .. cls
             }
             g.total[4 + tid] = cand;
+            // [4] = slots that can hold a list of more than 2048 entries, [5] = host_seq once it is there: what the host needs
+            // to leave the launch of that class out (launch_sort_tiles)
+            if (tid == 0 && host_out) { host_out[4] = cand; __hip_atomic_store(host_out + 5, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
         }
         __syncthreads();
         if (in_regs) {
@@ -391,245 +398,20 @@ void launch_emit(const ViewK& v, int N, const Geom& g, const Binning& b, hipStre
         hipLaunchKernelGGL(k_emit<false>, dim3(ch.n_sub), dim3(kBlock), 0, st, v, N, g, b, ch);
 }
 
-// ---- per-tile sort: register-resident bitonic network ---------------------------------------------------------
-// 256 threads, E consecutive elements per thread (N = 256*E).  A compare-exchange at distance j is
-//   j < E        : inside one thread's registers,
-//   j < 64*E     : with lane (lane ^ j/E) of the same wavefront through a cross-lane shuffle,
-//   otherwise    : with another wavefront through LDS -- exactly 3 such stages for every N.
-// (A network living entirely in LDS moves all 12 bytes/entry through LDS log2(N)(log2(N)+1)/2 times -- 55 for N = 1024 --
-// and was LDS-bandwidth bound in the first version; this one touches LDS 3 times.)
-// Value of lane (lane ^ D) without touching LDS (ds_bpermute_b32 measured at ~24 cycles per wave-instruction
-// per SIMD on MI355X, DPP adds/moves at ~4, v_permlane*_swap at ~8):
-//   D = 1, 2 : DPP quad_perm          D = 8 : DPP row_ror:8 (rotation by 8 in a row of 16 is xor 8)
-//   D = 4    : row_ror:4 for lanes with bit 2 set, row_ror:12 for the others
-//   D = 16/32: v_permlane16_swap / v_permlane32_swap of the value with itself, then pick the swapped half
-template <int D>
-__device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
-    if constexpr (D == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false);
-    else if constexpr (D == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, false);
-    else if constexpr (D == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x128, 0xf, 0xf, false);
-    else if constexpr (D == 4) {
-        const uint32_t a = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x124, 0xf, 0xf, false);  // from lane-4 (mod 16)
-        const uint32_t b = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x12C, 0xf, 0xf, false);  // from lane+4 (mod 16)
-        return (threadIdx.x & 4u) ? a : b;
-    } else if constexpr (D == 16) {
-        typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-        const u2 r = __builtin_amdgcn_permlane16_swap(x, x, false, false);  // r.x rows = (x0,x0,x2,x2), r.y rows = (x1,x1,x3,x3)
-        return (threadIdx.x & 16u) ? r.x : r.y;
-    } else {
-        typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-        const u2 r = __builtin_amdgcn_permlane32_swap(x, x, false, false);  // r.x = (lo,lo), r.y = (hi,hi)
-        return (threadIdx.x & 32u) ? r.x : r.y;
-    }
-}
-
-// d is a compile-time constant after the network loops are unrolled; the dead branches fold away
-__device__ __forceinline__ uint32_t lane_xor_d(uint32_t x, int d) {
-    switch (d) {
-        case 1: return lane_xor<1>(x);
-        case 2: return lane_xor<2>(x);
-        case 4: return lane_xor<4>(x);
-        case 8: return lane_xor<8>(x);
-        case 16: return lane_xor<16>(x);
-        default: return lane_xor<32>(x);
-    }
-}
-
-// The sort key is (view-depth bits << 32) | splat index: unique inside a tile (a splat appears once per tile), equal
-// depths are ordered by splat index like the stable radix sort of the published pipeline.  The payload IS the low half
-// of the key, so the network moves 8 bytes per entry and nothing else.
-__device__ __forceinline__ void exchange_select(uint64_t& k, uint64_t pk, bool keep_min) {
-    // keys are unique except for the +inf padding, where either choice is fine: one compare, mask xnor, 2 selects
-    const bool take = (pk < k) == keep_min;
-    k = take ? pk : k;
-}
-
-// `tid` is the thread's index inside its 256-thread group (several groups of one workgroup may run the same network
-// side by side on different data; the barriers inside are workgroup-wide, so all groups must call it together).
-template <int N, int E>
-__device__ __forceinline__ void bitonic_regs(uint64_t (&k)[E], uint64_t* skey, uint32_t tid) {
-#pragma unroll
-    for (int kk = 2; kk <= N; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            if (j < E) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if ((e & j) == 0) {
-                        const uint32_t i = tid * E + e;
-                        const bool asc = (i & kk) == 0;
-                        const bool swap = (k[e] > k[e | j]) == asc;
-                        const uint64_t ka = k[e], kb = k[e | j];
-                        k[e] = swap ? kb : ka; k[e | j] = swap ? ka : kb;
-                    }
-                }
-            } else if (j < 64 * E) {
-                const int d = j / E;
-                const bool lower = (tid & d) == 0;
-                // kk >= 2j > E here, so the direction bit (i & kk) depends on the thread only
-                const bool keep_min = lower == (((tid * E) & kk) == 0);
-                uint32_t plo[E], phi[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    plo[e] = lane_xor_d((uint32_t)k[e], d);
-                    phi[e] = lane_xor_d((uint32_t)(k[e] >> 32), d);
-                }
-#pragma unroll
-                for (int e = 0; e < E; ++e) exchange_select(k[e], ((uint64_t)phi[e] << 32) | plo[e], keep_min);
-            } else {
-                __syncthreads();
-#pragma unroll
-                for (int e = 0; e < E; ++e) skey[tid * E + e] = k[e];
-                __syncthreads();
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const uint32_t i = tid * E + e;
-                    const bool asc = (i & kk) == 0;
-                    const bool lower = (i & j) == 0;
-                    exchange_select(k[e], skey[i ^ j], lower == asc);
-                }
-            }
-        }
-    }
-}
-
-// Loads up to N = 256*E consecutive entries (padding with +inf keys), sorts them in registers; afterwards
-// thread t holds the entries of rank t*E .. t*E+E-1.
-template <int N, int E>
-__device__ __forceinline__ void load_sort_chunk(const Binning& b, uint32_t first, uint32_t m, uint64_t (&k)[E], uint64_t* scratch_key, uint32_t tid) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const uint32_t i = tid * E + e;
-        k[e] = i < m ? b.ent[first + i] : ~0ull;
-    }
-    bitonic_regs<N, E>(k, scratch_key, tid);
-}
-
-template <int N, int E>
-__device__ __forceinline__ void sort_tile_regs(const Binning& b, uint32_t start, uint32_t n, uint64_t* skey) {
-    uint64_t k[E];
-    load_sort_chunk<N, E>(b, start, n, k, skey, threadIdx.x);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const uint32_t i = threadIdx.x * E + e;
-        if (i < n) b.sorted_id[start + i] = (uint32_t)k[e];
-    }
-}
-
-// forward declaration (defined below): runs of 1024 sorted by the register network + pairwise merge passes in LDS
-template <int CAP, int THREADS, typename Emit>
-__device__ __forceinline__ void sort_block_lds(const Binning& b, uint32_t first, uint32_t n, uint64_t* run_key, Emit&& emit);
-
-// Lists of 1..2048 entries, one workgroup (256 threads) per tile, LDS 16 KiB: up to 1024 entries one register network;
-// 1025..2048 two runs sorted one after the other + the merge pass.  One launch for what used to be two (a launch per length
-// class spins up one workgroup per tile just to find out that most lists belong to the other class: at the headline
-// workload 2500 workgroups each, plus the launch gap, for ~40 % of the tiles).
+// Lists of 1..2048 entries, one workgroup (256 threads) per tile, LDS 16 KiB (sort_tile_small, sort_tile.h).  Since the
+// forward blend sorts these lists itself (render.hip) this kernel is launched only under the standalone-sort switch
+// (SPLATRASTER_SORT=standalone / sr_set_sort_kernel(1)): the A/B of the fusion, and a second path to the same lists for the
+// tests.
 __global__ void __launch_bounds__(256) k_sort_tiles_regs(const Geom g, const Binning b) {
-    __shared__ uint64_t skey[2048];
+    __shared__ uint64_t skey[kSortSmallMax];
     const uint32_t total_instances = g.total[0];
     const uint32_t tile = g.tile_order[blockIdx.x];  // longest lists first
     asm volatile("" :: "s"(tile));   // requested together with the count above, not behind the early exit (one round trip less per workgroup)
     if (total_instances > b.capacity) return;
     const uint32_t start = g.tile_start[tile];
     const uint32_t n = g.tile_start[tile + 1] - start;
-    if (n == 0u || n > 2048u) return;
-    if (n <= 256u) sort_tile_regs<256, 1>(b, start, n, skey);
-    else if (n <= 512u) sort_tile_regs<512, 2>(b, start, n, skey);
-    else if (n <= 1024u) sort_tile_regs<1024, 4>(b, start, n, skey);
-    else sort_block_lds<2048, 256>(b, start, n, skey, [&](uint32_t rank, uint64_t key) { b.sorted_id[start + rank] = (uint32_t)key; });
-}
-
-// One merge pass in LDS: src[0, n) holds sorted runs of `width` entries (the last one may be short); adjacent pairs are
-// merged, out(position, key) receives every entry with its position after the pass.  Merge path: a thread produces E
-// consecutive outputs of its pair -- one binary search along the diagonal for where they start in the two runs
-// (log2(width) probes per THREAD), then E sequential compare-and-advance steps with one LDS read each.  (Ranking every
-// entry by its own binary search in the other run costs log2(width) dependent probes per ENTRY: a quarter to a third of the
-// whole sort at lists of 2000-3000 entries.)  Keys are unique.  E divides 2 * width.
-template <int E, typename Out>
-__device__ __forceinline__ void merge_run_pairs(const uint64_t* src, uint32_t n, uint32_t width, Out&& out) {
-    const uint32_t o = threadIdx.x * (uint32_t)E;  // first output of this thread
-    if (o >= n) return;
-    const uint32_t base = o & ~(2u * width - 1u);  // start of the pair
-    const uint64_t* A = src + base;                 // run B follows run A at A + width
-    const uint32_t a = min(width, n - base);
-    const uint32_t b = n - base - a < width ? n - base - a : width;
-    const uint32_t d = o - base;                    // outputs of the pair before this thread's
-    uint32_t lo = d > b ? d - b : 0u, hi = min(d, a);
-    while (lo < hi) {                               // smallest ai with A[ai] > B[d - 1 - ai]
-        const uint32_t mid = (lo + hi) >> 1;
-        if (A[mid] < A[width + d - 1u - mid]) lo = mid + 1u; else hi = mid;
-    }
-    uint32_t ai = lo, bi = d - lo;
-    constexpr uint64_t kInf = ~0ull;
-    uint64_t ka = ai < a ? A[ai] : kInf;
-    uint64_t kb = bi < b ? A[width + bi] : kInf;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const bool take_a = ka < kb;
-        const uint64_t key = take_a ? ka : kb;
-        if (d + (uint32_t)e < a + b) out(o + (uint32_t)e, key);
-        ai += take_a ? 1u : 0u;
-        bi += take_a ? 0u : 1u;
-        const bool more = take_a ? ai < a : bi < b;
-        const uint64_t nxt = A[take_a ? min(ai, a - 1u) : width + min(bi, max(b, 1u) - 1u)];
-        if (take_a) ka = more ? nxt : kInf; else kb = more ? nxt : kInf;
-    }
-}
-
-// Sorts n <= CAP entries starting at b.ent[first]: runs of 1024 are sorted by the register network into LDS (one
-// 256-thread group per run, side by side), then merged pairwise (merge_run_pairs) until one run is left.  A list of 1100
-// entries costs a 1024- and a 256-network instead of the 2048-network of a power-of-two bitonic sort.
-// emit(rank, key) receives every entry with its final rank.  run_key: CAP entries, + CAP more when n > 2048.
-// Ends with a workgroup barrier.
-template <int CAP, int THREADS, typename Emit>
-__device__ __forceinline__ void sort_block_lds(const Binning& b, uint32_t first, uint32_t n, uint64_t* run_key, Emit&& emit) {
-    constexpr int GROUPS = THREADS / 256;
-    const uint32_t group = threadIdx.x >> 8, tid = threadIdx.x & 255u;
-    const uint32_t n_runs = (n + 1023u) / 1024u;
-    for (uint32_t r0 = 0; r0 < n_runs; r0 += GROUPS) {  // uniform trip count: the barriers below are workgroup-wide
-        const uint32_t r = r0 + group;
-        const uint32_t m = r < n_runs ? min(1024u, n - r * 1024u) : 0u;
-        __syncthreads();  // scratch reuse
-        // Every network size has exactly 3 cross-wavefront (LDS) stages = 6 workgroup barriers, so groups may run
-        // differently sized networks side by side: a short last run does not pay for a 1024-network.  A group uses the
-        // 1024-entry area of its run as the scratch of those stages and then leaves the sorted run there.
-        // r < CAP/1024 always (CAP/1024 is a multiple of GROUPS); an idle group (m = 0) sorts padding in its own free slot.
-        uint64_t* rk = run_key + r * 1024u;
-        uint64_t k[4];  // a 256- / 512-network uses the first 1 / 2 of them
-        if (m <= 256u) {
-            uint64_t k1[1];
-            load_sort_chunk<256, 1>(b, first + r * 1024u, m, k1, rk, tid);
-            k[0] = k1[0];
-        } else if (m <= 512u) {
-            uint64_t k2[2];
-            load_sort_chunk<512, 2>(b, first + r * 1024u, m, k2, rk, tid);
-            k[0] = k2[0]; k[1] = k2[1];
-        } else {
-            load_sort_chunk<1024, 4>(b, first + r * 1024u, m, k, rk, tid);
-        }
-        __syncthreads();  // every wavefront is past the last LDS stage of its network before the area is overwritten
-        const uint32_t per = m <= 256u ? 1u : (m <= 512u ? 2u : 4u);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t i = tid * per + e;
-            if ((uint32_t)e < per && i < m) rk[i] = k[e];
-        }
-    }
-    __syncthreads();
-    // Pairwise merge passes over the runs (1024 -> 2048 -> ...); the last one hands the entries to emit().  Lists of up
-    // to 2048 entries (two runs) need one pass and no second buffer; longer ones ping-pong with run_key + CAP.
-    uint64_t* src = run_key;
-    uint64_t* dst = run_key + CAP;
-    for (uint32_t width = 1024u;; width <<= 1) {
-        if (2u * width >= n) {
-            merge_run_pairs<CAP / THREADS>(src, n, width, emit);
-            break;
-        }
-        merge_run_pairs<CAP / THREADS>(src, n, width, [&](uint32_t pos, uint64_t key) { dst[pos] = key; });
-        __syncthreads();
-        uint64_t* t = src; src = dst; dst = t;
-    }
-    __syncthreads();
+    if (n == 0u || n > kSortSmallMax) return;
+    sort_tile_small(b, start, n, skey);
 }
 
 // lists of (LO, CAP] entries, one workgroup per tile; LDS = CAP * 16 bytes (runs + merge ping-pong buffer)
@@ -639,6 +421,8 @@ __global__ void __launch_bounds__(THREADS) k_sort_tiles_merge(const Geom g, cons
     uint64_t* run_key = reinterpret_cast<uint64_t*>(s_dyn);
     if (g.total[0] > b.capacity) return;
     const uint32_t limit = min((uint32_t)n_tiles, g.total[LO == 2048 ? 4 : 5]);   // slots that can hold a list longer than LO
+    // a view with few long tiles: the forward blend sorts them (it evaluates the same condition on the same words)
+    if (LO == 2048 && b.sort_in_blend >= kSortInlineMax && few_long_tiles(g.total[4], g.total[1])) return;
     for (uint32_t slot = blockIdx.x; slot < limit; slot += gridDim.x) {
         const uint32_t tile = g.tile_order[slot];  // longest lists first
         const uint32_t start = g.tile_start[tile];
@@ -702,23 +486,40 @@ __global__ void __launch_bounds__(THREADS) k_sort_tiles_long(const Geom g, const
 // headroom: a long-list class that is launched only because of the headroom -- no list of its length is expected -- gets a
 // grid of a few workgroups (they find Geom::total[4..6] = 0 slots and leave; should a list have grown into the class after
 // all, they sort it) instead of 512 x 1024 threads that start up to find nothing.
-void launch_sort_tiles(const ViewK& v, const Geom& g, const Binning& b, long long max_len, long long expected_len, hipStream_t st) {
+// Launches only the classes ABOVE 2048 entries unless b.sort_in_blend says that the forward blend does not sort the others.
+// Returns which classes it launched (sr_debug_sort_counters).
+int launch_sort_tiles(const ViewK& v, const Geom& g, const Binning& b, long long max_len, long long expected_len, long long long_tiles,
+                      hipStream_t st) {
     const int tiles = v.gx * v.gy;
-    if (tiles <= 0) return;
+    if (tiles <= 0) return 0;
+    int launched = 0;   // bit k: class k has a launch (k_sort_tiles_regs, 2049..4096, 4097..8192, longer)
     auto lds = [](int cap, int) { return (size_t)cap * 16; };   // the runs + the ping-pong buffer of the merge passes
-    hipLaunchKernelGGL(k_sort_tiles_regs, dim3(tiles), dim3(256), 0, st, g, b);   // every list of up to 2048 entries
-    if (max_len >= 0 && max_len <= 2048) return;
+    // every list of up to 2048 entries: by the forward blend itself (Binning::sort_in_blend), or here under the standalone switch
+    if (b.sort_in_blend < kSortSmallMax) { hipLaunchKernelGGL(k_sort_tiles_regs, dim3(tiles), dim3(256), 0, st, g, b); launched |= 1; }
+    if (max_len >= 0 && max_len <= 2048) return launched;
     allow_dynamic_lds(reinterpret_cast<const void*>(&k_sort_tiles_merge<2048, 4096, 1024>), 2, (int)lds(4096, 1024));
     allow_dynamic_lds(reinterpret_cast<const void*>(&k_sort_tiles_merge<4096, 8192, 1024>), 3, (int)lds(8192, 1024));
     allow_dynamic_lds(reinterpret_cast<const void*>(&k_sort_tiles_long<8192, 1024>), 4, (int)lds(8192, 1024));
     // the long classes walk the head of tile_order (Geom::total[4..6] slots) with a grid of at most two workgroups per CU
     const int long_grid = tiles < 512 ? tiles : 512;
     auto grid_for = [&](long long lo) { return (expected_len >= 0 && expected_len <= lo) ? (long_grid < 8 ? long_grid : 8) : long_grid; };
-    hipLaunchKernelGGL((k_sort_tiles_merge<2048, 4096, 1024>), dim3(grid_for(2048)), dim3(1024), lds(4096, 1024), st, g, b, tiles);
-    if (max_len >= 0 && max_len <= 4096) return;
+    // long_tiles: how many tiles can hold a list of more than 2048 entries, if the host knows (sr_forward: the figure itself) or
+    // expects (sr_forward_async) it; < 0: no idea.  Few of them and nothing beyond 4096: the forward blend sorts them, and
+    // this launch -- one or two busy workgroups on an otherwise idle GPU -- is left out.  Binning::long_class_launched tells the
+    // forward, so a wrong expectation costs time, never a sorted list.
+    const long long longest = expected_len >= 0 ? expected_len : max_len;
+    const bool leave_to_blend = b.sort_in_blend >= kSortInlineMax && long_tiles >= 0 && long_tiles <= (long long)kInlineLongTiles &&
+                                longest >= 0 && longest <= (long long)kSortInlineMax;
+    if (!leave_to_blend) {
+        hipLaunchKernelGGL((k_sort_tiles_merge<2048, 4096, 1024>), dim3(grid_for(2048)), dim3(1024), lds(4096, 1024), st, g, b, tiles);
+        launched |= 2;
+    }
+    if (max_len >= 0 && max_len <= 4096) return launched;
     hipLaunchKernelGGL((k_sort_tiles_merge<4096, 8192, 1024>), dim3(grid_for(4096)), dim3(1024), lds(8192, 1024), st, g, b, tiles);
-    if (max_len >= 0 && max_len <= 8192) return;
+    launched |= 4;
+    if (max_len >= 0 && max_len <= 8192) return launched;
     hipLaunchKernelGGL((k_sort_tiles_long<8192, 1024>), dim3(grid_for(8192)), dim3(1024), lds(8192, 1024), st, g, b, tiles);
+    return launched | 8;
 }
 
 }  // namespace sr

@@ -109,6 +109,13 @@ struct Binning {
                              // launched -- the host knew the longest list).  sr_forward_async launches the classes a HINT asks for
                              // without waiting for the real figure: k_render_forward exits if a longer list exists (its ids were
                              // never written), and the caller finds out when it redeems the ticket
+    uint32_t sort_in_blend;  // lists of 1..sort_in_blend entries are sorted by the workgroup of k_render_forward that blends them:
+                             // 4096 (the product path; the lists of 2049..4096 entries only on views that have few of them,
+                             // sort_tile.h: few_long_tiles), 2048, or 0: every class has a launch of its own in front of the forward
+                             // (sr_set_sort_kernel / SPLATRASTER_SORT).  Set per launch by api.hip: launch_stage2
+    uint32_t long_class_launched;   // k_sort_tiles_merge<2048, 4096> is in the stream in front of this forward (it still leaves the
+                             // lists to the forward on a view with few long tiles).  0: the host left it out -- it knew, or
+                             // expected, few long tiles -- and the forward sorts every list of 2049..4096 entries it meets
 };
 
 struct Image {
@@ -170,6 +177,8 @@ inline size_t carve_binning(void* base, long long R, Binning* b) {
     t.reached = c.take<uint8_t>(r);
     t.capacity = (uint32_t)(R > 0 ? R : 0);
     t.sorted_up_to = 0xffffffffu;
+    t.sort_in_blend = 0u;
+    t.long_class_launched = 1u;
     if (b) *b = t;
     return align_up(c.off, 256);
 }

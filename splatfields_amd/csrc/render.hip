@@ -6,7 +6,8 @@
 // reference's second "mask" pass (gaussian_renderer/__init__.py:104-115) unnecessary.
 //
 // MI355X mapping: one workgroup (4 wavefronts) per 16x16 binning tile; each 64-lane wavefront owns
-// one 8x8 sub-tile.  A batch of the tile's sorted list is staged once in LDS by all 256 threads
+// one 8x8 sub-tile.  The forward workgroup first SORTS the list of its tile (sort_tile.h; lists of up to 2048 entries, and
+// the few of up to 4096 -- longer ones were sorted by the launches of binning.hip in front of this kernel), then blends it.  A batch of the tile's sorted list is staged once in LDS by all 256 threads
 // (coalesced id loads + 48-byte record gathers), then every wavefront compacts -- with one ballot per
 // 64 entries -- the indices of the splats whose alpha >= 1/255 support box reaches *its* 8x8 pixels
 // and blends only those, reading records back with LDS broadcast reads.  Early termination is per
@@ -14,6 +15,7 @@
 // reductions, combines the 4 wavefronts through LDS in a fixed order and writes ONE record per
 // tile-splat instance to a scratch slot: no floating-point atomics anywhere, bit-reproducible.
 #include "kernels.h"
+#include "sort_tile.h"
 #define SR_QM_DEVICE 1
 #include "quadmask.h"
 
@@ -75,7 +77,9 @@ __device__ __forceinline__ void publish_tile_reach(const Geom& g, int tile, uint
 // ------------------------------------------------------------------------------------------
 // Forward
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_render_forward(const ViewK v, const Geom g, const Binning b, const Image im,
+// (amdgpu_waves_per_eu: the unrolled sort network at the head of the kernel holds its compare directions in scalar register
+// pairs -- 106 scalar registers if left alone, which is seven wavefronts per SIMD; the kernel lives on its eight.)
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) k_render_forward(const ViewK v, const Geom g, const Binning b, const Image im,
                                                            float* __restrict__ out_color, float* __restrict__ out_depth,
                                                            float* __restrict__ out_alpha) {
     // Staging area of one batch of the tile's list: the three hot quarters of every entry's record and its quad-reach mask.
@@ -87,19 +91,27 @@ __global__ void __launch_bounds__(kBlock) k_render_forward(const ViewK v, const 
     static_assert(kB == 256 || kB == 128, "a batch is staged by four or by two wavefronts");
     constexpr int kStagers = kB / kWave;       // wavefronts that stage one batch
     constexpr uint32_t kStep = 4 / kStagers;   // a wavefront stages every kStep-th batch
-    __shared__ float4 s_r0[1][kB];
-    __shared__ float4 s_r1[1][kB];
-    __shared__ float4 s_r2[1][kB];
-    __shared__ uint16_t s_qm[1][kB];   // quad-reach mask of every staged entry (quadmask.h)
+    // The staging area and the scratch of the sort at the head of the kernel (16 KiB: sort_tile_inline) are ONE block of LDS: the
+    // sort is over, behind a workgroup barrier, before the first batch is staged.  17 KB in all, eight workgroups per CU.
+    typedef float4 Quarter[1][kB];
+    typedef uint16_t QuadMasks[1][kB];
+    typedef uint8_t QuadIndex[4][4][kB + 4];
+    constexpr size_t kStageBytes = 3 * sizeof(Quarter) + sizeof(QuadMasks) + sizeof(QuadIndex), kSortBytes = kSortSmallMax * sizeof(uint64_t);
+    __shared__ __attribute__((aligned(16))) unsigned char s_blk[kStageBytes > kSortBytes ? kStageBytes : kSortBytes];
+    Quarter& s_r0 = *reinterpret_cast<Quarter*>(s_blk);
+    Quarter& s_r1 = *reinterpret_cast<Quarter*>(s_blk + sizeof(Quarter));
+    Quarter& s_r2 = *reinterpret_cast<Quarter*>(s_blk + 2 * sizeof(Quarter));
+    QuadMasks& s_qm = *reinterpret_cast<QuadMasks*>(s_blk + 3 * sizeof(Quarter));   // quad-reach mask of every staged entry (quadmask.h)
+    QuadIndex& s_idx = *reinterpret_cast<QuadIndex*>(s_blk + 3 * sizeof(Quarter) + sizeof(QuadMasks));   // per wavefront and quad of its
+                                                 // sub-tile: the batch entries that reach the quad (+ 4: the pipelined walk reads
+                                                 // its index two trips ahead)
     __shared__ uint32_t s_live[2][4];            // per batch parity and wavefront: does it still have accumulating pixels?
-    __shared__ uint8_t s_idx[4][4][kB + 4];      // per wavefront and quad of its sub-tile: the batch entries that reach the quad
-                                                 // (+ 4: the pipelined walk reads its index two trips ahead)
     // the pipelined walk fetches a record by an index byte it has not masked yet (a stale byte of s_idx): any byte must be a slot
     static_assert(kB == 256, "the pipelined walk indexes the staging area with unmasked bytes: 256 slots");
 
     // (the three scalar loads are requested together and tested with one wait: written as `a > x || b > y` ahead of the tile
     // lookup they were three dependent memory round trips at the head of every workgroup)
-    const uint32_t total_instances = g.total[0], longest_list = g.total[1];
+    const uint32_t total_instances = g.total[0], longest_list = g.total[1], long_slots = g.total[4];
     const int tile = (int)g.tile_order[blockIdx.x];  // longest lists first
     asm volatile("" :: "s"(tile));   // (keeps the compiler from sinking this load below the early exit: it is requested with the two above)
     if ((total_instances > b.capacity) | (longest_list > b.sorted_up_to)) {   // uniform: see sr_forward / sr_forward_async
@@ -119,8 +131,30 @@ __global__ void __launch_bounds__(kBlock) k_render_forward(const ViewK v, const 
         }
         return;
     }
+    const uint32_t start = g.tile_start[tile], end = g.tile_start[tile + 1];
+    // The list of this tile is sorted HERE, by the workgroup that blends it, when it has up to 2048 entries: with the bodies
+    // k_sort_tiles_regs runs in a launch of its own under the standalone switch (sort_tile.h).  The WHOLE list goes to
+    // b.sorted_id -- the entries behind every pixel's stop as well: the backward and the list read-backs see complete lists.
+    // The ids are read back from memory by other threads of the workgroup: release, barrier, acquire at workgroup scope.
+    // Longer lists were sorted by the launches of their classes in front of this kernel (launch_sort_tiles).
+    // A list of 2049..4096 entries is sorted here too when k_sort_tiles_merge<2048, 4096> left it alone: on a view with few
+    // such lists (that kernel makes the same test on the same words), or because the host did not launch it at all.
+    const uint32_t n_list = end - start;
+    const bool short_list = n_list <= min(b.sort_in_blend, kSortSmallMax);
+    const bool long_list = !short_list && n_list <= kSortInlineMax && b.sort_in_blend >= kSortInlineMax &&
+                           (b.long_class_launched == 0u || few_long_tiles(long_slots, longest_list));
+    if ((n_list != 0u) & (short_list | long_list)) {   // uniform
+        sort_tile_inline(b, start, n_list, reinterpret_cast<uint64_t*>(s_blk));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();   // also: the scratch is free to become the staging area
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // Everything per lane is computed from here on -- behind the sort, which wants the registers (the compiler would otherwise
+    // carry a dozen pixel coordinates through the network and spill).
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
     const int tx = tile % v.gx, ty = tile / v.gx;
-    const int wave = __builtin_amdgcn_readfirstlane(wave_id()), lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = (int)(tid & 63u);
     const int sx = tx * kTile + (wave & 1) * kSub, sy = ty * kTile + (wave >> 1) * kSub;
     // row j of 16 lanes = quad j of the sub-tile (4x4 pixels): every row walks ITS quad's entries
     const int qrow = lane >> 4;
@@ -128,7 +162,6 @@ __global__ void __launch_bounds__(kBlock) k_render_forward(const ViewK v, const 
     const bool inside = px < v.W && py < v.H;
     const float tx0f = (float)(tx * kTile), ty0f = (float)(ty * kTile);
     const float Xf = (float)(px - tx * kTile), Yf = (float)(py - ty * kTile);   // this lane's pixel relative to the tile
-    const uint32_t start = g.tile_start[tile], end = g.tile_start[tile + 1];
     // the four 4x4 quads of this wavefront's 8x8 sub-tile as bits 4 qy + qx
     const uint32_t my_quads = 0x33u << (2 * (wave & 1) + 8 * (wave >> 1));
 
@@ -146,7 +179,7 @@ __global__ void __launch_bounds__(kBlock) k_render_forward(const ViewK v, const 
     {
     // Which wavefronts stage batch k: all four (256 entries), or {0, 1} for even k and {2, 3} for odd k (128 entries).
     auto stages = [&](uint32_t k) { return kStagers == 4 || (uint32_t)(wave >> 1) == (k & 1u); };
-    const int slot = kStagers == 4 ? (int)threadIdx.x : (int)(threadIdx.x & 127u);   // this thread's entry of a batch it stages
+    const int slot = kStagers == 4 ? (int)tid : (int)(tid & 127u);   // this thread's entry of a batch it stages
     const int wslot = kStagers == 4 ? wave : (wave & 1);                              // its wavefront's 64-entry group there
     // LDS byte addresses of this wavefront's 64 slots in each copy (wave-uniform: the copy instruction adds 16 x lane)
     const uint32_t l0 = lds_address(&s_r0[0][wslot * kWave]), l1 = lds_address(&s_r1[0][wslot * kWave]), l2 = lds_address(&s_r2[0][wslot * kWave]);

@@ -159,6 +159,18 @@ def set_backward_kernel(which) -> str:
     return {0: "auto", 1: "wave", 2: "quads"}[prev]
 
 
+_SORT_KERNELS = {None: 0, "auto": 0, "inline": 0, "standalone": 1, "short": 2}
+
+
+def set_sort_kernel(which) -> str:
+    """Who sorts the tile lists of up to 4096 entries (A/B measurements, the tests that compare the paths): None / "auto" /
+    "inline" = the forward blend's workgroup sorts the list it blends (lists of 2049..4096 entries only on views with few of
+    them), "standalone" = sort kernels in launches of their own in front of the forward blend, "short" = inline up to 2048
+    entries only.  Same lists, images and gradients bit for bit.  Returns the previous setting."""
+    prev = _lib.load().sr_set_sort_kernel(_SORT_KERNELS[which])
+    return {0: "inline", 1: "standalone", 2: "short"}[prev]
+
+
 def _round_capacity(instances: int) -> int:
     """Capacity for `instances` tile-splat instances: 25 % headroom, rounded UP to eight steps per power of two.  The sizes of
     the binning buffer and of the backward scratch follow the capacity, and a training loop renders a different view -- a
@@ -185,6 +197,7 @@ class _Promise(NamedTuple):
     hint: Optional[int] = None  # None: the launch waits for its count (sr_forward); else the longest list to sort for, with headroom
     expected: int = -1          # ... and without
     covered: int = 0            # the longest list the sort classes of `hint` cover
+    long_tiles: int = -1        # tiles expected to hold a list of more than 2048 entries (sr_expect_long_tiles; < 0: unknown)
 
 
 # What finished forwards have taught the facade, used to size the binning buffer BEFORE the instance count is known, so that
@@ -200,6 +213,9 @@ class _Estimates:
     def __init__(self):
         self.capacity = {}    # (device index, n, H, W) -> capacity that size needed so far
         self.per_splat = {}   # (device index, H, W) -> most instances per splat this image size has shown
+        self.long_tiles = {}  # (id of a camera's `seen` table, splat count) -> tiles that can hold a list of more than 2048 entries,
+                              # as the camera's last render reported them (< 0: unknown).  Only ever an expectation
+                              # (sr_expect_long_tiles): a stale row -- a recycled id -- costs time, never a result
         self.lock = threading.Lock()
 
     def plan(self, device_index: int, n: int, H: int, W: int, view, may_async: bool) -> _Promise:
@@ -211,14 +227,16 @@ class _Estimates:
             ratio = self.per_splat.get((device_index, H, W))
             capacity = self.capacity.get(key) or (max(4 * n, 1 << 16) if ratio is None else _round_capacity(int(ratio * n)))
             before = view.seen.get(n) if may_async else None
+            long_tiles = int(self.long_tiles.get((id(view.seen), n), -1))
         # this camera was rendered with this splat count before, within the capacity: launch without waiting (see _ASYNC above)
         if before is None or _round_capacity(before[0]) > capacity:
             return _Promise(key, capacity)
         hint = int(before[1] * _HEADROOM) + 1
-        return _Promise(key, capacity, hint, int(before[1]), _covered_by_hint(hint))
+        return _Promise(key, capacity, hint, int(before[1]), _covered_by_hint(hint), long_tiles)
 
-    def record(self, promise: _Promise, view, instances: int, longest: int) -> None:
-        """A forward launched on `promise` reported `instances` and a longest tile list of `longest` (< 0: unknown)."""
+    def record(self, promise: _Promise, view, instances: int, longest: int, long_tiles: int = -1) -> None:
+        """A forward launched on `promise` reported `instances`, a longest tile list of `longest` (< 0: unknown) and `long_tiles`
+        tiles that can hold a list of more than 2048 entries (< 0: unknown)."""
         global LAST_INSTANCES
         dev, n, H, W = key = promise.key
         rkey = (dev, H, W)
@@ -231,6 +249,9 @@ class _Estimates:
                 if len(view.seen) > self.SEEN_ROWS:
                     view.seen.clear()
                 view.seen[n] = (int(instances), int(longest))
+                if len(self.long_tiles) > self.CAPACITY_ROWS:
+                    self.long_tiles.clear()
+                self.long_tiles[(id(view.seen), n)] = int(long_tiles)
             LAST_INSTANCES = instances
 
 
@@ -273,11 +294,14 @@ class _Pending:
     def _redeem(self, ticket):
         inst, longest = C.c_longlong(0), C.c_longlong(0)
         rc = self.lib.sr_ticket_wait(ticket, C.byref(inst), C.byref(longest))
+        # the long-tile figure of the wait this thread just made (thread-local in the library); self.lib is only asked for the
+        # ticket entries
+        long_tiles = int(_lib.load().sr_last_long_tiles()) if rc == 0 else -1
         with _PENDING_LOCK:
             self._list[:] = [r for r in self._list if r() is not None and r() is not self]
         _lib.check(rc)
         instances, longest, promise = int(inst.value), int(longest.value), self.promise
-        _ESTIMATES.record(promise, self.view, instances, longest)
+        _ESTIMATES.record(promise, self.view, instances, longest, long_tiles)
         covered = max(promise.covered, 2048)
         if instances > promise.capacity or longest > covered:
             return RasterizerOverflow(
@@ -478,6 +502,7 @@ def _launch_forward(lib, view, splats, n: int, H: int, W: int, dev, may_async: b
         if promise.hint is not None:
             # this camera was rendered with this splat count before: launch without waiting (see _ASYNC above)
             ticket = C.c_void_p()
+            lib.sr_expect_long_tiles(promise.long_tiles)   # of this thread's next sr_forward_async: the one below
             _lib.check(lib.sr_forward_async(*state, _ptr(radii), _ptr(binning), capacity, promise.hint, promise.expected, *outs,
                                             C.byref(ticket), stream))
             return geom, binning, image, capacity, None, _Pending(lib, ticket, promise, view)
@@ -486,7 +511,7 @@ def _launch_forward(lib, view, splats, n: int, H: int, W: int, dev, may_async: b
         if status != _lib.SR_NEED_CAPACITY:
             _lib.check(status)
         instances = int(inst.value)
-        _ESTIMATES.record(promise, view, instances, int(lib.sr_last_longest_list()))
+        _ESTIMATES.record(promise, view, instances, int(lib.sr_last_longest_list()), int(lib.sr_last_long_tiles()))
         if status == _lib.SR_NEED_CAPACITY:
             # first call for this size, or the cloud grew: re-run stage 2 with a buffer that fits
             capacity = _round_capacity(instances)
