@@ -1,7 +1,9 @@
 // Fused MLP kernels of the SplatFields deform network for gfx950: the layer chain (forward, and the
 // activation-gradient chain of the backward), the weight packer, and the weight-gradient kernel.  The chain and the packer exist
 // three times: exact fp32 (the default, described here) and, opt-in, with bf16 matrix operands (k_mlp_chain_bf16 below) or with
-// operands split into two bf16 values, three MFMAs per product (k_mlp_chain_bf16x3, mlp_bf16x3.h).
+// operands split into two bf16 values, three MFMAs per product (k_mlp_chain_bf16x3, mlp_bf16x3.h).  Each chain has its own copy
+// of the op interpreter: as policies of one shared body the fp32 and bf16x3 kernels compile to other code and measured slower
+// (DESIGN.md section 22); the packers share what they have in common (mlp_pack_source, mlp_pack_bias, mlp_pack_bf16_parts).
 //
 // What it replaces: reference utils/time_utils.py:123-191 (`GeneralMLP`: Linear -> activation for every layer, the
 // input concatenated back in front of the hidden state after the `skips` layers), which PyTorch-ROCm runs as one GEMM +
@@ -457,6 +459,22 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
 
 struct MlpPackK { SrMlpPackJob job[SR_MLP_MAX_PACK_JOBS]; };
 
+// Element (r, cp) of a job's padded matrix: padded column cp is a memory column, then a column of the register state; the padding
+// of either and the rows past n_rows are zero.
+__device__ __forceinline__ float mlp_pack_source(const SrMlpPackJob& J, int r, int cp) {
+    int col = -1;
+    if (cp < J.mem_pad) { if (cp < J.n_mem) col = J.mem_col0 + cp; }
+    else if (cp - J.mem_pad < J.n_reg) col = J.reg_col0 + cp - J.mem_pad;
+    if (r >= J.n_rows || col < 0) return 0.0f;
+    return J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
+}
+
+// the bias of a job, padded with zeros to its output tiles: fp32 in every precision
+__device__ __forceinline__ void mlp_pack_bias(const SrMlpPackJob& J) {
+    if (J.bias_dst && blockIdx.x == 0)
+        for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
+}
+
 // One packed float per thread step: thread index = the destination index, decoded to (c, mt, tl, lane, i) -> (row, column).
 __global__ void __launch_bounds__(kBlock) k_mlp_pack(const MlpPackK jobs) {
     const SrMlpPackJob J = jobs.job[blockIdx.y];
@@ -466,45 +484,39 @@ __global__ void __launch_bounds__(kBlock) k_mlp_pack(const MlpPackK jobs) {
         const int i = d & 3, lane = (d >> 2) & 63, tl = (d >> 8) & 1;
         const int rest = d >> 9;                       // c * MT + mt
         const int mt = rest % J.out_tiles, c = rest / J.out_tiles;
-        const int r = 16 * mt + (lane & 15);
-        const int cp = 16 * (2 * c + tl) + 4 * (lane >> 4) + i;
-        int col = -1;
-        if (cp < J.mem_pad) { if (cp < J.n_mem) col = J.mem_col0 + cp; }
-        else if (cp - J.mem_pad < J.n_reg) col = J.reg_col0 + cp - J.mem_pad;
-        float v = 0.0f;
-        if (r < J.n_rows && col >= 0) v = J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
-        J.dst[d] = v;
+        J.dst[d] = mlp_pack_source(J, 16 * mt + (lane & 15), 16 * (2 * c + tl) + 4 * (lane >> 4) + i);
     }
-    if (J.bias_dst && blockIdx.x == 0)
-        for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
+    mlp_pack_bias(J);
 }
 
-// The matrix of a job rounded to bf16 in the layout k_mlp_chain_bf16 reads (above): two adjacent packed elements (j, j + 1 = two
-// adjacent columns of the same 4-column group) per thread step, one 4-byte store.  The bias is copied as fp32.
-__global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16(const MlpPackK jobs) {
+// The matrix of a job as bf16 in the layout the bf16 chunks read (above): two adjacent packed elements (j, j + 1 = two adjacent
+// columns of the same 4-column group) per thread step, one 4-byte store.  PARTS = 1: the values rounded to bf16 (k_mlp_pack_bf16);
+// PARTS = 2: per chunk the block of the rounded values and then the block of their remainders (k_mlp_pack_bf16x3, mlp_bf16x3.h).
+template <int PARTS>
+__device__ __forceinline__ void mlp_pack_bf16_parts(const MlpPackK& jobs) {
     const SrMlpPackJob J = jobs.job[blockIdx.y];
-    const int pairs = 8 * J.out_tiles * (J.mem_pad + J.reg_width);
+    const int pairs = PARTS * 8 * J.out_tiles * (J.mem_pad + J.reg_width);
     uint32_t* dst = reinterpret_cast<uint32_t*>(J.dst);
     for (int d = blockIdx.x * kBlock + (int)threadIdx.x; d < pairs; d += gridDim.x * kBlock) {
         const int j = 2 * (d & 3), lane = (d >> 2) & 63;
-        const int rest = d >> 8;                       // c * MT + mt
-        const int mt = rest % J.out_tiles, c = rest / J.out_tiles;
+        const int rest = d >> 8;                       // (PARTS c + part) * MT + mt
+        const int mt = rest % J.out_tiles, cpart = rest / J.out_tiles;
+        const int part = PARTS == 2 ? cpart & 1 : 0, c = PARTS == 2 ? cpart >> 1 : cpart;
         const int r = 16 * mt + (lane & 15);
         const int cp = 32 * c + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-        float v[2] = {0.0f, 0.0f};
+        __bf16 p[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            int col = -1;
-            if (cp + e < J.mem_pad) { if (cp + e < J.n_mem) col = J.mem_col0 + cp + e; }
-            else if (cp + e - J.mem_pad < J.n_reg) col = J.reg_col0 + cp + e - J.mem_pad;
-            if (r < J.n_rows && col >= 0) v[e] = J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
+            const float v = mlp_pack_source(J, r, cp + e);
+            const __bf16 h = (__bf16)v;
+            p[e] = part ? (__bf16)(v - (float)h) : h;
         }
-        const __bf16 lo = (__bf16)v[0], hi = (__bf16)v[1];
-        dst[d] = (uint32_t)__builtin_bit_cast(unsigned short, lo) | ((uint32_t)__builtin_bit_cast(unsigned short, hi) << 16);
+        dst[d] = (uint32_t)__builtin_bit_cast(unsigned short, p[0]) | ((uint32_t)__builtin_bit_cast(unsigned short, p[1]) << 16);
     }
-    if (J.bias_dst && blockIdx.x == 0)
-        for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
+    mlp_pack_bias(J);
 }
+
+__global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16(const MlpPackK jobs) { mlp_pack_bf16_parts<1>(jobs); }
 
 // the split-bf16 ("bf16x3") chains and their packer: k_mlp_chain_bf16x3, k_mlp_chain_group_bf16x3, k_mlp_pack_bf16x3
 #include "mlp_bf16x3.h"
@@ -678,7 +690,7 @@ int launch_mlp_weight_grad(int n_points, int n_jobs, const SrMlpGradJob* jobs, v
 }
 
 // chain precision of a launch: which packer / chain kernel runs (validation is the same for all three)
-enum MlpMode { kMlpFp32 = 0, kMlpBf16 = 1, kMlpBf16x3 = 2 };
+enum MlpMode { kMlpFp32 = 0, kMlpBf16 = 1, kMlpBf16x3 = 2, kMlpModes };      // kMlpModes: the size of the kernel tables below
 
 int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, MlpMode mode, hipStream_t st) {
     if (n_jobs < 0 || n_jobs > SR_MLP_MAX_PACK_JOBS) return 1;
@@ -694,18 +706,10 @@ int launch_mlp_pack(int n_jobs, const SrMlpPackJob* jobs, MlpMode mode, hipStrea
         k.job[j] = s;
         most = max(most, 16 * s.out_tiles * (s.mem_pad + s.reg_width));
     }
-    if (mode == kMlpBf16) {           // two elements per thread step
-        const int bx = min(64, (most / 2 + kBlock * 4 - 1) / (kBlock * 4));
-        hipLaunchKernelGGL(k_mlp_pack_bf16, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
-        return 0;
-    }
-    if (mode == kMlpBf16x3) {         // two elements per thread step, two parts
-        const int bx = min(64, (most + kBlock * 4 - 1) / (kBlock * 4));
-        hipLaunchKernelGGL(k_mlp_pack_bf16x3, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
-        return 0;
-    }
-    const int bx = min(64, (most + kBlock * 4 - 1) / (kBlock * 4));
-    hipLaunchKernelGGL(k_mlp_pack, dim3(bx, n_jobs), dim3(kBlock), 0, st, k);
+    static void (*const kernel[])(const MlpPackK) = {k_mlp_pack, k_mlp_pack_bf16, k_mlp_pack_bf16x3};
+    static_assert(sizeof(kernel) / sizeof(kernel[0]) == kMlpModes, "one packer per precision");
+    const int steps = mode == kMlpBf16 ? most / 2 : most;     // thread steps, two elements each for the bf16 kinds: bf16 most / 2 pairs, bf16x3 two parts of most / 2 pairs
+    hipLaunchKernelGGL(kernel[mode], dim3(min(64, (steps + kBlock * 4 - 1) / (kBlock * 4)), n_jobs), dim3(kBlock), 0, st, k);
     return 0;
 }
 
@@ -731,22 +735,10 @@ int launch_mlp_chain(int n_points, int hidden_tiles, int n_ops, const SrMlpOp* o
         net.op[l] = ops[l];
     }
     if (n_points <= 0) return 0;
-    const int blocks = (n_points + 127) / 128;
-    if (mode == kMlpBf16) {
-        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_bf16<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-        else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain_bf16<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-        else return 1;
-        return 0;
-    }
-    if (mode == kMlpBf16x3) {
-        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_bf16x3<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-        else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain_bf16x3<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-        else return 1;
-        return 0;
-    }
-    if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain<8>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-    else if (hidden_tiles == 4) hipLaunchKernelGGL((k_mlp_chain<4>), dim3(blocks), dim3(kBlock), 0, st, net, n_points, slope);
-    else return 1;
+    if (hidden_tiles != 4 && hidden_tiles != 8) return 1;
+    static void (*const kernel[kMlpModes][2])(const MlpK, int, float) = {
+        {k_mlp_chain<4>, k_mlp_chain<8>}, {k_mlp_chain_bf16<4>, k_mlp_chain_bf16<8>}, {k_mlp_chain_bf16x3<4>, k_mlp_chain_bf16x3<8>}};
+    hipLaunchKernelGGL(kernel[mode][hidden_tiles == 8], dim3((n_points + 127) / 128), dim3(kBlock), 0, st, net, n_points, slope);
     return 0;
 }
 
@@ -772,18 +764,10 @@ const char* launch_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, c
     for (int y = n_nets; y <= SR_MLP_GROUP_MAX_NETS; ++y) grp.first[y] = total;
     if (n_points == 0 || n_nets == 0) return nullptr;
     const dim3 grid((n_points + 127) / 128, n_nets);
-    if (mode == kMlpBf16) {
-        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group_bf16<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
-        else hipLaunchKernelGGL((k_mlp_chain_group_bf16<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
-        return nullptr;
-    }
-    if (mode == kMlpBf16x3) {
-        if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group_bf16x3<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
-        else hipLaunchKernelGGL((k_mlp_chain_group_bf16x3<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
-        return nullptr;
-    }
-    if (hidden_tiles == 8) hipLaunchKernelGGL((k_mlp_chain_group<8>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
-    else hipLaunchKernelGGL((k_mlp_chain_group<4>), grid, dim3(kBlock), 0, st, grp, n_points, slope);
+    static void (*const kernel[kMlpModes][2])(const MlpGroupK, int, float) = {
+        {k_mlp_chain_group<4>, k_mlp_chain_group<8>}, {k_mlp_chain_group_bf16<4>, k_mlp_chain_group_bf16<8>},
+        {k_mlp_chain_group_bf16x3<4>, k_mlp_chain_group_bf16x3<8>}};
+    hipLaunchKernelGGL(kernel[mode][hidden_tiles == 8], grid, dim3(kBlock), 0, st, grp, n_points, slope);
     return nullptr;
 }
 
@@ -1355,22 +1339,22 @@ static int mlp_group_entry(const char* name, const char* why, const char* kernel
     return check_hip(hipGetLastError(), kernel);
 }
 
+static int mlp_chain_group_entry(const char* name, const char* kernel, sr::MlpMode mode, int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
+    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail(std::string(name) + ": negative_slope must be in [0, 1)");
+    return mlp_group_entry(name, sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, mode, static_cast<hipStream_t>(hip_stream)),
+                           kernel, n_points == 0 || n_nets == 0);
+}
+
 int sr_mlp_chain_group(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
-    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group: negative_slope must be in [0, 1)");
-    return mlp_group_entry("sr_mlp_chain_group", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpFp32,
-                                                                            static_cast<hipStream_t>(hip_stream)), "mlp_chain_group", n_points == 0 || n_nets == 0);
+    return mlp_chain_group_entry("sr_mlp_chain_group", "mlp_chain_group", sr::kMlpFp32, n_points, hidden_tiles, n_nets, nets, negative_slope, hip_stream);
 }
 
 int sr_mlp_chain_group_bf16(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
-    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16: negative_slope must be in [0, 1)");
-    return mlp_group_entry("sr_mlp_chain_group_bf16", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpBf16,
-                                                                                 static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16", n_points == 0 || n_nets == 0);
+    return mlp_chain_group_entry("sr_mlp_chain_group_bf16", "mlp_chain_group_bf16", sr::kMlpBf16, n_points, hidden_tiles, n_nets, nets, negative_slope, hip_stream);
 }
 
 int sr_mlp_chain_group_bf16x3(int n_points, int hidden_tiles, int n_nets, const SrMlpNet* nets, float negative_slope, void* hip_stream) {
-    if (!(negative_slope >= 0.0f && negative_slope < 1.0f)) return fail("sr_mlp_chain_group_bf16x3: negative_slope must be in [0, 1)");
-    return mlp_group_entry("sr_mlp_chain_group_bf16x3", sr::launch_mlp_chain_group(n_points, hidden_tiles, n_nets, nets, negative_slope, sr::kMlpBf16x3,
-                                                                                   static_cast<hipStream_t>(hip_stream)), "mlp_chain_group_bf16x3", n_points == 0 || n_nets == 0);
+    return mlp_chain_group_entry("sr_mlp_chain_group_bf16x3", "mlp_chain_group_bf16x3", sr::kMlpBf16x3, n_points, hidden_tiles, n_nets, nets, negative_slope, hip_stream);
 }
 
 int sr_mlp_group_input_forward(int n_points, int n_heads, const SrMlpHeadInput* heads, int n_features, int time_multires, const float* xyz,

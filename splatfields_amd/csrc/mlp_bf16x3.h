@@ -52,8 +52,9 @@ __device__ __forceinline__ void mlp_chunk_bf16x3(f32x4 (&acc)[2][HT], const bf16
     }
 }
 
-// body of k_mlp_chain_bf16x3 and k_mlp_chain_group_bf16x3: the op interpreter of mlp_chain_body_bf16 (its own copy: a mode
-// parameter on the shared body would recompile the bf16 kernels); s_w: two chunks of a packed matrix, [part][mt][lane]
+// body of k_mlp_chain_bf16x3 and k_mlp_chain_group_bf16x3: the op interpreter of mlp_chain_body_bf16 (its own copy: as a
+// policy of one shared body the 64-wide kernels compile to other code and measured 1 % slower);
+// s_w: two chunks of a packed matrix, [part][mt][lane]
 template <int HT>
 __device__ __forceinline__ void mlp_chain_body_bf16x3(const SrMlpOp* ops, const int n_ops, bf16x8 (&s_w)[2][HT * 128], int n_points, float slope) {
     const int wave = wave_id(), lane = lane_id();
@@ -195,36 +196,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HT 
     mlp_chain_body_bf16x3<HT>(grp.op + f0, grp.first[blockIdx.y + 1] - f0, s_w, n_points, slope);
 }
 
-// The matrix of a job split into hi = bf(v) and lo = bf(v - hi) in the layout k_mlp_chain_bf16x3 reads (above): the lane -> K
-// permutation of k_mlp_pack_bf16, per chunk the hi block and then the lo block.  Two adjacent packed elements of one part per
-// thread step, one 4-byte store; the destination holds 2 x 16 out_tiles (mem_pad + reg_width) bfloat16.  The bias is copied as fp32.
-__global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16x3(const MlpPackK jobs) {
-    const SrMlpPackJob J = jobs.job[blockIdx.y];
-    const int pairs = 16 * J.out_tiles * (J.mem_pad + J.reg_width);      // both parts
-    uint32_t* dst = reinterpret_cast<uint32_t*>(J.dst);
-    for (int d = blockIdx.x * kBlock + (int)threadIdx.x; d < pairs; d += gridDim.x * kBlock) {
-        const int j = 2 * (d & 3), lane = (d >> 2) & 63;
-        const int rest = d >> 8;                       // (2 c + part) * MT + mt
-        const int mt = rest % J.out_tiles, cpart = rest / J.out_tiles;
-        const int part = cpart & 1, c = cpart >> 1;
-        const int r = 16 * mt + (lane & 15);
-        const int cp = 32 * c + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);
-        float v[2] = {0.0f, 0.0f};
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            int col = -1;
-            if (cp + e < J.mem_pad) { if (cp + e < J.n_mem) col = J.mem_col0 + cp + e; }
-            else if (cp + e - J.mem_pad < J.n_reg) col = J.reg_col0 + cp + e - J.mem_pad;
-            if (r < J.n_rows && col >= 0) v[e] = J.transposed ? J.w[(size_t)col * J.ld + J.row0 + r] : J.w[(size_t)(J.row0 + r) * J.ld + col];
-        }
-        __bf16 p[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const __bf16 h = (__bf16)v[e];
-            p[e] = part ? (__bf16)(v[e] - (float)h) : h;
-        }
-        dst[d] = (uint32_t)__builtin_bit_cast(unsigned short, p[0]) | ((uint32_t)__builtin_bit_cast(unsigned short, p[1]) << 16);
-    }
-    if (J.bias_dst && blockIdx.x == 0)
-        for (int j = (int)threadIdx.x; j < 16 * J.out_tiles; j += kBlock) J.bias_dst[j] = j < J.n_bias ? J.bias_src[j] : 0.0f;
-}
+// The matrix of a job split into hi = bf(v) and lo = bf(v - hi) in the layout above: the lane -> K permutation of k_mlp_pack_bf16,
+// per chunk the hi block and then the lo block (mlp_pack_bf16_parts<2>, mlp.hip).  The destination holds
+// 2 x 16 out_tiles (mem_pad + reg_width) bfloat16.  The bias is copied as fp32.
+__global__ void __launch_bounds__(kBlock) k_mlp_pack_bf16x3(const MlpPackK jobs) { mlp_pack_bf16_parts<2>(jobs); }

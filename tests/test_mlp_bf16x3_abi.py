@@ -38,8 +38,9 @@ def test_symbols_are_declared_exported_bound_and_additions_only(lib):
         assert [f[1] for f in abi_text.structs()[name]] == [f[0] for f in getattr(_lib, name)._fields_]
     # the siblings' validation is the new entries' validation: one function each, the mode is an argument
     code = abi_text.source("mlp.hip")
-    for entry in ("mlp_chain_entry(", "mlp_pack_entry(", "launch_mlp_chain_group("):
+    for entry in ("mlp_chain_entry(", "mlp_pack_entry(", "mlp_chain_group_entry("):
         assert code.count(entry) == 4, entry                                       # the definition and one call per precision
+    assert code.count("launch_mlp_chain_group(") == 2                              # the definition and mlp_chain_group_entry's call
     assert code.count("static bool mlp_op_ok(") == 1
 
 
