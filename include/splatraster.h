@@ -45,6 +45,9 @@
  *   sr_adam_step
  *        <- reference train.py:314-322 (`gaussians.optimizer.step()`), the `torch.optim.Adam` of scene/gaussian_model.py:130-139:
  *           every tensor of the step in one launch.
+ *   sr_net_adam_plan, sr_net_adam_step
+ *        <- reference train.py:318 (`deform.optimizer.step()`), the `torch.optim.Adam` of scene/deform_model.py:23-34 over the
+ *           deform network's 71 to 502 parameter tensors: a job table in device memory, one launch per 480 tensors.
  *   sr_groupnorm_stats, sr_conv3x3_forward / _backward_data / _weight_grad, sr_groupnorm_silu_backward
  *        <- reference scene/time_decoders.py (`TimeVAEDecoder`) behind scene/tripFields.py:176-204 (`Tensorial2D`): the plane
  *           generator's GroupNorm -> SiLU -> [nearest x2] -> conv 3x3 -> [+ residual] layers, all planes per launch.
@@ -483,6 +486,43 @@ typedef struct SrAdamJob {
     float step_size, bias_correction2_sqrt, one_minus_beta1, one_minus_beta2, eps;
 } SrAdamJob;
 int sr_adam_step(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible_or_null, long long rows, void* hip_stream);
+
+/* The Adam step of the deform network (reference train.py:318 `deform.optimizer.step()`; scene/deform_model.py:23-34 builds
+ * `torch.optim.Adam(l, lr=0.0, eps=1e-15)` over every parameter of the network: 71 to 502 tensors, most of them under 1024
+ * elements).  The arithmetic is sr_adam_step's, bit for bit.  What differs is how the job list travels: the addresses of a
+ * network's parameters and moments do not change from step to step, so they live in a TABLE IN DEVICE MEMORY that the caller
+ * owns and writes once (one SrNetAdamSlot per tensor), and a step passes only what changes -- the range of the table it covers,
+ * one set of scalars and the range's gradient pointers -- by value as the kernel argument: no copy, no staging buffer, nothing
+ * to reuse too early and no wait.  One launch covers up to SR_NET_ADAM_MAX_GRADS consecutive table entries.
+ *
+ * Chunking.  A tensor's elements are laid over slots of four floats from the 16-byte boundary at or below `param`; a chunk is 512
+ * slots of one tensor; `chunk_end` is the running sum of the chunk counts over the table (entry i owns the chunks
+ * chunk_end[i-1] .. chunk_end[i] - 1, a tensor of 0 elements owns none).  It depends on `param` and `count` alone, never on the
+ * gradient's address: sr_net_adam_plan (host only, no device) fills it, and sr_net_adam_step refuses a table it disagrees with.
+ * Whether a tensor's interior moves as 16-byte vectors (its four addresses agree modulo 16) or element by element is decided in
+ * the kernel per step; both give the same bits.
+ *
+ * sr_net_adam_step: `table_host` and `table_dev` are the same `table_len` records in host and in device memory; the entries
+ * first .. first + n - 1 are stepped with `scalars`, entry first + i with the gradient grads_host[i]; a NULL gradient skips that
+ * tensor in this launch: its parameter and moments keep their bits.  Everything is validated on the host from `table_host`
+ * before the launch: count in 0 .. 2^31 - 1, no NULL and 4-byte alignment of every pointer of a tensor that is stepped (the
+ * gradients included), chunk_end as sr_net_adam_plan fills it.  n = 0, a range whose gradients are all NULL and a range whose
+ * counts are all 0 launch nothing and succeed without a device.  No LDS, no atomics, nothing waits for the device, and the
+ * library keeps no memory of its own. */
+#define SR_NET_ADAM_MAX_GRADS 480
+typedef struct SrNetAdamSlot {
+    float* param;
+    float* exp_avg;
+    float* exp_avg_sq;
+    long long count;
+    long long chunk_end;
+} SrNetAdamSlot;
+typedef struct SrNetAdamScalars {
+    float step_size, bias_correction2_sqrt, one_minus_beta1, one_minus_beta2, eps;
+} SrNetAdamScalars;
+int sr_net_adam_plan(SrNetAdamSlot* table_host, int table_len);
+int sr_net_adam_step(const SrNetAdamSlot* table_host, const SrNetAdamSlot* table_dev, int table_len, int first, int n,
+                     const float* const* grads_host, const SrNetAdamScalars* scalars, void* hip_stream);
 
 /* Fused MLP chains of the SplatFields deform network's `GeneralMLP`s (reference utils/time_utils.py:123-191; SURVEY.md
  * section 8f row 4): n_points points are carried through a list of OPS in ONE kernel, the running state (<= 16 * hidden_tiles

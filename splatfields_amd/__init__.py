@@ -6,6 +6,7 @@ from .losses import (centered_position_norm, depth_l1_loss, l1_loss, opacity_reg
 from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
 from .optim import SplatAdam  # noqa: F401
+from .network_optim import NetworkAdam, network_optimizer, set_network_optimizer  # noqa: F401
 from .fused_mlp import heads, mlp_precision, set_heads, set_mlp_precision  # noqa: F401
 from .flow_head import flow_head_path, fused_flow_head, set_flow_head  # noqa: F401
 from .view_color import fused_view_color, set_view_color, view_color_path  # noqa: F401

@@ -79,6 +79,16 @@ class SrAdamJob(C.Structure):
                 ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
 
 
+class SrNetAdamSlot(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("count", C.c_longlong),
+                ("chunk_end", C.c_longlong)]
+
+
+class SrNetAdamScalars(C.Structure):
+    _fields_ = [("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float), ("one_minus_beta1", C.c_float),
+                ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
+
+
 class SrPlaneJob(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in (
         "x", "weight", "bias", "gamma", "beta", "stats", "residual", "out", "pre", "dy", "dx", "dweight", "dbias", "dgamma", "dbeta",
@@ -112,6 +122,7 @@ MLP_MAX_GRAD_JOBS, MLP_MAX_GRAD_TASKS = 16, 128
 MLP_MAX_PACK_JOBS = 32
 MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatraster.h: SR_MORAN_MAX_TENSORS, SR_KNN_MAX_K
 ADAM_MAX_TENSORS = 32                                        # include/splatraster.h: SR_ADAM_MAX_TENSORS
+NET_ADAM_MAX_GRADS = 480                                     # include/splatraster.h: SR_NET_ADAM_MAX_GRADS
 QUANT_NONE, QUANT_PNG, QUANT_TO8B = 0, 1, 2                     # include/splatraster.h: SR_QUANT_*
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
 MLP_GROUP_MAX_NETS, MLP_GROUP_MAX_OPS, MLP_GROUP_MAX_HEADS = 8, 40, 8      # include/splatraster.h: SR_MLP_GROUP_*
@@ -181,6 +192,9 @@ SYMBOLS = {
                                    C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
     "sr_adam_step": (C.c_int, [C.c_int, C.POINTER(SrAdamJob), C.c_void_p, C.c_longlong, C.c_void_p]),
+    "sr_net_adam_plan": (C.c_int, [C.POINTER(SrNetAdamSlot), C.c_int]),
+    "sr_net_adam_step": (C.c_int, [C.POINTER(SrNetAdamSlot), C.POINTER(SrNetAdamSlot), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                   C.POINTER(SrNetAdamScalars), C.c_void_p]),
     "sr_splat_reg_workspace_bytes": (C.c_size_t, [C.c_int]),
     "sr_splat_reg_forward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_splat_reg_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,

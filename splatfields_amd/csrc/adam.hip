@@ -5,7 +5,8 @@
 //
 //   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;   p = p - step_size * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 //
-// with step_size = lr / (1 - beta1^t) and the other scalars computed by the caller in double.  Both moments are evaluated in
+// with step_size = lr / (1 - beta1^t) and the other scalars computed by the caller in double.  The element's arithmetic and the
+// 16-byte accesses are adam_math.h's, shared with network_adam.hip.  Both moments are evaluated in
 // torch's `lerp` form, m + (1 - beta1) (g - m): the two weights then add up to 1 exactly.  With a float32 beta beside a
 // float32 1 - beta they do not (0.9f + 0.1f is off by 1e-8, 0.999f + 0.001f by 1.3e-8), and that error enters the moment once
 // per step and adds up over 1 / (1 - beta) steps -- 1.3e-5 of v for beta2 = 0.999.  `/` and sqrtf are the correctly
@@ -24,25 +25,11 @@
 //
 // No LDS, no atomics, no scratch; every store is a vector store.
 #include "host_api.h"
+#include "adam_math.h"
 
 namespace sr {
 
 namespace {
-
-#ifndef SR_ADAM_UNROLL
-#define SR_ADAM_UNROLL 2        // A/B switch: 2 keeps the dense kernel at 56 registers (8 waves per SIMD), 4 needs 88 (5 waves)
-#endif
-constexpr int kAdamUnroll = SR_ADAM_UNROLL;              // slots a thread has in flight in a full chunk
-constexpr int kAdamChunkSlots = kBlock * kAdamUnroll;   // 512 slots = 8 KB of each of the four streams
-constexpr int kAdamBlocksPerCu = 8;                      // 32 waves per CU
-
-#ifndef SR_ADAM_NONTEMPORAL
-// A/B switch (tools/adam_bench.py --variants, profiles/adam_bench.json): bit 0 = the gradients are read with non-temporal loads,
-// bit 1 = parameter and moments are written with non-temporal stores.  Measured: bit 0 takes the step at 1 M splats from 0.325 to
-// 0.279 ms and costs 1 % at 300 k, bit 1 alone gives 0.287, both 0.279.  0 is shipped: the build with bit 0 as the default has
-// only been timed on the device, not run through tests/test_gpu_adam.py ("Next").
-#define SR_ADAM_NONTEMPORAL 0
-#endif
 
 struct AdamTable {
     SrAdamJob job[SR_ADAM_MAX_TENSORS];
@@ -54,39 +41,7 @@ struct AdamTable {
 // floats between the 16-byte boundary below a job's first element and that element; -1 when its four addresses disagree
 // modulo 16 (no vector path: the job goes element by element from slot 0)
 __host__ __device__ __forceinline__ int adam_lead(const SrAdamJob& job) {
-    const unsigned lp = ((unsigned)(uintptr_t)job.param >> 2) & 3u, lg = ((unsigned)(uintptr_t)job.grad >> 2) & 3u;
-    const unsigned lm = ((unsigned)(uintptr_t)job.exp_avg >> 2) & 3u, lv = ((unsigned)(uintptr_t)job.exp_avg_sq >> 2) & 3u;
-    return (lp == lg && lp == lm && lp == lv) ? (int)lp : -1;
-}
-
-struct AdamScalars { float step_size, bias2_sqrt, om_beta1, om_beta2, eps; };
-
-__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, const AdamScalars& k) {
-    m = fmaf(k.om_beta1, g - m, m);
-    v = fmaf(k.om_beta2, fmaf(g, g, -v), v);
-    const float denom = sqrtf(v) / k.bias2_sqrt + k.eps;
-    const float ratio = m / denom;
-    p = fmaf(-k.step_size, ratio, p);
-}
-
-typedef float NativeFloat4 __attribute__((ext_vector_type(4)));   // what the non-temporal builtins take
-
-__device__ __forceinline__ float4 load_grad4(const float* g) {
-#if SR_ADAM_NONTEMPORAL & 1
-    const NativeFloat4 v = __builtin_nontemporal_load(reinterpret_cast<const NativeFloat4*>(g));
-    return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4*>(g);
-#endif
-}
-
-__device__ __forceinline__ void store4(float* dst, const float4& value) {
-#if SR_ADAM_NONTEMPORAL & 2
-    const NativeFloat4 v = {value.x, value.y, value.z, value.w};
-    __builtin_nontemporal_store(v, reinterpret_cast<NativeFloat4*>(dst));
-#else
-    *reinterpret_cast<float4*>(dst) = value;
-#endif
+    return adam_same_lead(job.param, job.grad, job.exp_avg, job.exp_avg_sq) ? (int)adam_lead_of(job.param) : -1;
 }
 
 // bit i set: virtual element 4 slot + i belongs to a visible row (the slot lies inside the tensor)
@@ -98,21 +53,6 @@ __device__ __forceinline__ unsigned visible_bits(const unsigned char* __restrict
         if (++c == row) { c = 0; ++r; }
     }
     return bits;
-}
-
-__device__ __forceinline__ void adam_vector(float4& p, const float4& g, float4& m, float4& v, unsigned bits, const AdamScalars& k) {
-    float pn[4] = {p.x, p.y, p.z, p.w}, mn[4] = {m.x, m.y, m.z, m.w}, vn[4] = {v.x, v.y, v.z, v.w};
-    const float gn[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float pi = pn[i], mi = mn[i], vi = vn[i];
-        adam_element(pi, gn[i], mi, vi, k);
-        const bool on = (bits >> i) & 1u;      // a hidden element keeps the bits that were loaded
-        pn[i] = on ? pi : pn[i]; mn[i] = on ? mi : mn[i]; vn[i] = on ? vi : vn[i];
-    }
-    p = make_float4(pn[0], pn[1], pn[2], pn[3]);
-    m = make_float4(mn[0], mn[1], mn[2], mn[3]);
-    v = make_float4(vn[0], vn[1], vn[2], vn[3]);
 }
 
 template <bool MASKED>
@@ -185,17 +125,6 @@ __global__ __launch_bounds__(kBlock) void k_adam(const AdamTable t) {
     }
 }
 
-int cu_count() {   // of the current device; one query per device and process
-    static int cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cached[dev] == 0) {
-        int n = 0;
-        cached[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cached[dev];
-}
-
 void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible, hipStream_t st) {
     AdamTable t = {};
     int n = 0;
@@ -212,7 +141,7 @@ void launch_adam(int n_jobs, const SrAdamJob* jobs, const unsigned char* visible
     if (n == 0) return;
     t.total_chunks = (int)chunks;
     t.visible = visible;
-    const long long cap = (long long)cu_count() * kAdamBlocksPerCu;
+    const long long cap = (long long)adam_cu_count() * kAdamBlocksPerCu;
     const dim3 grid((unsigned)(chunks < cap ? chunks : cap));
     if (visible) hipLaunchKernelGGL(k_adam<true>, grid, dim3(kBlock), 0, st, t);
     else hipLaunchKernelGGL(k_adam<false>, grid, dim3(kBlock), 0, st, t);

@@ -428,9 +428,13 @@ class SplatFieldsModel:
     def step(self, xyz, time_emb):
         return self.deform(xyz, time_emb)
 
-    def train_setting(self, training_args):
+    def train_setting(self, training_args, optimizer: Optional[str] = None):
+        """`optimizer`: "torch" (torch.optim.Adam, as the reference), "fused" (splatfields_amd.NetworkAdam: the same step in one
+        launch per 480 tensors) or None = the process default at call time (set_network_optimizer, SPLATFIELDS_NETWORK_OPTIMIZER)."""
+        from .network_optim import NetworkAdam, resolve_network_optimizer
+        make = NetworkAdam if resolve_network_optimizer(optimizer) == "fused" else torch.optim.Adam
         lr0 = training_args.position_lr_init * self.spatial_lr_scale
-        self.optimizer = torch.optim.Adam([{"params": list(self.deform.parameters()), "lr": lr0, "name": "deform"}], lr=0.0, eps=1e-15)
+        self.optimizer = make([{"params": list(self.deform.parameters()), "lr": lr0, "name": "deform"}], lr=0.0, eps=1e-15)
         self._schedule = dict(lr_init=lr0, lr_final=training_args.position_lr_final, lr_delay_mult=training_args.position_lr_delay_mult,
                               max_steps=training_args.deform_lr_max_steps)
 
