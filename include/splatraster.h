@@ -56,6 +56,10 @@
  *           scene/dataset_readers.py:1385-1417 (`visual_hull_samples`), :1419-1458 (`visual_hull_samples_list`), :605-644 (the
  *           Blender `hull` branch of `readNerfSyntheticInfo`) and :544-588 (its `load` branch, a point cloud filtered by the same
  *           test): the host's projection of a G^3 grid into every training view, as one streaming pass plus an ordered compaction.
+ *   sr_depth_points_mark + sr_depth_points_gather / sr_depth_points_select
+ *        <- reference scene/dataset_readers.py:1476-1491 (`_gen_3dpoints`, called per camera and frame at :1376 and :1463) and
+ *           what `readNeuSceneInfo` takes from the concatenated cloud: its bounds (:1603-1613, the hull's box) or `num_pts`
+ *           random rows (:1653-1658, the `depth` initialisation): one streaming pass, an ordered compaction or a sample by rank.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -942,6 +946,50 @@ int sr_hull_carve(int n_views, const SrHullView* views, const unsigned char* mas
                   const void* points, long long n_points, int point_is_double, void* workspace, int* count_out, void* hip_stream);
 int sr_hull_gather(const double* grid, int G, const void* points, long long n_points, int point_is_double, const void* workspace,
                    long long capacity, int* indices_out, float* points_out, void* hip_stream);
+
+/* Depth-map initialisation (reference scene/dataset_readers.py:1476-1491 `_gen_3dpoints`, called at :1376 and :1463; its cloud is
+ * used at :1603-1613 for the hull's box and at :1653-1658 as the `depth` initialisation): every pixel with a positive depth of a
+ * batch of depth maps [B,H,W], back-projected.  For image b and the pixel (x, y) -- integers, no half-pixel offset --, all in
+ * double, in this order of operations (every three-term sum left to right), without fused multiply-adds:
+ *   p = kinv (x, y, 1),  v = p / sqrt(p0 p0 + p1 p1 + p2 p2),  v' = R v,  point = o + depth v'     (pose = [R | o], 3x4 row-major)
+ * rounded to float32 once.  A pixel survives iff depth > 0 (0, -0, negatives and NaN are dropped; +inf survives and gives
+ * non-finite coordinates) and, when `masks` is given, its mask byte is non-zero.  Survivors are numbered in pixel order
+ * i = b H W + y W + x.
+ *
+ * `cameras`: DEVICE array of B records, 8-byte aligned.  `depths`: device, [B,H,W] float32, or float64 with depth_is_double = 1.
+ * `masks`: device, [B,H,W] bytes, or NULL.  `images`: device, [B,H,W,3] elements of color_bytes (1, 4 or 8) bytes each, read only
+ * when colors_out is given.  `workspace`: sr_depth_points_workspace_bytes(B H W) bytes, 8-byte aligned.
+ *
+ * sr_depth_points_mark: 2 launches (one lane per pixel, then one workgroup that orders the workgroup counts and reduces the
+ *   bounds).  Writes the number of survivors to count_out (device int32) and to bounds_out (device float[2]) the smallest and the
+ *   largest float32 coordinate of the survivors, the three components together; either may be NULL, not both.  A NaN coordinate
+ *   (possible only for depth = +inf) takes no part in the bounds, an infinite one does; without any, the bounds are (+inf, -inf).
+ * sr_depth_points_gather (same batch and workspace, after the mark call): 1 launch; writes the first `capacity` survivors in pixel
+ *   order: points_out [capacity,3] float32 (recomputed, not stored by the mark call), colors_out [capacity,3] elements copied
+ *   from `images`, indices_out [capacity] int64 pixel indices; any of them may be NULL.  A capacity below the count gives an
+ *   ordered prefix.
+ * sr_depth_points_select (instead of the gather): 1 launch; row j of the outputs [n_ranks, ...] is survivor number ranks[j]
+ *   (device int64; any order, repeats allowed).  A rank outside [0, count) reads nothing and writes a row of NaN coordinates,
+ *   zero colour bytes and the index -1, and stores 1 to *flag_out (device int32), which the call otherwise leaves alone: zero it
+ *   before the call.
+ * No atomics: the same inputs give the same bytes.  Nothing waits for the device; every launch goes to hip_stream.
+ * Refused on the host, before any launch: B < 0, H or W < 1, B H W > 2^31 - 1, a depth_is_double other than 0 and 1, a
+ * color_bytes other than 1, 4 and 8 (when colors_out is given), a negative capacity or n_ranks, a null pointer where one is read
+ * or written, and a misaligned one.  B = 0 (an empty batch; mark and gather), capacity = 0, n_ranks = 0 and a call without any
+ * output launch nothing and succeed; the mark call then leaves count_out and bounds_out alone. */
+typedef struct SrDepthCamera {
+    double kinv[9];            /* rows of the inverse intrinsics' upper-left 3x3 */
+    double pose[12];           /* rows of the camera-to-world pose's upper 3x4: [R | o] */
+} SrDepthCamera;
+size_t sr_depth_points_workspace_bytes(long long n_items);
+int sr_depth_points_mark(int B, int H, int W, const SrDepthCamera* cameras, const void* depths, int depth_is_double,
+                         const unsigned char* masks, void* workspace, int* count_out, float* bounds_out, void* hip_stream);
+int sr_depth_points_gather(int B, int H, int W, const SrDepthCamera* cameras, const void* depths, int depth_is_double,
+                           const void* images, int color_bytes, const void* workspace, long long capacity, float* points_out,
+                           void* colors_out, long long* indices_out, void* hip_stream);
+int sr_depth_points_select(int B, int H, int W, const SrDepthCamera* cameras, const void* depths, int depth_is_double,
+                           const void* images, int color_bytes, const void* workspace, const long long* ranks, long long n_ranks,
+                           float* points_out, void* colors_out, long long* indices_out, int* flag_out, void* hip_stream);
 
 /* The flow head of the deform network (reference utils/time_utils.py:194-304 `FlowHead`, the last stage of a dynamic step; replaces
  * two to four nn.Linear calls, ~25 small per-point kernels and their autograd backward): per point n, with the row h = hidden[n]

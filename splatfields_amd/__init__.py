@@ -10,6 +10,6 @@ from .network_optim import NetworkAdam, network_optimizer, set_network_optimizer
 from .fused_mlp import heads, mlp_precision, set_heads, set_mlp_precision  # noqa: F401
 from .flow_head import flow_head_path, fused_flow_head, set_flow_head  # noqa: F401
 from .view_color import fused_view_color, set_view_color, view_color_path  # noqa: F401
-from .init import (hull_filter, hull_matrices, splats_from_points, visual_hull, visual_hull_samples,  # noqa: F401
-                   visual_hull_samples_list)
+from .init import (depth_point_cloud, depth_points, depth_points_bounds, gen_3dpoints, hull_filter, hull_matrices,  # noqa: F401
+                   splats_from_points, visual_hull, visual_hull_samples, visual_hull_samples_list)
 from .plane_generator import Tensorial2D, TimeVAEDecoder, VarTriPlaneEncoder, fused_attention, fused_layer, generate_planes, set_attention  # noqa: F401

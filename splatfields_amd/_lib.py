@@ -106,6 +106,10 @@ class SrHullView(C.Structure):
                 ("convention", C.c_int), ("outside", C.c_int)]
 
 
+class SrDepthCamera(C.Structure):
+    _fields_ = [("kinv", C.c_double * 9), ("pose", C.c_double * 12)]
+
+
 class SrFlowBranch(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("rows", C.c_int)]
 
@@ -212,6 +216,14 @@ SYMBOLS = {
                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_hull_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
+    # `cameras` is a DEVICE array of SrDepthCamera records: never dereferenced on the host (depth_cameras_arg casts the address)
+    "sr_depth_points_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "sr_depth_points_mark": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrDepthCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "sr_depth_points_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrDepthCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_depth_points_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrDepthCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_mlp_pack": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
     "sr_mlp_weight_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob)]),
     "sr_mlp_weight_grad": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob), C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -345,6 +357,11 @@ def check(status: int) -> None:
 def ptr(t):
     """the data pointer of a tensor as a void* argument; None (NULL) for None"""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def depth_cameras_arg(table):
+    """a float64 [B, 21] DEVICE tensor as the `const SrDepthCamera*` of sr_depth_points_*: the address only, never read here"""
+    return C.cast(C.c_void_p(table.data_ptr()), C.POINTER(SrDepthCamera))
 
 
 def stream(device):

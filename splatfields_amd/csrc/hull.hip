@@ -20,6 +20,7 @@
 // the four-term dot product inside the host's BLAS can decide.  About 20 fp64 operations per voxel and view: the pass is
 // bound by its byte gathers, not by the fp64 rate.
 #include "host_api.h"
+#include "ordered_scan.h"
 
 namespace sr {
 
@@ -99,27 +100,9 @@ __global__ void __launch_bounds__(kBlock) k_hull_carve(const HullItems it, int n
 }
 
 // exclusive prefix over the workgroup counts, in index order, in place; the total goes to `total` (workspace) and `count_out`
-__global__ void __launch_bounds__(1024) k_hull_scan(long long blocks, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ total,
-                                                    int* __restrict__ count_out) {
-    __shared__ uint32_t s_wave[1024 / kWave];
-    uint32_t carry = 0u;                                  // the same value in every thread
-    for (long long base = 0; base < blocks; base += 1024) {
-        const long long j = base + threadIdx.x;
-        const uint32_t v = j < blocks ? block_counts[j] : 0u;
-        const uint32_t inc = wave_inclusive_scan(v);
-        __syncthreads();                                  // s_wave of the previous round has been read
-        if (lane_id() == 63) s_wave[wave_id()] = inc;
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (int w = 0; w < 1024 / kWave; ++w) {
-            const uint32_t s = s_wave[w];
-            if (w < wave_id()) before += s;
-            all += s;
-        }
-        if (j < blocks) block_counts[j] = carry + before + inc - v;
-        carry += all;
-    }
+__global__ void __launch_bounds__(kScanBlock) k_hull_scan(long long blocks, uint32_t* __restrict__ block_counts,
+                                                          uint32_t* __restrict__ total, int* __restrict__ count_out) {
+    const uint32_t carry = ordered_scan_counts(blocks, block_counts);
     if (threadIdx.x == 0) { *total = carry; if (count_out) *count_out = (int)carry; }
 }
 
@@ -172,7 +155,7 @@ hipError_t launch_hull_carve(int n_views, const SrHullView* host_views, const ui
     const long long blocks = (n + kBlock - 1) / kBlock;
     if (blocks > 0)
         hipLaunchKernelGGL(k_hull_carve, dim3((unsigned)blocks), dim3(kBlock), 0, st, it, n_views, c.views, masks, c.words, c.counts);
-    hipLaunchKernelGGL(k_hull_scan, dim3(1), dim3(1024), 0, st, blocks, c.counts, c.total, count_out);
+    hipLaunchKernelGGL(k_hull_scan, dim3(1), dim3(kScanBlock), 0, st, blocks, c.counts, c.total, count_out);
     return hipSuccess;
 }
 

@@ -1,4 +1,5 @@
-"""Visual-hull initialisation on the device: masks and cameras in, trainable splat tensors out.
+"""Initialisation on the device: masks, depth maps and cameras in, trainable splat tensors out.  The visual hull first; the
+back-projection of the depth maps that gives the hull its box, or the initial cloud itself, stands below it (`depth_points`).
 
 Replaces the hull test of reference scene/dataset_readers.py -- :1385-1417 (`visual_hull_samples`), :1419-1458
 (`visual_hull_samples_list`), :605-644 (the Blender `hull` branch of `readNerfSyntheticInfo`) and :544-588 (its `load` branch) --
@@ -211,6 +212,195 @@ def hull_matrices(cameras: Sequence, convention: str = "krt") -> np.ndarray:
         m = getattr(cam, name)
         mats.append(m.detach().cpu().double().numpy() if torch.is_tensor(m) else np.asarray(m, np.float64))
     return np.stack(mats)
+
+
+# ---- depth-map initialisation (csrc/depth_init.hip) --------------------------------------------------------------------------
+# Replaces `_gen_3dpoints` of reference scene/dataset_readers.py:1476-1491 (called per camera and frame at :1376 and :1463) and
+# what `readNeuSceneInfo` takes from the concatenated cloud: its bounds (:1603-1613) or `num_pts` random rows (:1653-1658).
+# For image b and the pixel (x, y), integers: p = Kinv[b,:3,:3] (x, y, 1), v = p / |p|, point = pose[b,:3,3] + depth[b,y,x]
+# pose[b,:3,:3] v, in double, rounded to float32 once.  A pixel is kept iff depth > 0 (and mask > 0 when masks are given); rows
+# follow the pixels in row-major (y, x) order, image after image.
+
+def _host64(a, name, shapes):
+    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if a.ndim != 3 or a.shape[1:] not in shapes:
+        raise ValueError(f"{name} must be " + " or ".join(f"[B, {s[0]}, {s[1]}]" for s in shapes))
+    return a.astype(np.float64)
+
+
+class _DepthBatch:
+    """the arguments every sr_depth_points_* call shares, on the device"""
+
+    def __init__(self, depths, intrinsics_inv, poses, images, masks, dev):
+        d = depths if torch.is_tensor(depths) else torch.from_numpy(np.ascontiguousarray(depths))
+        if d.dim() != 3:
+            raise ValueError("depths must be [B, H, W]")
+        if d.dtype is not torch.float64:
+            d = d.to(torch.float32)
+        self.depths = d.detach().to(dev).contiguous()
+        self.B, self.H, self.W = (int(s) for s in d.shape)
+        if self.H < 1 or self.W < 1:
+            raise ValueError("H and W must be at least 1")
+        if self.B * self.H * self.W > 2 ** 31 - 1:
+            raise ValueError("B H W must not exceed 2^31 - 1: split the batch")
+        kinv = _host64(intrinsics_inv, "intrinsics_inv", ((3, 3), (4, 4)))[:, :3, :3]
+        pose = _host64(poses, "poses", ((3, 4), (4, 4)))[:, :3, :4]
+        if kinv.shape[0] != self.B or pose.shape[0] != self.B:
+            raise ValueError(f"{self.B} depth maps for {kinv.shape[0]} intrinsics and {pose.shape[0]} poses")
+        table = np.concatenate([kinv.reshape(self.B, 9), pose.reshape(self.B, 12)], axis=1)          # SrDepthCamera records
+        self.cameras = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        self.masks = None
+        if masks is not None:
+            m = masks if torch.is_tensor(masks) else torch.from_numpy(np.ascontiguousarray(masks))
+            if m.dim() == 4 and m.shape[-1] == 1:
+                m = m[..., 0]
+            if tuple(m.shape) != (self.B, self.H, self.W):
+                raise ValueError("masks must be [B, H, W] or [B, H, W, 1]")
+            self.masks = (m.to(dev) > 0).to(torch.uint8).contiguous()
+        self.images = None
+        if images is not None:
+            im = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))
+            if tuple(im.shape) != (self.B, self.H, self.W, 3):
+                raise ValueError("images must be [B, H, W, 3]")
+            if im.element_size() not in (1, 4, 8):
+                raise ValueError(f"images of {im.dtype} are not supported: the element size must be 1, 4 or 8 bytes")
+            self.images = im.detach().to(dev).contiguous()
+        self.dev = dev
+
+    @property
+    def n(self):
+        return self.B * self.H * self.W
+
+    def head(self):
+        return (self.B, self.H, self.W, _lib.depth_cameras_arg(self.cameras), ptr(self.depths), int(self.depths.dtype is torch.float64))
+
+    def mark(self, want_count=True, want_bounds=False):
+        """sr_depth_points_mark -> (workspace, device count or None, device bounds or None); nothing waits.  B >= 1: the scan
+        launch writes both words"""
+        lib = _lib.load()
+        ws = torch.empty(lib.sr_depth_points_workspace_bytes(self.n), dtype=torch.uint8, device=self.dev)
+        count = torch.empty(1, dtype=torch.int32, device=self.dev) if want_count else None
+        bounds = torch.empty(2, dtype=torch.float32, device=self.dev) if want_bounds else None
+        _lib.check(lib.sr_depth_points_mark(*self.head(), ptr(self.masks), ptr(ws), ptr(count), ptr(bounds), _lib.stream(self.dev)))
+        return ws, count, bounds
+
+    def _outputs(self, rows, want_indices):
+        xyz = torch.empty(rows, 3, dtype=torch.float32, device=self.dev)
+        colors = None if self.images is None else torch.empty(rows, 3, dtype=self.images.dtype, device=self.dev)
+        idx = torch.empty(rows, dtype=torch.int64, device=self.dev) if want_indices else None
+        return xyz, colors, idx
+
+    def _images_arg(self):
+        return (ptr(self.images), 0 if self.images is None else self.images.element_size())
+
+    def gather(self, ws, rows, want_indices=False):
+        xyz, colors, idx = self._outputs(rows, want_indices)
+        _lib.check(_lib.load().sr_depth_points_gather(*self.head(), *self._images_arg(), ptr(ws), rows, ptr(xyz), ptr(colors), ptr(idx),
+                                                      _lib.stream(self.dev)))
+        return xyz, colors, idx
+
+    def select(self, ws, ranks, want_indices=False):
+        """rows ranks[j] of the cloud and the device flag word (1 when a rank was out of range)"""
+        ranks = ranks.detach().to(self.dev, torch.int64).contiguous()
+        xyz, colors, idx = self._outputs(ranks.numel(), want_indices)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        _lib.check(_lib.load().sr_depth_points_select(*self.head(), *self._images_arg(), ptr(ws), ptr(ranks), ranks.numel(), ptr(xyz),
+                                                      ptr(colors), ptr(idx), ptr(flag), _lib.stream(self.dev)))
+        return xyz, colors, idx, flag
+
+
+def _depth_device(device, *things):
+    dev = _device_of(*things, device=device)
+    if dev.type != "cuda":
+        raise RuntimeError("splatfields_amd.init has no CPU path: the device must be a HIP ('cuda') device")
+    return dev
+
+
+def depth_points(depths, intrinsics_inv, poses, *, images=None, masks=None, n_pts: Optional[int] = None,
+                 generator: Optional[torch.Generator] = None, ranks=None, capacity: Optional[int] = None, return_indices: bool = False,
+                 return_flag: bool = False, device=None):
+    """The back-projected pixels of a batch of depth maps: ``(xyz float32 [M,3], colors [M,3] or None[, indices int64 [M]])`` on the
+    device, in pixel order (image after image, row-major inside an image); ``indices`` are the flat pixel indices b H W + y W + x.
+
+    depths: [B,H,W], float32 or float64 (anything else is converted to float32); intrinsics_inv: [B,3,3] or [B,4,4]; poses
+    (camera to world): [B,3,4] or [B,4,4], both widened to float64 on the host; images: [B,H,W,3] of 1-, 4- or 8-byte elements,
+    copied unchanged; masks: [B,H,W] or [B,H,W,1] of any dtype, ``> 0`` is inside -- the reader's ``depths[~(mask > 0)] = -1``
+    (:1325) without rewriting the depth maps.  Tensors or numpy arrays.
+
+    A full gather needs one host read, of the count.  ``capacity`` bounds the rows written: an ordered prefix when it is short.
+    n_pts: keep ``torch.randperm(M, generator=generator)[:n_pts]`` of the rows (the convention of `visual_hull`), picked by rank
+    on the device without materialising the cloud.  ranks: the caller's own draw instead, an int64 sequence of any order, repeats
+    allowed: row j is survivor number ranks[j], and nothing is read back; a rank outside [0, M) gives a row of NaN coordinates,
+    zero colours and the index -1.  return_flag (with ranks only): the select kernel's report is appended to the result, an int32
+    [1] device tensor that is 1 when any rank was outside [0, M) and 0 otherwise -- still no host read."""
+    dev = _depth_device(device, depths, images, masks)
+    if ranks is not None and (n_pts is not None or capacity is not None):
+        raise ValueError("ranks excludes n_pts and capacity")
+    if return_flag and ranks is None:
+        raise ValueError("return_flag needs ranks: only the caller's own ranks can be out of range")
+    flag = None
+    with torch.cuda.device(dev):
+        b = _DepthBatch(depths, intrinsics_inv, poses, images, masks, dev)
+        if b.B == 0:
+            if ranks is not None and len(ranks):
+                raise ValueError("an empty batch has no row to select")
+            out = b._outputs(0, return_indices)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev) if return_flag else None
+        elif ranks is not None:
+            r = ranks if torch.is_tensor(ranks) else torch.as_tensor(np.asarray(ranks, np.int64))
+            ws, _, _ = b.mark()
+            *out, flag = b.select(ws, r.reshape(-1), return_indices)
+        else:
+            ws, count, _ = b.mark()
+            m = int(count.item())                                  # the one host read
+            rows = m if capacity is None else min(m, int(capacity))
+            if n_pts is not None and rows > n_pts:
+                gen_dev = dev if generator is None else generator.device
+                pick = torch.randperm(rows, generator=generator, device=gen_dev)[:n_pts]
+                out = b.select(ws, pick, return_indices)[:3]
+            else:
+                out = b.gather(ws, rows, return_indices)
+    out = tuple(out) if return_indices else tuple(out[:2])
+    return out + (flag,) if return_flag else out
+
+
+def depth_points_bounds(depths, intrinsics_inv, poses, *, masks=None, as_aabb: bool = False, device=None):
+    """(lo, hi): the smallest and the largest coordinate of `depth_points`' cloud, all three components together -- the reference's
+    ``all_pc[0].min(), all_pc[0].max()`` (:1607) -- as a float32 [2] device tensor, with no host read and no cloud.  (+inf, -inf)
+    when no pixel is valid; a NaN coordinate (possible only where the depth is +inf) takes no part.  as_aabb=True: the pair of
+    Python floats `visual_hull(aabb=...)` takes, with one read."""
+    dev = _depth_device(device, depths, masks)
+    with torch.cuda.device(dev):
+        b = _DepthBatch(depths, intrinsics_inv, poses, None, masks, dev)
+        if b.B == 0:
+            bounds = torch.tensor([float("inf"), float("-inf")], dtype=torch.float32, device=dev)
+        else:
+            bounds = b.mark(want_count=False, want_bounds=True)[2]
+    if as_aabb:
+        lo, hi = bounds.tolist()
+        return lo, hi
+    return bounds
+
+
+def gen_3dpoints(img_idx, H, W, intrinsics_all_inv, pose_all, depths, image):
+    """Drop-in for reference scene/dataset_readers.py:1476-1491: the same arguments (``depths`` [n_images,H,W], ``image`` [H,W,3] of
+    image ``img_idx``), ``(pts float32 [M,3], rgb [M,3])`` as numpy arrays."""
+    d, k, p = depths[img_idx], intrinsics_all_inv[img_idx], pose_all[img_idx]
+    if tuple(d.shape) != (H, W):
+        raise ValueError(f"depths[{img_idx}] is {tuple(d.shape)}, not ({H}, {W})")
+    xyz, rgb = depth_points(d[None], k[None], p[None], images=image[None])
+    return xyz.cpu().numpy(), rgb.cpu().numpy()
+
+
+def depth_point_cloud(depths, intrinsics_inv, poses, images, num_pts: int, *, masks=None, generator: Optional[torch.Generator] = None,
+                      device=None):
+    """The `depth` branch of `readNeuSceneInfo` (reference scene/dataset_readers.py:1653-1658): at most ``num_pts`` rows of the
+    back-projected cloud, a uniform subset without replacement, as ``(xyz float32 [n,3], colors float32 [n,3])`` on the device for
+    `splats_from_points`.  uint8 images are scaled by 1/255, as the reference's round trip through its .ply file does."""
+    if images is None:
+        raise ValueError("depth_point_cloud needs the images: the cloud's colours come from them")
+    xyz, colors = depth_points(depths, intrinsics_inv, poses, images=images, masks=masks, n_pts=int(num_pts), generator=generator, device=device)
+    return xyz, colors.float() / 255.0 if colors.dtype is torch.uint8 else colors.float()
 
 
 def splats_from_points(points, colors=None, sh_degree: int = 3, isotropic: bool = False, generator: Optional[torch.Generator] = None):
