@@ -169,3 +169,26 @@ def load_fixture_case(golden_dir: str, name: str):
         emul[f"grad:{layer}.matrix_t"] = np.outer(coeff, emul[f"grad:{layer}.weight"].reshape(-1))
     e_fmt = {k[len(f"{name}/e_fmt/"):]: float(fx[k]) for k in fx.files if k.startswith(f"{name}/e_fmt/")}
     return kwargs, data, emul, e_fmt, float(fx["rho"])
+
+
+def run_module(name, device, precision="unset", data=None, kwargs=None):
+    """forward + backward of GeneralMLP on a committed case -> {tensor name: float64 CPU tensor}"""
+    import os
+
+    from splatfields_amd.general_mlp import GeneralMLP
+    if data is None:
+        kwargs, data, _, _, _ = load_fixture_case(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"), name)
+    net = GeneralMLP(**kwargs) if precision == "unset" else GeneralMLP(**kwargs, precision=precision)
+    net.load_state_dict({k[len("param:"):]: torch.from_numpy(data[k]) for k in data.files if k.startswith("param:")}, strict=True)
+    net = net.to(device)
+    xyz = torch.from_numpy(data["xyz"]).to(device).requires_grad_()
+    feat = torch.from_numpy(data["feat"]).to(device).requires_grad_() if "feat" in data.files else None
+    frame = int(data["frame_id"])
+    out = net(xyz, feat, frame_id=None if frame < 0 else torch.tensor(frame, device=device))
+    (out * torch.from_numpy(data["probe"]).to(device)).sum().backward()
+    res = {"out": out.detach(), "grad_xyz": xyz.grad}
+    if feat is not None:
+        res["grad_feat"] = feat.grad
+    for k, p in net.named_parameters():
+        res["grad:" + k] = p.grad if p.grad is not None else torch.zeros_like(p)
+    return {k: v.cpu().double() for k, v in res.items()}

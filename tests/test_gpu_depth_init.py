@@ -5,7 +5,6 @@ Which pixels survive, their order, their pixel indices and their colours involve
 restatement's.  The kernel evaluates the restatement's expressions in double, in the same order, without fused multiply-adds, and
 rounds to float32 once, so every coordinate must lie within R.coordinate_bound of the float64 value: half a float32 ulp of it plus
 1e-12 of the largest coordinate (derived there, not measured)."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 import torch
 
 from tests import depth_init_reference as R
+from tests.launches import stage_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -351,19 +351,7 @@ def test_same_call_twice_is_bit_identical():
 
 
 def library_launches(fn):
-    from splatfields_amd import _lib
-    lib = _lib.load()
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_collect(ms, cnt)                                         # drop whatever was recorded before
-    cnt = (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.sr_profile_enable(0)
-    lib.sr_profile_collect(ms, cnt)
-    return sum(cnt)
+    return sum(stage_counts(fn)[1])
 
 
 def test_launch_budget():

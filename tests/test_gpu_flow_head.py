@@ -1,48 +1,24 @@
 """The fused flow head (splatfields_amd/csrc/flow_head.hip, `FlowHead(path="fused")`) on the MI355X against the PyTorch-op path of
 the same module on the CPU, which tests/test_flow_head.py pins to the reference's own classes.
 
-The measure is the project's (tests/test_gpu_plane_attention.py): per tensor, d = max |fused - float64 torch path| over EVERY
-element may be 4 r, r = max |float32 torch path - float64 torch path| on the same inputs, floored at one float32 ulp of the
-tensor's largest magnitude.  Every case prints d / (4 r) (run with -s).  No element is left out; the inputs never hold an
-exactly-zero w_raw (the one stated limit of the SE(3) models, shared with the reference).
+The measure is the suite's rule (tests/accuracy.py), with r from the float32 torch path on the CPU.  No element is left out; the
+inputs never hold an exactly-zero w_raw (the one stated limit of the SE(3) models, shared with the reference).
 
 Shapes: N = 1 (one lane), 63 / 64 / 65 (a wavefront's edge), 255 / 256 / 257 (the workgroup's edge: a workgroup is 256 points),
 1000 (several workgroups); widths 4 (one vector), 36 (not a multiple of the 16 columns a pass moves), 128 (the reference's) and
 256 (the limit); K = 1, 4, 10 bases.  Branch weights scaled by 1e-3, 1 and 8 put theta between ~1e-3 (the cancellation in
 theta - sin theta) and beyond 2 pi (the range reduction of sin / cos)."""
-import numpy as np
 import pytest
 import torch
 
 from splatfields_amd.deform_field import FLOW_MODELS, FlowHead, SplatFields
+from tests.accuracy import within
+from tests.launches import device_records
 
 pytestmark = pytest.mark.gpu
 N_FRAMES, FRAME_ID, TIME_STEP = 6, 3, 0.625
 NS = (1, 63, 64, 65, 255, 256, 257, 1000)
 WIDTHS = (4, 36, 128, 256)
-
-
-def ulp(top):
-    return float(np.spacing(np.float32(top)))
-
-
-def within(tag, got, ref64, ref32):
-    """got / ref64 / ref32: {name: tensor}.  Asserts d <= 4 r for every name of ref64 and returns the worst ratio."""
-    lines, bad = [], []
-    for k, w in ref64.items():
-        g = got[k].detach().double().cpu().reshape(w.shape)
-        assert torch.isfinite(g).all(), (tag, k)
-        top = w.abs().max().item()
-        r = max((ref32[k].double().reshape(w.shape) - w).abs().max().item(), ulp(top))
-        d = (g - w).abs().max().item()
-        lines.append((d / (4 * r), k, d, r))
-        if not d <= 4 * r:
-            bad.append((k, d, 4 * r))
-    worst = max(lines)
-    print(f"[flow_head] {tag}: {len(lines)} tensors, worst d/4r {worst[0]:.3f} ({worst[1]})  " +
-          "  ".join(f"{k} {q:.3f}" for q, k, _, _ in sorted(lines, reverse=True)[:4]))
-    assert not bad, (tag, bad)
-    return worst[0]
 
 
 def make_case(model, n, width, k=4, scale=1.0, seed=0, integers=False):
@@ -92,7 +68,7 @@ def check(tag, head, t, dev, **kw):
     got = run(head, t, torch.float32, dev, "fused", **kw)
     assert set(got) == set(r64)
     assert got["flow"].dtype == torch.float32 and got["flow"].shape == r64["flow"].shape
-    return within(tag, got, r64, r32)
+    return within("flow_head", tag, got, r64, r32)
 
 
 @pytest.mark.parametrize("model", FLOW_MODELS)
@@ -179,15 +155,8 @@ def test_float64_and_autocast_inputs_are_converted_at_the_boundary(hip_device):
 
 
 def library_launches(fn):
-    """Device kernel records of the flow head's kernels and of the weight-gradient kernels it calls while fn runs (host activity
-    on as well: with the device activity alone the trace loses records)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU]
-    return [n for n in names if "k_flow_head" in n or "k_mlp_weight_grad" in n]
+    """device records of the flow head's kernels and of the weight-gradient kernels it calls while fn runs"""
+    return [n for n in device_records(fn) if "k_flow_head" in n or "k_mlp_weight_grad" in n]
 
 
 @pytest.mark.parametrize("model", FLOW_MODELS)
@@ -296,5 +265,5 @@ def test_whole_network(hip_device, monkeypatch, model):
     r32 = step(nets["torch"], torch.float32, dev)
     got = step(nets["fused"], torch.float32, dev)
     r64 = {k: v.double().cpu() for k, v in r64.items()}
-    within(f"network {model}, r from the CPU", got, r64, r32_cpu)
-    within(f"network {model}, r from the device", got, r64, {k: v.cpu() for k, v in r32.items()})
+    within("flow_head", f"network {model}, r from the CPU", got, r64, r32_cpu)
+    within("flow_head", f"network {model}, r from the device", got, r64, {k: v.cpu() for k, v in r32.items()})

@@ -2,54 +2,20 @@
 sr_mlp_group_*): the group chain kernels bit for bit against the single-net kernels on the same op tables, the small kernels
 against float64 formulas, the module against the float64 CPU formula path, the reference fixtures, determinism, the default
 path untouched, and the launch budgets of the design."""
-import functools
-import math
-
 import pytest
 import torch
 
 import heads_reference as hr
+from tests.heads_cases import (MODULE_CONFIGS, bound, build_net, chain_groups, cpu_references, default_specs, library, make_net,
+                               module_inputs)
+from tests.launches import device_records
 
 pytestmark = pytest.mark.gpu
 POINT_COUNTS = (1, 31, 32, 33, 127, 128, 129, 1000)      # the edges of a wavefront's 32 points and of a workgroup's 128
 NEW_KERNELS = ("k_mlp_chain_group", "k_mlp_group_")
 
 
-def ulp32(x: float) -> float:
-    """one unit in the last place of float32 at magnitude x"""
-    return 2.0 ** (math.frexp(max(x, 1e-30))[1] - 24)
-
-
-def bound(ref64, *approximations):
-    """4 x the largest error of the given approximations of ref64, floored at one float32 ulp of the tensor's maximum"""
-    r = max([(a.detach().double().cpu() - ref64).abs().max().item() for a in approximations] + [ulp32(ref64.abs().max().item())])
-    return 4.0 * r
-
-
-def default_specs(dynamic=True):
-    from splatfields_amd.deform_field import SplatFields
-    torch.manual_seed(11)
-    net = SplatFields(n_frames=5 if dynamic else 0, heads="grouped", encoder=hr.LinearEncoder())
-    return net._head_group.specs, net.time_multires
-
-
 # ---- kernel against kernel ----------------------------------------------------------------------------------------------------
-
-def chain_groups():
-    from splatfields_amd import fused_mlp as fm
-    specs, _ = default_specs()
-    s64, s128 = [s.shape for s in specs[:3]], [s.shape for s in specs[3:]]
-    small = fm._Shape([torch.zeros(64, 21), torch.zeros(64, 64), torch.zeros(5, 64)], 21, [])      # 3 ops forward, 3 backward
-    return {"three_64": s64, "two_128": s128, "one_net": [s64[2]], "net_limit": [small] * 8}
-
-
-def make_net(shape, n, gen, dev):
-    ws = [(torch.randn(r, c, generator=gen) / c ** 0.5).to(dev) for r, c in shape.layer_dims]
-    bs = [(0.1 * torch.randn(r, generator=gen)).to(dev) for r, _ in shape.layer_dims]
-    x0 = torch.zeros(n, shape.mem_pad)
-    x0[:, :shape.d_in] = torch.randn(n, shape.d_in, generator=gen)
-    return ws, bs, x0.to(dev), torch.randn(n, shape.out_features, generator=gen).to(dev)
-
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("group", ["three_64", "two_128", "one_net", "net_limit"])
@@ -216,52 +182,6 @@ def test_output_and_top_gradient_kernels_match_the_float64_formulas(hip_device, 
 
 # ---- the module against the float64 CPU formula path --------------------------------------------------------------------------------
 
-MODULE_CONFIGS = {
-    "static": dict(n_frames=0, kwargs=dict()),
-    "dynamic_se3": dict(n_frames=6, kwargs=dict(composition_rank=4, flow_model="se3")),
-    "viewdep": dict(n_frames=0, kwargs=dict(use_view_dep_rgb=True)),
-}
-
-
-def build_net(name, with_encoder, **extra):
-    from splatfields_amd.deform_field import SplatFields
-    cfg = MODULE_CONFIGS[name]
-    torch.manual_seed(21)
-    enc = dict(encoder=hr.LinearEncoder()) if with_encoder else dict(encoder_type="none")
-    return SplatFields(n_frames=cfg["n_frames"], **enc, **cfg["kwargs"], **extra)
-
-
-def module_inputs(n):
-    gen = torch.Generator().manual_seed(40 + n)
-    xyz = 0.6 * torch.randn(n, 3, generator=gen)
-    t = torch.full((n, 1), 0.4)
-    viewdir = torch.nn.functional.normalize(torch.randn(n, 3, generator=gen), dim=-1)
-    return xyz, t, viewdir, gen
-
-
-@functools.lru_cache(maxsize=None)
-def cpu_references(name, with_encoder, n):
-    """(state dict, probes, float64 outputs and gradients, float32 outputs and gradients) of the CPU formula path: computed once,
-    shared by the precisions"""
-    from splatfields_amd import general_mlp
-    from test_general_mlp import formula
-    xyz, t, viewdir, gen = module_inputs(n)
-    net = build_net(name, with_encoder)
-    state = {k: v.clone() for k, v in net.state_dict().items()}
-    real = general_mlp.fused_general_mlp
-    general_mlp.fused_general_mlp = formula
-    try:
-        first, _ = hr.step(net, xyz, t, viewdir, {k: torch.ones(1) for k in ("scales", "opacity", "rotations", "rgb", "flow", "means3D")})
-        probes = {k: torch.randn(v.shape, generator=gen) for k, v in first.items()}
-        f32 = hr.step(net, xyz, t, viewdir, probes)
-        net64 = build_net(name, with_encoder).double()
-        net64.load_state_dict({k: v.double() for k, v in state.items()})
-        f64 = hr.step(net64, xyz.double(), t.double(), viewdir.double(), probes)
-    finally:
-        general_mlp.fused_general_mlp = real
-    return state, probes, f64, f32
-
-
 WORST = {}
 
 
@@ -312,21 +232,6 @@ def test_reference_fixtures_pass_grouped(hip_device, name, monkeypatch):
     assert calls == [1]
 
 
-def device_kernels(fn):
-    """names of the device activity records while fn runs (host activity on as well: with the device activity alone the trace
-    loses records)"""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU]
-
-
-def library(names):
-    return [n for n in names if "k_mlp_" in n or "k_resfield_" in n]
-
-
 def test_two_grouped_steps_are_bit_identical(hip_device):
     dev = hip_device
     xyz, t, viewdir, gen = module_inputs(1000)
@@ -357,7 +262,7 @@ def test_the_default_path_is_untouched(hip_device):
     first, _ = hr.step(default, xyz.to(dev), t.to(dev), viewdir.to(dev), {k: torch.ones(1) for k in ("scales", "opacity", "rotations", "rgb", "flow", "means3D")})
     probes = {k: torch.randn(v.shape, generator=gen) for k, v in first.items()}
     held = {}
-    names = device_kernels(lambda: held.update(a=hr.step(default, xyz.to(dev), t.to(dev), viewdir.to(dev), probes)))
+    names = device_records(lambda: held.update(a=hr.step(default, xyz.to(dev), t.to(dev), viewdir.to(dev), probes)))
     b = hr.step(named, xyz.to(dev), t.to(dev), viewdir.to(dev), probes)
     for x, y in zip(held["a"], b):
         for k in x:
@@ -366,7 +271,7 @@ def test_the_default_path_is_untouched(hip_device):
     assert not [n for n in names if any(new in n for new in NEW_KERNELS)]
     grouped = build_net("dynamic_se3", True, heads="grouped").to(dev)
     grouped.load_state_dict(default.state_dict())
-    names = device_kernels(lambda: hr.step(grouped, xyz.to(dev), t.to(dev), viewdir.to(dev), probes))
+    names = device_records(lambda: hr.step(grouped, xyz.to(dev), t.to(dev), viewdir.to(dev), probes))
     assert [n for n in names if "k_mlp_chain_group" in n] and [n for n in names if "k_mlp_group_" in n]
 
 
@@ -397,10 +302,10 @@ def test_launch_budgets(hip_device, config, precision):
         held["out"] = net._head_group(xyz_can, feat, frame_id=frame, time=t.reshape(-1) if config == "dynamic" else None)
 
     forward()                                             # plans, tables and the allocator are warm
-    fwd = library(device_kernels(forward))
+    fwd = library(device_records(forward))
     probes = {k: torch.randn(v.shape, generator=gen).to(dev) for k, v in held["out"].items()}
     loss = sum((held["out"][k] * probes[k]).sum() for k in sorted(probes))
-    bwd = library(device_kernels(loss.backward))
+    bwd = library(device_records(loss.backward))
     print(f"{config} {precision}: {len(fwd)} library launches forward, {len(bwd)} backward")
     assert fwd and bwd, "the profiler recorded none of the library's kernels"
     assert len(fwd) <= budget[0], fwd
@@ -417,7 +322,7 @@ def test_launch_budgets(hip_device, config, precision):
             total.backward()
 
         step()
-        names = device_kernels(step)
+        names = device_records(step)
         assert library(names), "the profiler recorded none of the library's kernels"
         totals[mode] = len(names)
     print(f"{config} {precision}: {totals['grouped']} device kernels per step grouped, {totals['separate']} separate")

@@ -36,12 +36,12 @@ that no threshold decision of these scenes is close, so nothing here is exempt a
 """
 import math
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import c_oracle
 from tests import boundary_scenes as B
+from tests.accuracy import ulp32
 from tests.helpers import record_observed, run_hip
 from tests.test_gpu_lists import check_tile_lists, hip_tile_lists
 
@@ -96,10 +96,6 @@ def references(sc, with_depth, with_alpha):
     return _refs[key]
 
 
-def ulp32(x: float) -> float:
-    return float(np.spacing(np.float32(x))) if x > 0 else 0.0
-
-
 worst_rel = [0.0]   # largest gradient deviation from the C oracle in float seen so far, relative to its tensor's maximum
 
 
@@ -122,7 +118,8 @@ def check_parity(sc, out, g, with_depth, with_alpha, tag, problems):
             if idx.numel() == 0:
                 continue
             d = d_all[idx].max().item()
-            r = max(r_all[idx].max().item(), ulp32(ref64[idx].abs().max().item()))
+            top = ref64[idx].abs().max().item()
+            r = max(r_all[idx].max().item(), ulp32(top) if top > 0 else 0.0)       # an all-zero reference gets no floor
             ratio = d / (4 * r) if r > 0 else (0.0 if d == 0 else math.inf)
             worst = max(worst, ratio)
             e32 = (g[k].double() - g32[k].double()).abs()[idx].max().item() / max(g32[k].abs().max().item(), 1e-30)

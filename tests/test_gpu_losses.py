@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import loss_reference as R
+from tests.accuracy import assert_deviations
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +36,7 @@ def hip_evaluate(dev, image, gt, opacity=None, gt_mask=None, lambda_dssim=0.2, l
 
 
 def assert_within(tag, got, want, r):
-    d = R.deviations(got, want)
-    print(f"[loss] {tag}: deviation {d}  allowed 4 x {r}")
-    for k in R.METRICS:
-        assert d[k] <= 4.0 * r[k], (tag, k, d[k], 4.0 * r[k])
+    assert_deviations("loss", tag, R.deviations(got, want), r, R.METRICS)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import metric_reference as R
+from tests.accuracy import assert_deviations, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -30,14 +31,7 @@ def hip_metrics(dev, pred, gt, mask=None, **kw):
 
 
 def assert_within(tag, got, want, r):
-    d = R.deviations(got, want)
-    print(f"[metrics] {tag}: deviation {d}  allowed 4 x {r}")
-    for k in R.METRICS:
-        assert d[k] <= 4.0 * r[k], (tag, k, d[k], 4.0 * r[k])
-
-
-def same_bits(a: dict, b: dict):
-    return a.keys() == b.keys() and all(torch.equal(a[k], b[k]) for k in a)
+    assert_deviations("metrics", tag, R.deviations(got, want), r, R.METRICS)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

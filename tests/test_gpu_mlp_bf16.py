@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import mlp_bf16_reference as R
+from mlp_bf16_reference import run_module
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -75,27 +76,6 @@ def test_exact_arithmetic_chains_are_bit_identical(hip_device, exact_references,
     assert torch.equal(x.grad.cpu().double(), want["d_in"])
     for got, ref in zip([w.grad for w in ws] + [b.grad for b in bs], want["dW"] + want["db"]):
         assert (got.cpu().double() - ref).abs().max().item() <= 2e-4 * ref.abs().max().item()
-
-
-def run_module(name, device, precision="unset", data=None, kwargs=None):
-    """forward + backward of GeneralMLP on a committed case -> {tensor name: float64 CPU tensor}"""
-    from splatfields_amd.general_mlp import GeneralMLP
-    if data is None:
-        kwargs, data, _, _, _ = R.load_fixture_case(GOLDEN, name)
-    net = GeneralMLP(**kwargs) if precision == "unset" else GeneralMLP(**kwargs, precision=precision)
-    net.load_state_dict({k[len("param:"):]: torch.from_numpy(data[k]) for k in data.files if k.startswith("param:")}, strict=True)
-    net = net.to(device)
-    xyz = torch.from_numpy(data["xyz"]).to(device).requires_grad_()
-    feat = torch.from_numpy(data["feat"]).to(device).requires_grad_() if "feat" in data.files else None
-    frame = int(data["frame_id"])
-    out = net(xyz, feat, frame_id=None if frame < 0 else torch.tensor(frame, device=device))
-    (out * torch.from_numpy(data["probe"]).to(device)).sum().backward()
-    res = {"out": out.detach(), "grad_xyz": xyz.grad}
-    if feat is not None:
-        res["grad_feat"] = feat.grad
-    for k, p in net.named_parameters():
-        res["grad:" + k] = p.grad if p.grad is not None else torch.zeros_like(p)
-    return {k: v.cpu().double() for k, v in res.items()}
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import mlp_bf16x3_reference as R
+from mlp_bf16_reference import run_module
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -85,27 +86,6 @@ def test_exact_arithmetic_chains_are_bit_identical(hip_device, exact_references,
     assert torch.equal(x.grad.cpu().double(), want["d_in"])
     for got, ref in zip([w.grad for w in ws] + [b.grad for b in bs], want["dW"] + want["db"]):
         assert (got.cpu().double() - ref).abs().max().item() <= 2e-4 * ref.abs().max().item()
-
-
-def run_module(name, device, precision="unset", data=None, kwargs=None):
-    """forward + backward of GeneralMLP on a committed case -> {tensor name: float64 CPU tensor}"""
-    from splatfields_amd.general_mlp import GeneralMLP
-    if data is None:
-        kwargs, data, _, _, _ = R.load_fixture_case(GOLDEN, name)
-    net = GeneralMLP(**kwargs) if precision == "unset" else GeneralMLP(**kwargs, precision=precision)
-    net.load_state_dict({k[len("param:"):]: torch.from_numpy(data[k]) for k in data.files if k.startswith("param:")}, strict=True)
-    net = net.to(device)
-    xyz = torch.from_numpy(data["xyz"]).to(device).requires_grad_()
-    feat = torch.from_numpy(data["feat"]).to(device).requires_grad_() if "feat" in data.files else None
-    frame = int(data["frame_id"])
-    out = net(xyz, feat, frame_id=None if frame < 0 else torch.tensor(frame, device=device))
-    (out * torch.from_numpy(data["probe"]).to(device)).sum().backward()
-    res = {"out": out.detach(), "grad_xyz": xyz.grad}
-    if feat is not None:
-        res["grad_feat"] = feat.grad
-    for k, p in net.named_parameters():
-        res["grad:" + k] = p.grad if p.grad is not None else torch.zeros_like(p)
-    return {k: v.cpu().double() for k, v in res.items()}
 
 
 _RUNS: dict = {}
@@ -249,7 +229,7 @@ def test_group_chain_is_bit_identical_to_separate_chains(hip_device, group):
     every stored value (y, saved activations, sign words, dz, the accumulated dL/dx0), bit for bit -- the guarantee of DESIGN.md
     section 20 for the other precisions (tests/test_gpu_heads.py, whose set-up this is)"""
     from splatfields_amd import _lib, fused_mlp as fm
-    from test_gpu_heads import chain_groups, make_net
+    from tests.heads_cases import chain_groups, make_net
     dev, lib, slope = hip_device, _lib.load(), 0.01
     shapes = chain_groups()[group]
     for n in (1, 77, 131, 300):
@@ -303,7 +283,8 @@ def test_grouped_module_runs_the_group_entry_within_the_separate_path(hip_device
     top-gradient kernels compute in double where the separate path's compute in float32, in every precision.)  Two grouped steps are
     bit-identical."""
     import heads_reference as hr
-    from test_gpu_heads import bound, build_net, cpu_references, device_kernels, module_inputs
+    from tests.heads_cases import bound, build_net, cpu_references, module_inputs
+    from tests.launches import device_records
     dev, n = hip_device, 300
     state, probes, (out64, grad64), (out32, grad32) = cpu_references(name, True, n)
     xyz, t, viewdir, _ = module_inputs(n)
@@ -314,7 +295,7 @@ def test_grouped_module_runs_the_group_entry_within_the_separate_path(hip_device
     out_sep, grad_sep = hr.step(net, *args)
     net.heads = "grouped"
     held = {}
-    names = device_kernels(lambda: held.update(r=hr.step(net, *args)))
+    names = device_records(lambda: held.update(r=hr.step(net, *args)))
     out_grp, grad_grp = held["r"]
     chains = [k for k in names if "k_mlp_chain" in k]
     assert [k for k in chains if "k_mlp_chain_group_bf16x3" in k], chains
@@ -342,7 +323,8 @@ def test_launch_counts_of_the_grouped_heads_are_unchanged(hip_device, config):
     (four heads, rank 0) 6 and 14 -- with the bf16x3 packer and group kernels in the places of their siblings"""
     import heads_reference as hr
     from splatfields_amd.deform_field import SplatFields
-    from test_gpu_heads import device_kernels, library
+    from tests.heads_cases import library
+    from tests.launches import device_records
     dev, n = hip_device, 300
     torch.manual_seed(5)
     if config == "dynamic":
@@ -362,10 +344,10 @@ def test_launch_counts_of_the_grouped_heads_are_unchanged(hip_device, config):
         held["out"] = net._head_group(xyz_can, feat, frame_id=frame, time=t.reshape(-1) if config == "dynamic" else None)
 
     forward()                                             # plans, tables and the allocator are warm
-    fwd = library(device_kernels(forward))
+    fwd = library(device_records(forward))
     probes = {k: torch.randn(v.shape, generator=gen).to(dev) for k, v in held["out"].items()}
     loss = sum((held["out"][k] * probes[k]).sum() for k in sorted(probes))
-    bwd = library(device_kernels(loss.backward))
+    bwd = library(device_records(loss.backward))
     print(f"{config} bf16x3: {len(fwd)} library launches forward, {len(bwd)} backward")
     assert (len(fwd), len(bwd)) == counts, (fwd, bwd)
     for part in (fwd, bwd):

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import moran_reference as R
+from tests.accuracy import assert_deviations
 
 pytestmark = pytest.mark.gpu
 
@@ -34,10 +35,7 @@ def hip_evaluate(dev, points, features, k=5, eps=1e-5, graph=None, scale=None, w
 
 
 def assert_within(tag, got, want, r):
-    d = R.deviations(got, want)
-    print(f"[moran] {tag}: " + "  ".join(f"{k} {d[k]:.3e}/{4.0 * r[k]:.3e} = {d[k] / (4.0 * r[k]):.2f}" for k in R.METRICS))
-    for k in R.METRICS:
-        assert d[k] <= 4.0 * r[k], (tag, k, d[k], 4.0 * r[k])
+    assert_deviations("moran", tag, R.deviations(got, want), r, R.METRICS)
 
 
 def assert_same_neighbours(tag, nn_ix, points, k, swap_rel=1e-5, max_share=1e-4, ties_by_index=False):

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 import test_gpu_adam as A
+from tests.launches import device_records
 
 pytestmark = pytest.mark.gpu
 
@@ -312,20 +313,6 @@ def test_the_state_goes_to_torch_adam(hip_device):
 
 # --------------------------------------------------------------------------------------------------------------- launch budget
 
-def device_records(fn):
-    """the name of every device record (kernel, copy, fill) while fn runs (host activity on as well: with the device activity
-    alone the trace loses records)"""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    host = {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CPU}
-    # a record_function range of the host (torch wraps Optimizer.step in one) is mirrored on the device's time line under its
-    # own name: that is no device work.  Kernels, copies and fills have no host record of their name.
-    return [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and e.name not in host]
-
-
 def check_budget(params, dev, tag):
     from splatfields_amd import _lib
     gen = torch.Generator().manual_seed(12)
@@ -334,7 +321,7 @@ def check_budget(params, dev, tag):
         p.grad = A.gradients(tuple(p.shape) or (1,), "uniform", gen).reshape(p.shape).to(dev)
     opt.step()                                                          # plans, creates the state
     opt.step()
-    names = device_records(opt.step)
+    names = device_records(opt.step, drop_host_ranges=True)
     want = math.ceil(len(params) / _lib.NET_ADAM_MAX_GRADS)
     print(f"[network adam] {tag}: {len(params)} tensors, device records of a step: {names}")
     assert len(names) > 0, "the profiler recorded nothing: the budget was not checked"

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import objective_reference as R
+from tests.launches import device_records
 
 pytestmark = pytest.mark.gpu
 
@@ -383,15 +384,8 @@ def test_no_host_wait_from_the_python_side(hip_device):
 
 
 def library_launches(fn):
-    """Device kernel records of this library's objective kernels while fn runs (host activity on as well: with the device activity
-    alone the trace loses records)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU]
-    return [n for n in names if "k_splat_reg" in n or "k_depth_l1" in n]
+    """device records of this library's objective kernels while fn runs"""
+    return [n for n in device_records(fn) if "k_splat_reg" in n or "k_depth_l1" in n]
 
 
 def test_launch_counts_are_within_the_budgets(hip_device):

@@ -1,10 +1,9 @@
 """The plane generator's attention layer on its HIP kernels (splatfields_amd/csrc/attention.hip, `fused_attention`,
 `attention="fused"`) on the MI355X against the plain-PyTorch restatement tests/plane_decoder_reference.py in float64.
 
-The measure is the one of tests/test_gpu_plane_generator.py, restated here: per tensor, d = max |ours - float64 restatement| over
-EVERY element may be 4 r, r = max |float32 restatement - float64 restatement| on the same inputs, floored at one float32 ulp of
-the tensor's largest magnitude.  The kernels compute in double and round once, so what the allowance has to absorb is their
-order of summation; a ratio d / 4r above about 0.3 points at a float32 intermediate.  Every case prints d / (4 r) (run with -s).
+The measure is the suite's rule (tests/accuracy.py), with r from the float32 restatement.  The kernels compute in double and round
+once, so what the allowance has to absorb is their order of summation; a ratio d / 4r above about 0.3 points at a float32
+intermediate.
 
 Two tensors are outside that rule, for reasons of the mathematics and not of the kernels:
   * the gradient of `to_k.bias` is analytically zero (a key bias shifts a whole score row, which the softmax does not see); its
@@ -12,54 +11,24 @@ Two tensors are outside that rule, for reasons of the mathematics and not of the
   * with a single token (T = 1) the softmax is the constant 1 and the gradients of `to_q.weight`, `to_q.bias` and `to_k.weight` are
     identically zero in both restatements, so the ulp floor of the rule is zero as well.  Ours are checked to be finite and at
     most one float32 ulp of the largest magnitude among the case's other parameter gradients."""
+import functools
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
+from tests import accuracy
 from tests import plane_decoder_reference as R
+from tests.accuracy import ulp32
+from tests.launches import stage_counts
+from tests.plane_cases import GOLDEN, SMALL, load, params_of, run_module
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SMALL = dict(in_channels=8, out_channels=16, up_block_types=("TimeUpDecoderBlock2D",) * 4, block_out_channels=(16,) * 4, norm_num_groups=4,
-             layers_per_block=1)
+within = functools.partial(accuracy.within, "plane_attention")
 NAMES = ("group_norm.weight", "group_norm.bias", "to_q.weight", "to_q.bias", "to_k.weight", "to_k.bias", "to_v.weight", "to_v.bias",
          "to_out.0.weight", "to_out.0.bias")
 QK_SIDE = ("to_q.weight", "to_q.bias", "to_k.weight")
-
-
-def ulp(top):
-    return float(np.spacing(np.float32(top)))
-
-
-def within(tag, got, ref64, ref32):
-    """got / ref64 / ref32: {name: tensor}.  Asserts d <= 4 r for every name of ref64 and returns the worst ratio."""
-    lines, bad = [], []
-    for k, w in ref64.items():
-        g = got[k].detach().double().cpu().reshape(w.shape)
-        assert torch.isfinite(g).all(), (tag, k)
-        top = w.abs().max().item()
-        r = max((ref32[k].double().reshape(w.shape) - w).abs().max().item(), ulp(top))
-        d = (g - w).abs().max().item()
-        lines.append((d / (4 * r), k, d, r))
-        if not d <= 4 * r:
-            bad.append((k, d, 4 * r))
-    worst = max(lines)
-    print(f"[plane_attention] {tag}: {len(lines)} tensors, worst d/4r {worst[0]:.3f} ({worst[1]})  " +
-          "  ".join(f"{k} {q:.3f}" for q, k, _, _ in sorted(lines, reverse=True)[:6]))
-    assert not bad, (tag, bad)
-    return worst[0]
-
-
-def load(name):
-    z = np.load(os.path.join(GOLDEN, f"plane_decoder_{name}.npz"))
-    return {k: torch.as_tensor(z[k].astype(np.float32) if z[k].dtype == np.float16 else z[k]) for k in z.files}
-
-
-def params_of(z):
-    return {k[len("param/"):]: v for k, v in z.items() if k.startswith("param/")}
 
 
 # ---- the layer alone --------------------------------------------------------------------------------------------------------
@@ -115,7 +84,7 @@ def check_layer(tag, ts, groups, dev):
             for k in QK_SIDE:
                 assert r64["d_" + k].abs().max().item() == 0.0, (tag, k, "identically zero in the reference")
                 g = got["d_" + k].double().cpu()
-                assert torch.isfinite(g).all() and g.abs().max().item() <= ulp(top), (tag, i, k, g.abs().max().item(), ulp(top))
+                assert torch.isfinite(g).all() and g.abs().max().item() <= ulp32(top), (tag, i, k, g.abs().max().item(), ulp32(top))
     return worst
 
 
@@ -174,13 +143,6 @@ def test_bad_shapes_raise_before_any_launch(hip_device):
 
 
 # ---- the fixtures through the module ------------------------------------------------------------------------------------------
-def run_module(net, noise, probe, frame_id=None):
-    net.zero_grad()
-    out = net(noise, frame_id=frame_id)
-    (out * probe).sum().backward()
-    return out.detach(), {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}
-
-
 def test_small_fixture_through_the_module(hip_device):
     from splatfields_amd.plane_generator import TimeVAEDecoder
     z = load("small")
@@ -280,23 +242,6 @@ def test_reference_size_three_planes_and_repeats(hip_device):
 
 
 # ---- launch budget ----------------------------------------------------------------------------------------------------------
-def library_launches(fn):
-    import ctypes as C
-    from splatfields_amd import _lib
-    lib = _lib.load()
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_collect(ms, cnt)                                         # drop whatever was recorded before
-    cnt = (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.sr_profile_enable(0)
-    lib.sr_profile_collect(ms, cnt)
-    return list(cnt)
-
-
 def test_launch_budget_of_both_paths(hip_device):
     from splatfields_amd.plane_generator import ATTENTION_LAUNCHES, Tensorial2D, generate_planes
     subs = [Tensorial2D(8, 16, 4).to(hip_device) for _ in range(3)]
@@ -309,11 +254,11 @@ def test_launch_budget_of_both_paths(hip_device):
 
     fwd, bwd = ATTENTION_LAUNCHES
     assert fwd <= 4 and bwd <= 8
-    one, three = library_launches(step(1, "fused")), library_launches(step(3, "fused"))
+    one, three = stage_counts(step(1, "fused"))[1], stage_counts(step(3, "fused"))[1]
     print(f"[plane_attention] library launches per step, fused: one plane {one}, three planes {three} (stage 0 forward, stage 6 backward)")
     assert one == three
     assert one[0] == 67 + fwd and one[6] == 116 + bwd and sum(one) == 183 + fwd + bwd
-    one, three = library_launches(step(1, "torch")), library_launches(step(3, "torch"))
+    one, three = stage_counts(step(1, "torch"))[1], stage_counts(step(3, "torch"))[1]
     assert one == three and one[0] == 67 and one[6] == 116 and sum(one) == 183
 
 

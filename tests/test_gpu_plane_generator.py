@@ -1,56 +1,23 @@
 """The plane generator (splatfields_amd/plane_generator.py, csrc/planegen.hip) on the MI355X against the plain-PyTorch restatement
 tests/plane_decoder_reference.py, which tests/test_plane_decoder_reference.py pins to runs of the reference's own classes.
 
-The measure, per tensor: d = max |ours - float64 restatement| over EVERY element may be 4 r, r = max |float32 restatement -
-float64 restatement| on the same inputs, floored at one float32 ulp of the tensor's largest magnitude: the kernels are another
-float32 evaluation of the same formulas.  For the fixtures the float32 evaluation is the reference's own run (the fixture).
-Every case prints d / (4 r) per tensor (run with -s)."""
+The measure is the suite's rule (tests/accuracy.py), with r from the float32 restatement; for the fixtures the float32 evaluation
+is the reference's own run (the fixture)."""
+import functools
 import itertools
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
+from tests import accuracy
 from tests import plane_decoder_reference as R
+from tests.launches import stage_counts
+from tests.plane_cases import GOLDEN, SMALL, load, params_of, run_module
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SMALL = dict(in_channels=8, out_channels=16, up_block_types=("TimeUpDecoderBlock2D",) * 4, block_out_channels=(16,) * 4, norm_num_groups=4,
-             layers_per_block=1)
-
-
-def ulp(top):
-    return float(np.spacing(np.float32(top)))
-
-
-def within(tag, got, ref64, ref32):
-    """got / ref64 / ref32: {name: tensor}.  Asserts d <= 4 r for every name of ref64 and returns the worst ratio."""
-    lines, bad = [], []
-    for k, w in ref64.items():
-        g = got[k].detach().double().cpu().reshape(w.shape)
-        assert torch.isfinite(g).all(), (tag, k)
-        top = w.abs().max().item()
-        r = max((ref32[k].double().reshape(w.shape) - w).abs().max().item(), ulp(top))
-        d = (g - w).abs().max().item()
-        lines.append((d / (4 * r), k, d, r))
-        if not d <= 4 * r:
-            bad.append((k, d, 4 * r))
-    worst = max(lines)
-    print(f"[plane_generator] {tag}: {len(lines)} tensors, worst d/4r {worst[0]:.3f} ({worst[1]})  " +
-          "  ".join(f"{k} {q:.3f}" for q, k, _, _ in sorted(lines, reverse=True)[:6]))
-    assert not bad, (tag, bad)
-    return worst[0]
-
-
-def load(name):
-    z = np.load(os.path.join(GOLDEN, f"plane_decoder_{name}.npz"))
-    return {k: torch.as_tensor(z[k].astype(np.float32) if z[k].dtype == np.float16 else z[k]) for k in z.files}
-
-
-def params_of(z):
-    return {k[len("param/"):]: v for k, v in z.items() if k.startswith("param/")}
+within = functools.partial(accuracy.within, "plane_generator")
 
 
 # ---- single fused layer ------------------------------------------------------------------------------------------------------
@@ -121,13 +88,6 @@ def test_bad_shapes_raise_value_error_before_any_launch(hip_device):
 
 
 # ---- the fixtures through the module ------------------------------------------------------------------------------------------
-def run_module(net, noise, probe, frame_id=None):
-    net.zero_grad()
-    out = net(noise, frame_id=frame_id)
-    (out * probe).sum().backward()
-    return out.detach(), {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}
-
-
 def test_small_fixture_through_the_module(hip_device):
     from splatfields_amd.plane_generator import TimeVAEDecoder
     z = load("small")
@@ -227,23 +187,6 @@ def test_reference_size_three_planes_and_repeats(hip_device):
 
 
 # ---- launch budget ----------------------------------------------------------------------------------------------------------
-def library_launches(fn):
-    import ctypes as C
-    from splatfields_amd import _lib
-    lib = _lib.load()
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_collect(ms, cnt)                                         # drop whatever was recorded before
-    cnt = (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.sr_profile_enable(0)
-    lib.sr_profile_collect(ms, cnt)
-    return list(cnt)
-
-
 def test_three_planes_cost_the_launches_of_one(hip_device):
     from splatfields_amd.plane_generator import Tensorial2D, generate_planes
     subs = [Tensorial2D(8, 16, 4).to(hip_device) for _ in range(3)]
@@ -254,7 +197,7 @@ def test_three_planes_cost_the_launches_of_one(hip_device):
             out.sum().backward()
         return fn
 
-    one, three = library_launches(step(1)), library_launches(step(3))
+    one, three = stage_counts(step(1))[1], stage_counts(step(3))[1]
     print(f"[plane_generator] library launches per step: one plane {one}, three planes {three} (stage 0 forward, stage 6 backward)")
     assert one == three
     # conv_in 1, ten resnet blocks x (2 statistics x 2 + 2 convolutions), three upsamplers, conv_out 2 + 1;

@@ -12,12 +12,9 @@ Which case launches which kernel (K coefficients per splat, active degree deg):
 The LDS staging (stage_sh_in / stage_sh_out) meets a partial only workgroup at N = 1 and 255, a whole one at 256, a whole one
 and a partial second at 257, and two whole ones and a partial third at 700.
 
-The measure is the suite's (test_gpu_plane_generator.within): per tensor d = max |ours - float64 restatement| over EVERY
-element may be 4 r, r = max |float32 restatement - float64 restatement| on the same inputs, floored at one float32 ulp of the
-tensor's largest magnitude -- the kernel is one more float32 evaluation of the same formula in another operation order.  For
-the fixture cases r is the reference's own float32 run (tests/golden/sh_cases.npz).  Clamp decisions are exact: the inputs
-are built so that no float64 pre-clamp channel lies within 1e-4 of zero (asserted), and then the clamp byte and `keep` equal
-the restatement's bit for bit.  Every case prints d / (4 r) per tensor (run with -s).
+The measure is the suite's rule (tests/accuracy.py), with r from the float32 restatement; for the fixture cases r is the
+reference's own float32 run (tests/golden/sh_cases.npz).  Clamp decisions are exact: the inputs are built so that no float64
+pre-clamp channel lies within 1e-4 of zero (asserted), and then the clamp byte and `keep` equal the restatement's bit for bit.
 
 Worst d / (4 r) seen on the MI355X over every case of this module, per entry point and tensor:
     sr_sh_forward        colours 0.51 (K16-deg3-N257, fifth camera)
@@ -30,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import accuracy
 from tests import sh_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -47,27 +45,12 @@ def kd_ids(pairs):
     return [f"K{k}-deg{deg}" for k, deg in pairs]
 
 
-def ulp(top):
-    return float(np.spacing(np.float32(top)))
-
-
-def within(entry, tag, got, ref64, ref32):
-    """got / ref64 / ref32: {name: tensor}.  Asserts d <= 4 r for every name of ref64; keeps the worst ratio per entry point."""
-    lines, bad = [], []
-    for k, w in ref64.items():
-        g = got[k].detach().double().cpu().reshape(w.shape)
-        assert torch.isfinite(g).all(), (tag, k)
-        top = w.abs().max().item() if w.numel() else 0.0
-        r = max((ref32[k].double().reshape(w.shape) - w).abs().max().item() if w.numel() else 0.0, ulp(top))
-        d = (g - w).abs().max().item() if w.numel() else 0.0
-        lines.append((d / (4 * r), k, d, r))
-        if not d <= 4 * r:
-            bad.append((k, d, 4 * r))
-    worst = max(lines)
-    WORST[entry] = max(WORST.get(entry, 0.0), worst[0])
-    print(f"[sh] {entry} {tag}: " + "  ".join(f"{k} d/4r {q:.3f}" for q, k, _, _ in lines) + f"   (worst of {entry} so far {WORST[entry]:.3f})")
-    assert not bad, (entry, tag, bad)
-    return worst[0]
+def held(entry, tag, got, ref64, ref32):
+    """the suite's rule on every tensor of ref64; keeps the worst ratio per entry point"""
+    worst = accuracy.within("sh", f"{entry} {tag}", got, ref64, ref32, show=None)
+    WORST[entry] = max(WORST.get(entry, 0.0), worst)
+    print(f"[sh]    (worst of {entry} so far {WORST[entry]:.3f})")
+    return worst
 
 
 def camera_centres(v=5):
@@ -154,13 +137,13 @@ def test_every_kernel_path_against_the_restatement(hip_device, k, deg, n):
         for vi in range(v):
             colors, clamped = sh_forward(md, sd, campos[vi].to(dev), deg)
             assert colors.shape == (n, 3) and clamped.shape == (n,) and clamped.dtype == torch.uint8
-            within("sh_forward", f"{tag} view {vi}", {"colors": colors}, {"colors": r64["colors"][vi]}, {"colors": r32["colors"][vi]})
+            held("sh_forward", f"{tag} view {vi}", {"colors": colors}, {"colors": r64["colors"][vi]}, {"colors": r32["colors"][vi]})
             assert torch.equal(clamped.cpu(), R.clamp_bits(r64["pre"][vi])), (tag, vi)
             assert torch.equal(colors.cpu() == 0, ~keep[vi]), (tag, vi)
         # sr_sh_forward_views: with keep, without, and into a caller's buffer
         colors, got_keep = sh_forward_views(md, sd, campos.to(dev), deg)
         assert colors.shape == (v, n, 3) and got_keep.shape == (v, n, 3) and got_keep.dtype == torch.float32
-        within("sh_forward_views", tag, {"colors": colors}, {"colors": r64["colors"]}, {"colors": r32["colors"]})
+        held("sh_forward_views", tag, {"colors": colors}, {"colors": r64["colors"]}, {"colors": r32["colors"]})
         assert torch.equal(got_keep.cpu(), keep.float()), tag
         bare, none = sh_forward_views(md, sd, campos.to(dev), deg, want_keep=False)
         assert none is None and torch.equal(bare, colors)
@@ -171,7 +154,7 @@ def test_every_kernel_path_against_the_restatement(hip_device, k, deg, n):
         dcol = probe * keep
         d_shs, d_means = hip_backward(dev, means, shs, campos, dcol, deg)
         assert d_shs.shape == (n, k, 3) and d_shs.dtype == torch.float32
-        within("sh_backward", tag, {"d_shs": d_shs, "d_means": d_means}, {x: r64[x] for x in ("d_shs", "d_means")}, r32)
+        held("sh_backward", tag, {"d_shs": d_shs, "d_means": d_means}, {x: r64[x] for x in ("d_shs", "d_means")}, r32)
         assert (d_shs[:, (deg + 1) ** 2:] == 0).all()
     # sh_to_rgb end to end, first camera: the clamp mask is the forward's own
     m, s = md.clone().requires_grad_(True), sd.clone().requires_grad_(True)
@@ -179,7 +162,7 @@ def test_every_kernel_path_against_the_restatement(hip_device, k, deg, n):
     (col * probe5[0].to(dev)).sum().backward()
     r64 = reference(means, shs, campos5[:1], probe5[:1], deg, torch.float64)
     r32 = reference(means, shs, campos5[:1], probe5[:1], deg, torch.float32)
-    within("sh_to_rgb", name, {"colors": col, "d_shs": s.grad, "d_means": m.grad},
+    held("sh_to_rgb", name, {"colors": col, "d_shs": s.grad, "d_means": m.grad},
            {"colors": r64["colors"][0], "d_shs": r64["d_shs"], "d_means": r64["d_means"]},
            {"colors": r32["colors"][0], "d_shs": r32["d_shs"], "d_means": r32["d_means"]})
 
@@ -198,13 +181,13 @@ def test_fixture_cases(hip_device, deg):
     assert (pre.abs() > 1e-4).all()
     colors, keep = sh_forward_views(means.to(dev), shs.to(dev), campos.to(dev), deg)
     assert torch.equal(keep.cpu().bool(), pre >= 0) and torch.equal(keep.cpu().bool(), want["colors"] > 0)
-    within("sh_forward_views", f"fixture deg{deg}", {"colors": colors}, {"colors": want["colors"]}, ref32)
+    held("sh_forward_views", f"fixture deg{deg}", {"colors": colors}, {"colors": want["colors"]}, ref32)
     for vi in range(2):
         one, clamped = sh_forward(means.to(dev), shs.to(dev), campos[vi].to(dev), deg)
-        within("sh_forward", f"fixture deg{deg} view {vi}", {"colors": one}, {"colors": want["colors"][vi]}, {"colors": ref32["colors"][vi]})
+        held("sh_forward", f"fixture deg{deg} view {vi}", {"colors": one}, {"colors": want["colors"][vi]}, {"colors": ref32["colors"][vi]})
         assert torch.equal(clamped.cpu(), R.clamp_bits(pre[vi]))
     d_shs, d_means = hip_backward(dev, means, shs, campos, probe * keep.cpu(), deg)
-    within("sh_backward", f"fixture deg{deg}", {"d_shs": d_shs, "d_means": d_means}, {k: want[k] for k in ("d_shs", "d_means")}, ref32)
+    held("sh_backward", f"fixture deg{deg}", {"d_shs": d_shs, "d_means": d_means}, {k: want[k] for k in ("d_shs", "d_means")}, ref32)
 
 
 # ---- the clamp boundary ------------------------------------------------------------------------------------------------------
@@ -301,11 +284,11 @@ def test_accumulate_means_adds_or_overwrites(hip_device, k, deg):
     prefill = torch.randn(257, 3, generator=torch.Generator().manual_seed(5))
     acc = prefill.to(dev)
     sh_backward(*args, means_grad=acc, accumulate_means=True)
-    within("sh_backward", f"accumulate K{k}-deg{deg}", {"d_means": acc}, {"d_means": prefill.double() + r64["d_means"]},
+    held("sh_backward", f"accumulate K{k}-deg{deg}", {"d_means": acc}, {"d_means": prefill.double() + r64["d_means"]},
            {"d_means": prefill + r32["d_means"]})
     over = torch.full((257, 3), NAN, device=dev)
     sh_backward(*args, means_grad=over, accumulate_means=False)
-    within("sh_backward", f"overwrite K{k}-deg{deg}", {"d_means": over}, {"d_means": r64["d_means"]}, r32)
+    held("sh_backward", f"overwrite K{k}-deg{deg}", {"d_means": over}, {"d_means": r64["d_means"]}, r32)
     if deg == 0:
         assert (over == 0).all() and torch.equal(acc.cpu(), prefill)
     default = prefill.to(dev)                                   # accumulate is the default
@@ -334,7 +317,7 @@ def test_scale_one_half_halves_exactly(hip_device, k, deg):
         assert torch.equal(a, 0.5 * b) and (b != 0).any()
     r64 = {k_: 0.5 * v for k_, v in reference(means, shs, campos, probe5[:3], deg, torch.float64).items() if k_ in ("d_shs", "d_means")}
     r32 = reference(means, shs, campos, probe5[:3], deg, torch.float32, scale=0.5)
-    within("sh_backward", f"scale 0.5 K{k}-deg{deg}", {"d_shs": half[0], "d_means": half[1]}, r64, r32)
+    held("sh_backward", f"scale 0.5 K{k}-deg{deg}", {"d_shs": half[0], "d_means": half[1]}, r64, r32)
 
 
 @pytest.mark.parametrize("k", (16, 4), ids=lambda k: f"K{k}")

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import triplane_reference as R
+from tests.accuracy import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +49,6 @@ def assert_within(tag, got, ref64, r, fragile, tensors=R.TENSORS):
         assert d <= b, (tag, k, d, b)
 
 
-def identical(a: dict, b: dict, tensors=R.TENSORS) -> bool:
-    return all(torch.equal(a[k], b[k]) for k in tensors)
-
-
 # ---- parity table ----
 
 @pytest.mark.parametrize("name", [c.name for c in R.CASES])
@@ -59,7 +56,7 @@ def test_every_kernel_path_against_the_float64_reference(hip_device, name):
     e = R.evaluated(name)
     got = hip_lookup(hip_device, e["planes"], e["pts"], e["probe"])
     again = hip_lookup(hip_device, e["planes"], e["pts"], e["probe"])
-    assert identical(got, again), (name, "a second forward + backward differs")
+    assert same_bits(got, again, R.TENSORS), (name, "a second forward + backward differs")
     assert_within(name, got, e["f64"], e["r"], e["fragile"])
 
 
@@ -323,4 +320,4 @@ def test_more_than_128_channels(hip_device):
         out.backward(probe.to(dev))
     assert p.grad is None
     torch.cuda.synchronize(dev)                                               # refused on the host: nothing was launched, nothing is pending
-    assert identical(hip_lookup(dev, planes, pts, probe, planes_grad=False), got, ("out", "d_pts"))
+    assert same_bits(hip_lookup(dev, planes, pts, probe, planes_grad=False), got, ("out", "d_pts"))

@@ -2,11 +2,10 @@
 the PyTorch-op path of the same object (`ViewColor`, path "torch") on the CPU, which tests/test_view_color_reference.py pins to the
 reference's own network and render() expressions.
 
-The measure is the project's (tests/test_gpu_flow_head.py::within): per tensor, d = max |fused - float64 torch path| over EVERY
-element may be 4 r, r = max |float32 torch path - float64 torch path| on the same inputs, floored at one float32 ulp of the
-tensor's largest magnitude.  Every case prints d / (4 r) (run with -s).  No element is left out: points lie in [-1, 1]^3 and camera
-centres at radius >= 3, so the reference is finite everywhere (the one stated limit, a point AT a camera centre, has its own
-test).  Tensors compared: the colours and the gradients of feature, means3D or dirs, weight and bias.
+The measure is the suite's rule (tests/accuracy.py), with r from the float32 torch path on the CPU.  No element is left out:
+points lie in [-1, 1]^3 and camera centres at radius >= 3, so the reference is finite everywhere (the one stated limit, a point
+AT a camera centre, has its own test).  Tensors compared: the colours and the gradients of feature, means3D or dirs, weight and
+bias.
 
 Shapes: N = 1 (one lane), 63 / 64 / 65 (a wavefront's edge), 255 / 256 / 257 (the workgroup's edge: a workgroup is 256 points),
 1000 (several workgroups); widths 4 (one vector), 36 (not a multiple of the 16 columns a pass moves), 64, 128 (the reference's)
@@ -16,11 +15,11 @@ import copy
 import os
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from test_gpu_flow_head import within
+from tests.accuracy import ulp32, within
+from tests.launches import device_records
 
 pytestmark = pytest.mark.gpu
 NS = (1, 63, 64, 65, 255, 256, 257, 1000)
@@ -75,7 +74,7 @@ def check(tag, case, mode, dev):
     r64, r32 = (run(case, mode, dt, cpu, "torch") for dt in (torch.float64, torch.float32))
     got = run(case, mode, torch.float32, dev, "fused")
     assert set(got) == set(r64) and got["colours"].dtype == torch.float32 and got["colours"].shape == r64["colours"].shape
-    return within(f"view_color {tag} {mode}", got, r64, r32)
+    return within("view_color", f"{tag} {mode}", got, r64, r32)
 
 
 @pytest.mark.parametrize("mode", (CAMERAS, DIRS))
@@ -140,15 +139,8 @@ def test_no_points_and_converted_inputs(hip_device):
 
 
 def library_launches(fn):
-    """Device kernel records of the head's kernels and of the weight-gradient kernels it calls while fn runs (host activity on as
-    well: with the device activity alone the trace loses records), counted as tests/test_gpu_flow_head.py counts them."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU]
-    return [n for n in names if "k_view_color" in n or "k_mlp_weight_grad" in n]
+    """device records of the head's kernels and of the weight-gradient kernels it calls while fn runs"""
+    return [n for n in device_records(fn) if "k_view_color" in n or "k_mlp_weight_grad" in n]
 
 
 @pytest.mark.parametrize("mode", (CAMERAS, DIRS))
@@ -192,7 +184,7 @@ def test_a_point_at_a_camera_centre_is_non_finite_in_that_view_only(hip_device):
     mask[1, 77] = False
     assert torch.isfinite(got["colours"].cpu()[mask]).all()
     pick = lambda res: {"colours": res["colours"].cpu()[mask]}
-    within("view_color point at a camera centre, every other entry", pick(got), pick(r64), pick(r32))
+    within("view_color", "point at a camera centre, every other entry", pick(got), pick(r64), pick(r32))
 
 
 def fixture_step(data, dtype, device, **extra):
@@ -210,7 +202,7 @@ def test_whole_network_against_the_reference_record(hip_device):
     assert set(got) == set(names)
     r64 = {k: torch.from_numpy(data["f64/" + k]) for k in names}
     r32 = {k: torch.from_numpy(data["f32/" + k]) for k in names}
-    within("view_color network, reference record", got, r64, r32)
+    within("view_color", "network, reference record", got, r64, r32)
 
 
 def test_the_default_path_is_untouched(hip_device):
@@ -321,6 +313,6 @@ def test_a_view_loop_fed_from_one_call_against_single_view_calls_in_view_order(h
         total = sum(s[k].double() for s in singles)                      # view order
         top = max([total.abs().max().item()] + [s[k].abs().max().item() for s in singles])
         d = (one[k].double() - total).abs().max().item()
-        ulp = float(np.spacing(np.float32(top)))
+        ulp = ulp32(top)
         print(f"[view_color] view loop {k}: max difference {d:.3e}, float32 ulp at the largest magnitude {ulp:.3e}")
         assert top > 0 and d <= 2 * V * ulp, (k, d, ulp)

@@ -20,10 +20,8 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import csv
 import json
 import os
-import statistics
 import sys
 import types
 
@@ -31,6 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 HBM_ACHIEVABLE = 6.29e12     # bytes / s: a float4 copy on this part (79 % of the 8.0e12 specification)
 BYTES_PER_ELEMENT = 28       # read parameter, gradient and both moments, write three of them back
@@ -89,30 +89,9 @@ def optimizer_steps(n, dev, masks=(), variants=(), only=None):
     return steps
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
 def alternate(steps, warmup, min_window_s, repeats):
     """All sides warmed up, then `repeats` rounds over all of them; every window lasts at least `min_window_s`."""
-    iters = {}
-    for name, fn in steps.items():
-        for _ in range(warmup):
-            fn()
-        iters[name] = max(5, int(min_window_s * 1e3 / window_ms(fn, 5)) + 1)
-    times = {name: [] for name in steps}
-    for _ in range(repeats):
-        for name, fn in steps.items():
-            times[name].append(window_ms(fn, iters[name]))
-    return {name: {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                   "max_ms": round(max(ts), 5), "iterations_per_window": iters[name]} for name, ts in times.items()}
+    return benchkit.alternate(steps, warmup, min_window_s, repeats, calibrate=5, digits=5)[0]
 
 
 def optimizer_alone(n, height, width, sh_degree, dev, variants, min_window, repeats):
@@ -213,19 +192,7 @@ def render_step_with_optimizer_between(n, height, width, sh_degree, dev, steps_p
     for _ in range(repeats):
         for name, (params, opt, between) in series.items():
             out[name].append(window(params, opt, between, steps_per_window))
-    return {name: {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                   "max_ms": round(max(ts), 5), "steps_per_window": steps_per_window} for name, ts in out.items()}
-
-
-def read_stats(directory):
-    path = None
-    for dirpath, _, files in os.walk(directory):
-        for f in files:
-            if f.endswith("kernel_stats.csv"):
-                path = os.path.join(dirpath, f)
-    if path is None:
-        raise SystemExit(f"no kernel_stats.csv under {directory}")
-    return [(row["Name"], int(row["Calls"]), float(row["AverageNs"]), float(row["TotalDurationNs"])) for row in csv.DictReader(open(path))]
+    return {name: benchkit.window_stats(ts, steps_per_window, 5, "steps_per_window") for name, ts in out.items()}
 
 
 def merge(pairs, out_path, iters_total, n):
@@ -234,7 +201,7 @@ def merge(pairs, out_path, iters_total, n):
     for item in pairs:
         name, directory = item.split("=", 1)
         # the kernels of a step run in every step: the fills of the set-up and of the first step's state do not count
-        rows = [r for r in read_stats(directory) if r[1] >= iters_total]
+        rows = [r for r in benchkit.read_stats(directory) if r[1] >= iters_total]
         traces[name] = {"launches_per_step": round(sum(c for _, c, _, _ in rows) / iters_total, 2),
                         "kernel_us_per_step": round(sum(t for _, _, _, t in rows) / iters_total / 1e3, 3),
                         "distinct_kernels": len(rows), "steps_traced": iters_total, "splats": n,
@@ -243,8 +210,7 @@ def merge(pairs, out_path, iters_total, n):
         if name != "masked" and us > 0:
             traces[name]["share_of_achievable_hbm_in_kernel_time"] = round(BYTES_PER_ELEMENT * ELEMENTS_PER_SPLAT * n / (us * 1e-6) / HBM_ACHIEVABLE, 4)
     doc["kernel_trace"] = traces
-    json.dump(doc, open(out_path, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, out_path)
 
 
 def main():
@@ -299,10 +265,7 @@ def main():
         doc["render_step_optimizer_between"] = dict(
             splats=a.splats, shape=[3, a.height, a.width], sh_degree=a.sh_degree,
             **render_step_with_optimizer_between(a.splats, a.height, a.width, a.sh_degree, dev, 40, a.repeats))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -18,8 +18,6 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 import time
@@ -30,7 +28,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tools.hull_bench import alternate, look_at  # noqa: E402
+from tests.launches import stage_counts  # noqa: E402
+from tools import benchkit  # noqa: E402
+from tools.hull_bench import look_at  # noqa: E402
 
 
 def workload(n_images, size, seed=3):
@@ -75,22 +75,6 @@ def torch_cloud(depths, kinv, pose, images, n_pts):
     return xyz.min(), xyz.max(), xyz[pick], rgb[pick]
 
 
-def library_launches(fn):
-    from splatfields_amd import _lib
-    lib = _lib.load()
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_collect(ms, cnt)                                         # drop whatever was recorded before
-    cnt = (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_enable(1)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.sr_profile_enable(0)
-    lib.sr_profile_collect(ms, cnt)
-    return int(sum(cnt))
-
-
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--out", default=None)
@@ -131,8 +115,13 @@ def main():
                        f"ends with the host read of the count, the pytorch side is the float32 cloud, its min / max and a randperm pick; "
                        f"launches per call from torch.profiler and, for the hip side, from sr_profile_collect; peak device memory of one "
                        f"call above what was allocated before it; the numpy restatement on the host is timed once with the wall clock"}
-    doc.update(alternate(steps, a.warmup, a.min_window, a.repeats, a.profiled_iterations))
-    doc["hip"]["library_launches_per_call"] = library_launches(hip)
+    sides, times = benchkit.alternate(steps, a.warmup, a.min_window, a.repeats, calibrate=3, digits=4, count_key="calls_per_window")
+    doc.update(benchkit.with_launches(sides, steps, a.profiled_iterations, key="launches_per_call"))
+    doc["speedup_median"] = round(doc["pytorch"]["median_ms"] / doc["hip"]["median_ms"], 2)
+    doc["hip_faster_in_every_alternation"] = all(b < a_ for a_, b in zip(times["pytorch"], times["hip"]))
+    for name, fn in steps.items():
+        doc[name]["peak_device_mib"] = benchkit.peak_mib(fn)
+    doc["hip"]["library_launches_per_call"] = int(sum(stage_counts(hip)[1]))
     doc["rows"] = int(xyz.shape[0])
     doc["bounds"] = {"hip": bounds.tolist(), "pytorch_float32": [float(lo), float(hi)]}
     if not a.skip_cpu:
@@ -141,10 +130,7 @@ def main():
         doc["numpy_host"] = {"seconds": round(time.perf_counter() - t0, 2), "rows": int(want.shape[0])}
         doc["hip_bounds_equal_numpy_host_rounded"] = bounds.tolist() == [float(np.float32(want.min())), float(np.float32(want.max()))]
         doc["speedup_over_numpy_host"] = round(doc["numpy_host"]["seconds"] * 1e3 / doc["hip"]["median_ms"], 1)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0
 
 

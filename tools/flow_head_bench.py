@@ -15,7 +15,6 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -24,7 +23,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from tools.plane_attention_bench import compare  # noqa: E402
+from tools import benchkit  # noqa: E402
 
 
 def head_steps(dev, model, n, width, n_basis, seed=5):
@@ -111,12 +110,9 @@ def main():
                        "sr_profile_collect (one iteration); 'torch' is the default path and the baseline",
            "flow_head_launches": list(FLOW_HEAD_LAUNCHES), "head": {}}
     for model in FLOW_MODELS:
-        doc["head"][model] = compare(head_steps(dev, model, a.points, a.width, a.basis), a)
-    doc["network_step_se3"] = compare(network_steps(dev, a.points), a)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+        doc["head"][model] = benchkit.compare(head_steps(dev, model, a.points, a.width, a.basis), a)
+    doc["network_step_se3"] = benchkit.compare(network_steps(dev, a.points), a)
+    benchkit.write_doc(doc, a.out)
     return 0
 
 

@@ -16,9 +16,7 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +24,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from tools.plane_decoder_bench import launches_per_iteration, window_ms  # noqa: E402
+from tools import benchkit  # noqa: E402
 
 CONFIGS = {
     "static": dict(n_frames=0, composition_rank=0),
@@ -56,20 +54,8 @@ def network_steps(dev, config, precision, n, seed=0):
 
 
 def compare(fns, a):
-    iters = {}
-    for name, fn in fns.items():
-        for _ in range(a.warmup):
-            fn()
-        iters[name] = max(3, int(a.min_window * 1e3 / window_ms(fn, 3)) + 1)
-    times = {name: [] for name in fns}
-    for _ in range(a.repeats):
-        for name, fn in fns.items():
-            times[name].append(window_ms(fn, iters[name]))
-    doc = {}
-    for name, ts in times.items():
-        doc[name] = {"ms": [round(t, 4) for t in ts], "median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4),
-                     "max_ms": round(max(ts), 4), "iterations_per_window": iters[name],
-                     "launches_per_iteration": launches_per_iteration(fns[name], a.profiled_iterations) if a.profiled_iterations else "not measured"}
+    doc, times = benchkit.alternate(fns, a.warmup, a.min_window, a.repeats, calibrate=3, digits=4)
+    benchkit.with_launches(doc, fns, a.profiled_iterations)
     doc["grouped_minus_separate_median_ms"] = round(doc["grouped"]["median_ms"] - doc["separate"]["median_ms"], 4)
     doc["speedup_median"] = round(doc["separate"]["median_ms"] / doc["grouped"]["median_ms"], 3)
     doc["grouped_faster_in_every_alternation"] = all(g < s for s, g in zip(times["separate"], times["grouped"]))
@@ -105,10 +91,7 @@ def main():
             doc["steps"][f"{config}_{precision}"] = entry
             del fns, net
             torch.cuda.empty_cache()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0
 
 

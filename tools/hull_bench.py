@@ -17,7 +17,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -26,6 +25,8 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 
 def look_at(center, up):
@@ -86,60 +87,13 @@ def torch_hull(masks, rows, convention, tables, G):
     return idx.int(), torch.stack([x[idx], y[idx], z[idx]], dim=1).float()
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def launches_per_call(fn, iters):
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and not e.name.startswith(("Memcpy", "Memset"))]
-    if not events:
-        return None
-    return {"all": round(len(events) / iters, 2), "library": round(sum(1 for e in events if "sr::" in e.name) / iters, 2)}
-
-
-def peak_mib(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    fn()
-    torch.cuda.synchronize()
-    return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
-
-
 def alternate(steps, warmup, min_window_s, repeats, profiled):
-    iters = {}
-    for name, fn in steps.items():
-        for _ in range(warmup):
-            fn()
-        per = window_ms(fn, 3)
-        iters[name] = max(3, int(min_window_s * 1e3 / per) + 1)
-    times = {name: [] for name in steps}
-    for _ in range(repeats):
-        for name, fn in steps.items():
-            times[name].append(window_ms(fn, iters[name]))
-    out = {}
-    for name, ts in times.items():
-        out[name] = {"ms": [round(t, 4) for t in ts], "median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4),
-                     "max_ms": round(max(ts), 4), "calls_per_window": iters[name]}
+    out, times = benchkit.alternate(steps, warmup, min_window_s, repeats, calibrate=3, digits=4, count_key="calls_per_window")
     out["speedup_median"] = round(out["pytorch"]["median_ms"] / out["hip"]["median_ms"], 2)
     out["hip_faster_in_every_alternation"] = all(b < a for a, b in zip(times["pytorch"], times["hip"]))
+    benchkit.with_launches(out, steps, profiled, key="launches_per_call")
     for name, fn in steps.items():
-        out[name]["launches_per_call"] = launches_per_call(fn, profiled) if profiled else "not measured"
-        out[name]["peak_device_mib"] = peak_mib(fn)
+        out[name]["peak_device_mib"] = benchkit.peak_mib(fn)
     return out
 
 
@@ -190,10 +144,7 @@ def main():
         doc["conventions"][convention] = res
         print(json.dumps({convention: res}), flush=True)
     doc["hip_faster_in_every_alternation_of_both_conventions"] = all(r["hip_faster_in_every_alternation"] for r in doc["conventions"].values())
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0 if doc["hip_faster_in_every_alternation_of_both_conventions"] else 1
 
 

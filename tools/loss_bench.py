@@ -15,10 +15,8 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import csv
 import json
 import os
-import statistics
 import sys
 import types
 
@@ -26,6 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 HBM_PEAK = 8.0e12        # bytes / s (specification)
 FP32_PEAK = 157.3e12     # vector FLOP / s (specification)
@@ -92,33 +92,9 @@ def view_steps(n, height, width, sh_degree, dev):
     return {"restated": restated, "fused": fused}
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
 def alternate(steps, warmup, min_window_s, repeats):
     """Both sides warmed up, then `repeats` alternations; every window lasts at least `min_window_s`."""
-    iters = {}
-    for name, fn in steps.items():
-        for _ in range(warmup):
-            fn()
-        per = window_ms(fn, 5)
-        iters[name] = max(5, int(min_window_s * 1e3 / per) + 1)
-    times = {name: [] for name in steps}
-    for _ in range(repeats):
-        for name, fn in steps.items():
-            times[name].append(window_ms(fn, iters[name]))
-    out = {}
-    for name, ts in times.items():
-        out[name] = {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                     "max_ms": round(max(ts), 5), "iterations_per_window": iters[name]}
+    out = benchkit.alternate(steps, warmup, min_window_s, repeats, calibrate=5, digits=5)[0]
     r, f = out["restated"], out["fused"]
     out["speedup_median"] = round(r["median_ms"] / f["median_ms"], 3)
     out["saved_ms_median"] = round(r["median_ms"] - f["median_ms"], 5)
@@ -137,24 +113,13 @@ def algorithmic_bytes(channels, height, width):
     return {"forward": fwd, "backward": bwd, "flops": flops}
 
 
-def read_stats(directory):
-    path = None
-    for dirpath, _, files in os.walk(directory):
-        for f in files:
-            if f.endswith("kernel_stats.csv"):
-                path = os.path.join(dirpath, f)
-    if path is None:
-        raise SystemExit(f"no kernel_stats.csv under {directory}")
-    return [(row["Name"], int(row["Calls"]), float(row["AverageNs"]), float(row["TotalDurationNs"])) for row in csv.DictReader(open(path))]
-
-
 def merge(pairs, out_path, iters_total):
     doc = json.load(open(out_path))
     shape = doc["loss_alone"]["shape"]
     traces = {}
     for item in pairs:
         name, directory = item.split("=", 1)
-        rows = read_stats(directory)
+        rows = benchkit.read_stats(directory)
         traces[name] = {"launches_per_iteration": round(sum(c for _, c, _, _ in rows) / iters_total, 2),
                         "kernel_us_per_iteration": round(sum(t for _, _, _, t in rows) / iters_total / 1e3, 3),
                         "distinct_kernels": len(rows), "iterations_traced": iters_total}
@@ -177,8 +142,7 @@ def merge(pairs, out_path, iters_total):
                 kernels[label] = entry
             traces[name]["kernels"] = kernels
     doc["kernel_trace"] = traces
-    json.dump(doc, open(out_path, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, out_path)
 
 
 def main():
@@ -218,10 +182,7 @@ def main():
         doc["view_step"] = dict(splats=a.splats, shape=[3, a.height, a.width], sh_degree=a.sh_degree,
                                 **alternate(view_steps(a.splats, a.height, a.width, a.sh_degree, dev), 10, a.min_window, a.repeats))
     doc["algorithmic_bytes"] = algorithmic_bytes(3, a.height, a.width)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -15,11 +15,9 @@ Needs a HIP device; there is no CPU fallback for the fused side."""
 from __future__ import annotations
 
 import argparse
-import csv
 import json
 import math
 import os
-import statistics
 import sys
 import time
 
@@ -27,6 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 HBM_PEAK = 8.0e12        # bytes / s (specification)
 FP32_PEAK = 157.3e12     # vector FLOP / s (specification)
@@ -60,33 +60,9 @@ def device_steps(batch, height, width, masked, dev):
             "fused": lambda: image_metrics(pred, gt, mask, quantize=QUANTIZE)}
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
 def alternate(steps, warmup, min_window_s, repeats):
     """Both sides warmed up, then `repeats` alternations; every window lasts at least `min_window_s`."""
-    iters = {}
-    for name, fn in steps.items():
-        for _ in range(warmup):
-            fn()
-        per = window_ms(fn, 5)
-        iters[name] = max(5, int(min_window_s * 1e3 / per) + 1)
-    times = {name: [] for name in steps}
-    for _ in range(repeats):
-        for name, fn in steps.items():
-            times[name].append(window_ms(fn, iters[name]))
-    out = {}
-    for name, ts in times.items():
-        out[name] = {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                     "max_ms": round(max(ts), 5), "iterations_per_window": iters[name]}
+    out = benchkit.alternate(steps, warmup, min_window_s, repeats, calibrate=5, digits=5)[0]
     r, f = out["restated"], out["fused"]
     out["speedup_median"] = round(r["median_ms"] / f["median_ms"], 3)
     out["fused_faster_in_every_repetition"] = f["max_ms"] < r["min_ms"]     # worst fused < best restated
@@ -124,23 +100,12 @@ def algorithmic(batch, height, width, masked):
             "bound": "memory" if t_mem >= t_alu else "compute"}
 
 
-def read_stats(directory):
-    path = None
-    for dirpath, _, files in os.walk(directory):
-        for f in files:
-            if f.endswith("kernel_stats.csv"):
-                path = os.path.join(dirpath, f)
-    if path is None:
-        raise SystemExit(f"no kernel_stats.csv under {directory}")
-    return [(row["Name"], int(row["Calls"]), float(row["AverageNs"]), float(row["TotalDurationNs"])) for row in csv.DictReader(open(path))]
-
-
 def merge(pairs, out_path, iters_total, batch, height, width):
     doc = json.load(open(out_path))
     traces = {"batch": batch, "masked": True, "quantize": QUANTIZE}
     for item in pairs:
         name, directory = item.split("=", 1)
-        rows = read_stats(directory)
+        rows = benchkit.read_stats(directory)
         traces[name] = {"launches_per_call": round(sum(c for _, c, _, _ in rows) / iters_total, 2),
                         "kernel_us_per_call": round(sum(t for _, _, _, t in rows) / iters_total / 1e3, 3),
                         "distinct_kernels": len(rows), "calls_traced": iters_total}
@@ -157,8 +122,7 @@ def merge(pairs, out_path, iters_total, batch, height, width):
                     kernels[label].update(alg, share_of_peak=round(alg["least_time_us"] / us, 4))
             traces[name]["kernels"] = kernels
     doc["kernel_trace"] = traces
-    json.dump(doc, open(out_path, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, out_path)
 
 
 def main():
@@ -207,10 +171,7 @@ def main():
                 case["speedup_over_cpu"] = round(case["cpu_restated"]["min_ms"] / case["fused"]["median_ms"], 1)
             print(json.dumps(case), flush=True)
             doc["cases"].append(case)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

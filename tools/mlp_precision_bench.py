@@ -19,7 +19,6 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -28,6 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 KERNEL_GROUPS = (("chain", "k_mlp_chain"), ("pack", "k_mlp_pack"), ("weight_grad", "k_mlp_weight_grad"))
 WIDTH_GROUPS = (("chain8", "<8>"), ("chain4", "<4>"))      # the chain kernels of one hidden width (template argument HT)
@@ -58,17 +59,6 @@ def make_steps(n, dev, precisions, heads=None):
             sum((v * v).mean() for k, v in out.items() if torch.is_tensor(v) and k != "flow").backward()
         steps[precision] = step
     return steps
-
-
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
 
 
 def kernel_sums(fn, iters):
@@ -138,13 +128,13 @@ def main():
     for name, fn in steps.items():
         for _ in range(a.warmup):
             fn()
-        iters[name] = max(5, int(a.min_window * 1e3 / window_ms(fn, 5)) + 1)
+        iters[name] = max(5, int(a.min_window * 1e3 / benchkit.window_ms(fn, 5)) + 1)
         kernel_sums(fn, 2)                                # the profiler's own first-use cost stays out of the alternations
     rounds = []
     for _ in range(a.repeats):
         r = {}
         for name, fn in steps.items():
-            r[name] = dict(step_ms=round(window_ms(fn, iters[name]), 5), **kernel_sums(fn, a.profiled_steps))
+            r[name] = dict(step_ms=round(benchkit.window_ms(fn, iters[name]), 5), **kernel_sums(fn, a.profiled_steps))
         rounds.append(r)
     med = lambda name, key: round(statistics.median(r[name][key] for r in rounds), 5)
     summary = {name: {key: med(name, key) for key in ("step_ms", "chain", "pack", "weight_grad", "all_kernels", "launches")}
@@ -159,10 +149,7 @@ def main():
            "chain_speedup_median": round(summary["fp32"]["chain"] / summary["bf16"]["chain"], 3),
            "step_speedup_median": round(summary["fp32"]["step_ms"] / summary["bf16"]["step_ms"], 3),
            "verdict_item6_ask_ms": VERDICT_ASK_MS}
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0 if doc["chain_us_bf16_below_fp32_in_every_alternation"] else 1
 
 
@@ -176,11 +163,11 @@ def measure(a, dev, precisions, heads):
     for name, fn in steps.items():
         for _ in range(a.warmup):
             fn()
-        iters[name] = max(5, int(a.min_window * 1e3 / window_ms(fn, 5)) + 1)
+        iters[name] = max(5, int(a.min_window * 1e3 / benchkit.window_ms(fn, 5)) + 1)
         kernel_sums(fn, 2)
     rounds = []
     for _ in range(a.repeats):
-        rounds.append({name: dict(step_ms=round(window_ms(fn, iters[name]), 5), **kernel_sums(fn, a.profiled_steps)) for name, fn in steps.items()})
+        rounds.append({name: dict(step_ms=round(benchkit.window_ms(fn, iters[name]), 5), **kernel_sums(fn, a.profiled_steps)) for name, fn in steps.items()})
     gc.enable()
     keys = ("step_ms", "chain", "chain8", "chain4", "pack", "weight_grad", "all_kernels", "launches")
     summary = {name: {key: round(statistics.median(r[name][key] for r in rounds), 5) for key in keys} for name in steps}
@@ -211,10 +198,7 @@ def main_split(a, dev):
                 "chain8_speedup_median": round(summary["fp32"]["chain8"] / summary[name]["chain8"], 3),
                 "chain4_speedup_median": round(summary["fp32"]["chain4"] / summary[name]["chain4"], 3)}
         doc["heads"][heads or "default"] = entry
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0
 
 

@@ -16,16 +16,16 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import csv
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 HBM_PEAK = 8.0e12            # bytes / s (specification)
 GATHER_INFINITY_CACHE = 8.6e12   # bytes / s: random 1 KiB rows of a 38 MB table gathered chip-wide (measured figure of the kernel guide)
@@ -84,17 +84,6 @@ def steps(n, dev):
     return {"restated": restated, "fused": fused}
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
 def alternate(both, warmup, min_window_s, repeats):
     """Both sides warmed up, then `repeats` alternations; every window lasts at least `min_window_s`.  A side that runs out of
     memory is recorded as such."""
@@ -107,7 +96,7 @@ def alternate(both, warmup, min_window_s, repeats):
         try:
             for _ in range(warmup):
                 fn()
-            per = window_ms(fn, 3)
+            per = benchkit.window_ms(fn, 3)
         except torch.cuda.OutOfMemoryError as e:
             failed[name] = f"out of memory: {str(e).splitlines()[0]}"
             continue
@@ -116,11 +105,10 @@ def alternate(both, warmup, min_window_s, repeats):
     times = {name: [] for name in iters}
     for _ in range(repeats):
         for name in iters:
-            times[name].append(window_ms(both[name], iters[name]))
+            times[name].append(benchkit.window_ms(both[name], iters[name]))
     out = {}
     for name, ts in times.items():
-        out[name] = {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                     "max_ms": round(max(ts), 5), "iterations_per_window": iters[name], **peak[name]}
+        out[name] = {**benchkit.window_stats(ts, iters[name], 5, "iterations_per_window"), **peak[name]}
     for name, why in failed.items():
         out[name] = {"failed": why}
     if "restated" in times and "fused" in times:
@@ -144,23 +132,12 @@ GROUPS = (("forward", ("k_moran_forward", "k_moran_reduce")), ("backward_edges",
           ("knn", ("k_knn_", "k_rank_segments", "k_rev_")))
 
 
-def read_stats(directory):
-    path = None
-    for dirpath, _, files in os.walk(directory):
-        for f in files:
-            if f.endswith("kernel_stats.csv"):
-                path = os.path.join(dirpath, f)
-    if path is None:
-        raise SystemExit(f"no kernel_stats.csv under {directory}")
-    return [(row["Name"], int(row["Calls"]), float(row["AverageNs"]), float(row["TotalDurationNs"])) for row in csv.DictReader(open(path))]
-
-
 def merge(pairs, out_path, iters_total):
     doc = json.load(open(out_path))
     traces = {}
     for item in pairs:
         n, directory = item.split("=", 1)
-        rows = read_stats(directory)
+        rows = benchkit.read_stats(directory)
         by = algorithmic_bytes(int(n))
         entry = {"launches_per_iteration": round(sum(c for _, c, _, _ in rows) / iters_total, 2),
                  "kernel_us_per_iteration": round(sum(t for _, _, _, t in rows) / iters_total / 1e3, 3), "iterations_traced": iters_total,
@@ -179,8 +156,7 @@ def merge(pairs, out_path, iters_total):
                                             "launches_per_iteration": round(sum(c for _, c, _, _ in other) / iters_total, 2)}
         traces[n] = entry
     doc["kernel_trace_fused"] = traces
-    json.dump(doc, open(out_path, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, out_path)
 
 
 def main():
@@ -214,10 +190,7 @@ def main():
     for n in a.sizes:
         doc["sizes"][str(n)] = dict(algorithmic_bytes=algorithmic_bytes(n), **alternate(steps(n, dev), 5, a.min_window, a.repeats))
         print(json.dumps({n: doc["sizes"][str(n)]}), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -27,7 +27,9 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from tools.adam_bench import BYTES_PER_ELEMENT, HBM_ACHIEVABLE, alternate  # noqa: E402
+from tests.launches import device_events  # noqa: E402
+from tools import benchkit  # noqa: E402
+from tools.adam_bench import BYTES_PER_ELEMENT, HBM_ACHIEVABLE  # noqa: E402
 
 CONFIGS = {
     "static": dict(n_frames=0),
@@ -70,14 +72,7 @@ def host_ms(step, repeats=30):
 
 
 def launches(step):
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        step()
-        torch.cuda.synchronize()
-    host = {e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CPU}
-    # a host range (torch wraps Optimizer.step in one) is mirrored on the device's time line under its own name: no device work
-    records = [e for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and e.name not in host]
+    records = device_events(step, drop_host_ranges=True)
     return len(records), round(sum(e.time_range.elapsed_us() for e in records), 2)
 
 
@@ -85,7 +80,7 @@ def optimizer_alone(config, dev, min_window, repeats):
     shapes = shapes_of(config)
     elements = sum(int(torch.Size(s).numel()) for s in shapes)
     opts = sides(shapes, dev)
-    out = alternate({name: o.step for name, o in opts.items()}, 10, min_window, repeats)
+    out = benchkit.alternate({name: o.step for name, o in opts.items()}, 10, min_window, repeats, calibrate=5, digits=5)[0]
     for name, o in opts.items():
         r = out[name]
         h = host_ms(o.step)
@@ -122,7 +117,7 @@ def whole_step(dev, points, min_window, repeats):
             sum(v.sum() for k, v in out.items() if torch.is_tensor(v) and k != "flow").backward()
             model.optimizer.step()
         steps[name] = step
-    out = alternate(steps, 10, min_window, repeats)
+    out = benchkit.alternate(steps, 10, min_window, repeats, calibrate=5, digits=5)[0]
     out["fused_faster_in_every_alternation"] = all(a < b for a, b in zip(out["fused"]["ms"], out["torch"]["ms"]))
     out["saved_ms_median"] = round(out["torch"]["median_ms"] - out["fused"]["median_ms"], 5)
     return dict(points=points, what="forward + backward + optimizer step of SplatFields(n_frames=50, composition_rank=10)", **out)
@@ -157,10 +152,7 @@ def main():
     if not a.only_optimizer:
         doc["whole_step_4d"] = whole_step(dev, a.points, a.min_window, a.repeats)
         print(json.dumps(doc["whole_step_4d"]), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -19,13 +19,14 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 LAMBDAS = {"lambda_dssim": 0.2, "lambda_mask": 0.1, "lambda_norm": 0.01, "lambda_norm_mean": 0.01, "lambda_opacity": 0.01,
@@ -129,56 +130,14 @@ def objective_steps(n_views, n, height, width, dev):
     return {"pytorch": pytorch, "fused": fused}
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def launches_per_iteration(fn, iters):
-    """Device kernel records per iteration (host activity on as well: with the device activity alone the trace loses records);
-    None where the profiler records no device kernel."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and not e.name.startswith(("Memcpy", "Memset"))]
-    if not events:
-        return None
-    return {"all": round(len(events) / iters, 2),
-            "library": round(sum(1 for e in events if "sr::" in e.name) / iters, 2)}
-
-
 def alternate(steps, warmup, min_window_s, repeats, profiled):
     """Both sides warmed up, then `repeats` alternations; every window lasts at least `min_window_s`."""
-    iters = {}
-    for name, fn in steps.items():
-        for _ in range(warmup):
-            fn()
-        per = window_ms(fn, 5)
-        iters[name] = max(5, int(min_window_s * 1e3 / per) + 1)
-    times = {name: [] for name in steps}
-    for _ in range(repeats):
-        for name, fn in steps.items():
-            times[name].append(window_ms(fn, iters[name]))
-    out = {}
-    for name, ts in times.items():
-        out[name] = {"ms": [round(t, 5) for t in ts], "median_ms": round(statistics.median(ts), 5), "min_ms": round(min(ts), 5),
-                     "max_ms": round(max(ts), 5), "iterations_per_window": iters[name]}
+    out, times = benchkit.alternate(steps, warmup, min_window_s, repeats, calibrate=5, digits=5)
     p, f = out["pytorch"], out["fused"]
     out["speedup_median"] = round(p["median_ms"] / f["median_ms"], 3)
     out["saved_ms_median"] = round(p["median_ms"] - f["median_ms"], 5)
     out["fused_faster_in_every_alternation"] = all(b < a for a, b in zip(times["pytorch"], times["fused"]))
-    for name, fn in steps.items():
-        out[name]["launches_per_iteration"] = launches_per_iteration(fn, profiled) if profiled else "not measured"
-    return out
+    return benchkit.with_launches(out, steps, profiled)
 
 
 def main():
@@ -218,10 +177,7 @@ def main():
         print(json.dumps({"objective": doc["objective"][str(v)]}), flush=True)
     workloads = list(doc["splat_terms"].values()) + [doc["depth_l1"]] + list(doc["objective"].values())
     doc["fused_faster_in_every_alternation_of_every_workload"] = all(w["fused_faster_in_every_alternation"] for w in workloads)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0 if doc["fused_faster_in_every_alternation_of_every_workload"] else 1
 
 

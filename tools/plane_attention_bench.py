@@ -14,9 +14,7 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +22,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from tools.plane_decoder_bench import launches_per_iteration, library_launches, window_ms  # noqa: E402
+from tools import benchkit  # noqa: E402
 
 
 def generator_steps(dev, noise_res, seed=5):
@@ -78,27 +76,6 @@ def layer_steps(dev, noise_res, channels=32, groups=32, planes=3, seed=6):
     return {"torch": torch_path, "fused": fused}
 
 
-def compare(fns, a):
-    iters = {}
-    for name, fn in fns.items():
-        for _ in range(a.warmup):
-            fn()
-        iters[name] = max(3, int(a.min_window * 1e3 / window_ms(fn, 3)) + 1)
-    times = {name: [] for name in fns}
-    for _ in range(a.repeats):
-        for name, fn in fns.items():
-            times[name].append(window_ms(fn, iters[name]))
-    doc = {}
-    for name, ts in times.items():
-        doc[name] = {"ms": [round(t, 4) for t in ts], "median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4),
-                     "max_ms": round(max(ts), 4), "iterations_per_window": iters[name],
-                     "launches_per_iteration": launches_per_iteration(fns[name], a.profiled_iterations) if a.profiled_iterations else "not measured",
-                     "library_launches": library_launches(fns[name])}
-    doc["speedup_median"] = round(doc["torch"]["median_ms"] / doc["fused"]["median_ms"], 3)
-    doc["fused_faster_in_every_alternation"] = all(f < t for t, f in zip(times["torch"], times["fused"]))
-    return doc
-
-
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--out", default=None)
@@ -120,12 +97,9 @@ def main():
                        f">= {a.min_window} s between device events; launches from torch.profiler ({a.profiled_iterations} iterations per side) and from "
                        "sr_profile_collect (one iteration); 'torch' is the default path and the baseline",
            "attention_launches": list(ATTENTION_LAUNCHES),
-           "generator_step": compare(generator_steps(dev, a.noise_res), a),
-           "attention_layer": compare(layer_steps(dev, a.noise_res), a)}
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+           "generator_step": benchkit.compare(generator_steps(dev, a.noise_res), a),
+           "attention_layer": benchkit.compare(layer_steps(dev, a.noise_res), a)}
+    benchkit.write_doc(doc, a.out)
     return 0
 
 

@@ -12,16 +12,15 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+from tools import benchkit  # noqa: E402
 
 
 def steps(dev, noise_res, seed=5):
@@ -51,44 +50,6 @@ def steps(dev, noise_res, seed=5):
     return {"pytorch": pytorch, "hip": hip}
 
 
-def window_ms(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) / iters
-
-
-def launches_per_iteration(fn, iters):
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-    events = [e for e in prof.events() if e.device_type != torch.autograd.DeviceType.CPU and not e.name.startswith(("Memcpy", "Memset"))]
-    if not events:
-        return None
-    return {"all": round(len(events) / iters, 2), "library": round(sum(1 for e in events if "sr::" in e.name) / iters, 2)}
-
-
-def library_launches(fn):
-    from splatfields_amd import _lib
-    lib = _lib.load()
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_collect(ms, cnt)
-    ms, cnt = (C.c_double * _lib.PROFILE_STAGES)(), (C.c_longlong * _lib.PROFILE_STAGES)()
-    lib.sr_profile_enable(1)
-    fn()
-    torch.cuda.synchronize()
-    lib.sr_profile_enable(0)
-    lib.sr_profile_collect(ms, cnt)
-    return {"forward": cnt[0], "backward": cnt[6], "kernel_ms_forward": round(ms[0], 4), "kernel_ms_backward": round(ms[6], 4)}
-
-
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--out", default=None)
@@ -103,31 +64,17 @@ def main():
     dev = torch.device("cuda:0")
     from splatfields_amd.build import source_hash
     fns = steps(dev, a.noise_res)
-    iters = {}
-    for name, fn in fns.items():
-        for _ in range(a.warmup):
-            fn()
-        iters[name] = max(3, int(a.min_window * 1e3 / window_ms(fn, 3)) + 1)
-    times = {name: [] for name in fns}
-    for _ in range(a.repeats):
-        for name, fn in fns.items():
-            times[name].append(window_ms(fn, iters[name]))
+    stats, times = benchkit.alternate(fns, a.warmup, a.min_window, a.repeats, calibrate=3, digits=4)
     doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "_source_hash": source_hash(),
            "workload": f"three planes, 8 x {a.noise_res} x {a.noise_res} -> 16 x {8 * a.noise_res} x {8 * a.noise_res}, forward + backward, float32",
            "protocol": f"one process; both sides warmed up ({a.warmup} iterations), then {a.repeats} alternations pytorch / hip, windows >= "
                        f"{a.min_window} s between device events; launches from torch.profiler ({a.profiled_iterations} iterations per side) "
                        "and from sr_profile_collect (one iteration)"}
-    for name, ts in times.items():
-        doc[name] = {"ms": [round(t, 4) for t in ts], "median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4),
-                     "max_ms": round(max(ts), 4), "iterations_per_window": iters[name],
-                     "launches_per_iteration": launches_per_iteration(fns[name], a.profiled_iterations) if a.profiled_iterations else "not measured"}
-    doc["hip"]["library_launches"] = library_launches(fns["hip"])
+    doc.update(benchkit.with_launches(stats, fns, a.profiled_iterations))
+    doc["hip"]["library_launches"] = benchkit.library_launches(fns["hip"])
     doc["speedup_median"] = round(doc["pytorch"]["median_ms"] / doc["hip"]["median_ms"], 3)
     doc["hip_faster_in_every_alternation"] = all(h < t for t, h in zip(times["pytorch"], times["hip"]))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+    benchkit.write_doc(doc, a.out)
     return 0 if doc["hip_faster_in_every_alternation"] else 1
 
 

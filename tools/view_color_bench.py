@@ -16,7 +16,6 @@ Needs a HIP device; there is no CPU fallback."""
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 import types
@@ -26,7 +25,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from tools.plane_attention_bench import compare  # noqa: E402
+from tools import benchkit  # noqa: E402
 
 
 def head_steps(dev, n, width, n_views, seed=5):
@@ -122,12 +121,9 @@ def main():
            "view_color_launches": list(VIEW_COLOR_LAUNCHES), "head": {}}
     for n in a.points:
         for v in a.views:
-            doc["head"][f"N={n} V={v}"] = compare(head_steps(dev, n, a.width, v), a)
-    doc["view_dependent_step"] = compare(network_steps(dev, a.step_points, a.step_views, a.step_size), a)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc))
+            doc["head"][f"N={n} V={v}"] = benchkit.compare(head_steps(dev, n, a.width, v), a)
+    doc["view_dependent_step"] = benchkit.compare(network_steps(dev, a.step_points, a.step_views, a.step_size), a)
+    benchkit.write_doc(doc, a.out)
     return 0
 
 
