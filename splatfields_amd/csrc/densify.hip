@@ -14,6 +14,7 @@
 //
 // One host read (the new count, to allocate the outputs) instead of the reference's several.
 #include "host_api.h"
+#include "ordered_scan.h"
 
 namespace sr {
 
@@ -71,35 +72,15 @@ __global__ void __launch_bounds__(kBlock) k_densify_count(int n, const float* lo
     }
 }
 
-// exclusive prefix over the [kSeg][blocks] counts in segment-major order (= the final row order); totals[k] = rows of kind k
-__global__ void __launch_bounds__(1024) k_densify_scan(int blocks, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t s_part[1024];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0u;
-    __syncthreads();
-    for (int k = 0; k < kSeg; ++k) {
-        const uint32_t seg_start = s_carry;
-        for (int base = 0; base < blocks; base += 1024) {
-            const int j = base + (int)threadIdx.x;
-            const uint32_t v = j < blocks ? block_counts[(size_t)k * blocks + j] : 0u;
-            s_part[threadIdx.x] = v;
-            __syncthreads();
-            for (int d = 1; d < 1024; d <<= 1) {   // Hillis-Steele inclusive scan
-                const uint32_t add = threadIdx.x >= (unsigned)d ? s_part[threadIdx.x - d] : 0u;
-                __syncthreads();
-                s_part[threadIdx.x] += add;
-                __syncthreads();
-            }
-            const uint32_t carry = s_carry;
-            if (j < blocks) block_counts[(size_t)k * blocks + j] = carry + s_part[threadIdx.x] - v;
-            __syncthreads();
-            if (threadIdx.x == 1023) s_carry = carry + s_part[1023];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) totals[k] = s_carry - seg_start;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[kSeg] = s_carry;
+// exclusive prefix over the [kSeg][blocks] counts in segment-major order (= the final row order): the segments are contiguous and
+// the offsets global across them, so this is one scan in place (ordered_scan.h); totals[k] = rows of kind k, totals[kSeg] = all rows
+__global__ void __launch_bounds__(kScanBlock) k_densify_scan(int blocks, uint32_t* __restrict__ block_counts, uint32_t* __restrict__ totals) {
+    const uint32_t total = ordered_scan((long long)kSeg * blocks, [&](long long j) { return block_counts[j]; },
+                                        [&](long long j, uint32_t offset) { block_counts[j] = offset; });
+    __syncthreads();   // the offsets read below were stored by other threads of the workgroup
+    const int k = threadIdx.x;
+    if (k < kSeg) totals[k] = (k + 1 < kSeg ? block_counts[(size_t)(k + 1) * blocks] : total) - block_counts[(size_t)k * blocks];
+    if (k == kSeg) totals[kSeg] = total;
 }
 
 // dest[k][i] = final row of splat i's row of kind k, or -1
@@ -156,25 +137,31 @@ __global__ void __launch_bounds__(kBlock) k_densify_gather(int n, int row, const
     if (d3 >= 0) dst[(size_t)d3 * row + c] = c3;
 }
 
-size_t densify_workspace_bytes(int n) {
-    const size_t nb = (size_t)((n > 0 ? n : 1) + kBlock - 1) / kBlock;
-    return align_up((size_t)(n > 0 ? n : 1), 256) + align_up(sizeof(uint32_t) * kSeg * nb, 256) + 256;
-}
+struct DensifyCarve { uint8_t* flags; uint32_t* counts; uint32_t* totals; };
 
 // flags [N] | block counts / offsets [4][blocks] | totals [5]
+size_t carve_densify(void* base, int n, DensifyCarve* out) {
+    Carver c{static_cast<char*>(base), 0};
+    const size_t rows = (size_t)(n > 0 ? n : 1), blocks = (rows + kBlock - 1) / kBlock;
+    DensifyCarve t;
+    t.flags = c.take<uint8_t>(rows);
+    t.counts = c.take<uint32_t>(kSeg * blocks);
+    t.totals = c.take<uint32_t>(kSeg + 1);
+    if (out) *out = t;
+    return align_up(c.off, 256);
+}
+
 void launch_densify_plan(int n, const float* log_scales, int scale_cols, const float* opacity_logit, const float* grad_accum,
                          const float* denom, const float* max_radii2D, const DensifyArgs& a, void* workspace, int32_t* dest,
                          uint32_t** totals_out, hipStream_t st) {
     const int blocks = (n + kBlock - 1) / kBlock;
-    char* base = static_cast<char*>(workspace);
-    uint8_t* flags = reinterpret_cast<uint8_t*>(base);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(base + align_up((size_t)n, 256));
-    uint32_t* totals = reinterpret_cast<uint32_t*>(base + align_up((size_t)n, 256) + align_up(sizeof(uint32_t) * kSeg * (size_t)blocks, 256));
-    *totals_out = totals;
+    DensifyCarve c;
+    carve_densify(workspace, n, &c);
+    *totals_out = c.totals;
     hipLaunchKernelGGL(k_densify_count, dim3(blocks), dim3(kBlock), 0, st, n, log_scales, scale_cols, opacity_logit, grad_accum, denom,
-                       max_radii2D, a, flags, counts);
-    hipLaunchKernelGGL(k_densify_scan, dim3(1), dim3(1024), 0, st, blocks, counts, totals);
-    hipLaunchKernelGGL(k_densify_place, dim3(blocks), dim3(kBlock), 0, st, n, flags, counts, dest);
+                       max_radii2D, a, c.flags, c.counts);
+    hipLaunchKernelGGL(k_densify_scan, dim3(1), dim3(kScanBlock), 0, st, blocks, c.counts, c.totals);
+    hipLaunchKernelGGL(k_densify_place, dim3(blocks), dim3(kBlock), 0, st, n, c.flags, c.counts, dest);
 }
 
 void launch_densify_gather(int n, int row, const float* src, float* dst, const int32_t* dest, int mode, const float* log_scales,
@@ -194,7 +181,7 @@ using sr::fail; using sr::check_hip;
 
 extern "C" {
 
-size_t sr_densify_workspace_bytes(int n) { return sr::densify_workspace_bytes(n); }
+size_t sr_densify_workspace_bytes(int n) { return sr::carve_densify(nullptr, n, nullptr); }
 
 int sr_densify_plan(int n, const float* log_scales, int scale_cols, const float* opacity_logits, const float* grad_accum,
                     const float* denom, const float* max_radii2D, float grad_threshold, float min_opacity, float extent,

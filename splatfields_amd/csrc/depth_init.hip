@@ -79,7 +79,6 @@ __device__ __forceinline__ float wave_max(float v) {
 __global__ void __launch_bounds__(kBlock) k_depth_mark(const DepthItems it, const uint8_t* __restrict__ masks,
                                                        unsigned long long* __restrict__ words, uint32_t* __restrict__ block_counts,
                                                        float* __restrict__ block_lo, float* __restrict__ block_hi) {
-    __shared__ uint32_t s_count[kBlock / kWave];
     __shared__ float s_lo[kBlock / kWave], s_hi[kBlock / kWave];
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     bool alive = false;
@@ -95,16 +94,10 @@ __global__ void __launch_bounds__(kBlock) k_depth_mark(const DepthItems it, cons
                 if (c[a] == c[a]) { lo = c[a] < lo ? c[a] : lo; hi = c[a] > hi ? c[a] : hi; }   // a NaN coordinate is skipped
         }
     }
-    const unsigned long long word = __ballot(alive);     // every lane of the workgroup arrives here: lanes past n vote 0
     lo = wave_min(lo); hi = wave_max(hi);
-    if (lane_id() == 0) {
-        words[i / kWave] = word;                          // = 4 blockIdx + wave: the word array holds whole workgroups
-        s_count[wave_id()] = (uint32_t)__popcll(word);
-        s_lo[wave_id()] = lo; s_hi[wave_id()] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        block_counts[blockIdx.x] = s_count[0] + s_count[1] + s_count[2] + s_count[3];
+    if (lane_id() == 0) { s_lo[wave_id()] = lo; s_hi[wave_id()] = hi; }
+    compaction_mark(alive, i, words, block_counts);      // every lane of the workgroup arrives here: lanes past n vote 0
+    if (threadIdx.x == 0) {                               // behind the barrier of compaction_mark
         float l = s_lo[0], h = s_hi[0];
 #pragma unroll
         for (int w = 1; w < kBlock / kWave; ++w) { l = s_lo[w] < l ? s_lo[w] : l; h = s_hi[w] > h ? s_hi[w] : h; }
@@ -118,7 +111,8 @@ __global__ void __launch_bounds__(kScanBlock) k_depth_scan(long long blocks, uin
                                                            uint32_t* __restrict__ total, int* __restrict__ count_out,
                                                            float* __restrict__ bounds_out) {
     __shared__ float s_lo[kScanBlock / kWave], s_hi[kScanBlock / kWave];
-    const uint32_t carry = ordered_scan_counts(blocks, block_counts);
+    const uint32_t carry = ordered_scan(blocks, [&](long long j) { return block_counts[j]; },
+                                        [&](long long j, uint32_t offset) { block_counts[j] = offset; });
     float lo = __builtin_inff(), hi = -__builtin_inff();
     for (long long j = threadIdx.x; j < blocks; j += kScanBlock) {
         const float l = block_lo[j], h = block_hi[j];
@@ -170,14 +164,8 @@ __global__ void __launch_bounds__(kBlock) k_depth_gather(const DepthItems it, co
                                                          const DepthRows out) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= it.n) return;
-    const long long w0 = (long long)blockIdx.x * (kBlock / kWave);
-    const int w = wave_id(), lane = lane_id();
-    const unsigned long long word = words[w0 + w];
-    if (!((word >> lane) & 1ull)) return;
-    long long rank = block_offsets[blockIdx.x];
-    for (int k = 0; k < w; ++k) rank += __popcll(words[w0 + k]);
-    rank += __popcll(word & ((1ull << lane) - 1ull));
-    if (rank >= capacity) return;                        // an ordered prefix when the caller's buffers are short
+    long long rank;
+    if (!compaction_rank(words, block_offsets, rank) || rank >= capacity) return;            // dropped, or past an ordered prefix when the caller's buffers are short
     depth_write_row(it, out, rank, i);
 }
 

@@ -82,7 +82,6 @@ __device__ __forceinline__ void hull_position(const HullItems& it, long long i, 
 __global__ void __launch_bounds__(kBlock) k_hull_carve(const HullItems it, int n_views, const SrHullView* __restrict__ views,
                                                        const uint8_t* __restrict__ masks, unsigned long long* __restrict__ words,
                                                        uint32_t* __restrict__ block_counts) {
-    __shared__ uint32_t s_count[kBlock / kWave];
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     bool alive = i < it.n;
     if (alive) {
@@ -90,19 +89,14 @@ __global__ void __launch_bounds__(kBlock) k_hull_carve(const HullItems it, int n
         hull_position(it, i, x, y, z);
         for (int v = 0; v < n_views && alive; ++v) alive = hull_view_keeps(views[v], masks, x, y, z);   // views[v]: the same record for every lane
     }
-    const unsigned long long word = __ballot(alive);     // every lane of the workgroup arrives here: lanes past n vote 0
-    if (lane_id() == 0) {
-        words[i / kWave] = word;                          // = 4 blockIdx + wave: the word array holds whole workgroups (carve_hull),
-        s_count[wave_id()] = (uint32_t)__popcll(word);    // so the waves of the last one that start past n have their slot too
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_count[0] + s_count[1] + s_count[2] + s_count[3];
+    compaction_mark(alive, i, words, block_counts);      // every lane of the workgroup arrives here: lanes past n vote 0
 }
 
 // exclusive prefix over the workgroup counts, in index order, in place; the total goes to `total` (workspace) and `count_out`
 __global__ void __launch_bounds__(kScanBlock) k_hull_scan(long long blocks, uint32_t* __restrict__ block_counts,
                                                           uint32_t* __restrict__ total, int* __restrict__ count_out) {
-    const uint32_t carry = ordered_scan_counts(blocks, block_counts);
+    const uint32_t carry = ordered_scan(blocks, [&](long long j) { return block_counts[j]; },
+                                        [&](long long j, uint32_t offset) { block_counts[j] = offset; });
     if (threadIdx.x == 0) { *total = carry; if (count_out) *count_out = (int)carry; }
 }
 
@@ -111,14 +105,8 @@ __global__ void __launch_bounds__(kBlock) k_hull_gather(const HullItems it, cons
                                                         int* __restrict__ indices_out, float* __restrict__ points_out) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= it.n) return;
-    const long long w0 = (long long)blockIdx.x * (kBlock / kWave);
-    const int w = wave_id(), lane = lane_id();
-    const unsigned long long word = words[w0 + w];
-    if (!((word >> lane) & 1ull)) return;
-    long long rank = block_offsets[blockIdx.x];
-    for (int k = 0; k < w; ++k) rank += __popcll(words[w0 + k]);
-    rank += __popcll(word & ((1ull << lane) - 1ull));
-    if (rank >= capacity) return;                        // an ordered prefix when the caller's buffers are short
+    long long rank;
+    if (!compaction_rank(words, block_offsets, rank) || rank >= capacity) return;            // carved, or past an ordered prefix when the caller's buffers are short
     if (indices_out) indices_out[rank] = (int)i;
     if (points_out) {
         double x, y, z;

@@ -10,6 +10,7 @@
 // Second half of the file: the K-nearest-neighbour GRAPH (2 <= K <= 8, self included) of the Moran's I regulariser on the same
 // grid -- the counterpart of [EXT] pytorch3d.ops.knn.knn_points at reference extract_geo.py:101-103.
 #include "host_api.h"
+#include "ordered_scan.h"
 
 namespace sr {
 
@@ -76,31 +77,18 @@ __global__ void k_knn_count(int n, const float* __restrict__ pts, const float* _
     atomicAdd(&count[(c.z * g.gy + c.y) * g.gx + c.x], 1u);
 }
 
-// exclusive scan of count[0..cells) by one workgroup of 1024 -> start[0..cells]; cursor := 0
+// exclusive scan of count[0..cells) by one workgroup (ordered_scan.h) -> start[0..cells]; cursor := 0
 __device__ __forceinline__ void scan_counts(int cells, const uint32_t* __restrict__ count, uint32_t* __restrict__ start,
-                                            uint32_t* __restrict__ cursor, uint32_t* s_wave) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    uint32_t carry = 0;
-    for (int base = 0; base < cells; base += 1024) {
-        const int i = base + tid;
-        const uint32_t v = i < cells ? count[i] : 0u;
-        const uint32_t inc = wave_inclusive_scan(v);
-        if (lane == 63) s_wave[w] = inc;
-        __syncthreads();
-        uint32_t wave_base = 0, all = 0;
-        for (int k = 0; k < 16; ++k) { const uint32_t t = s_wave[k]; if (k < w) wave_base += t; all += t; }
-        if (i < cells) { start[i] = carry + wave_base + inc - v; cursor[i] = 0u; }
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) start[cells] = carry;
+                                            uint32_t* __restrict__ cursor) {
+    const uint32_t total = ordered_scan(cells, [&](long long i) { return count[i]; },
+                                        [&](long long i, uint32_t offset) { start[i] = offset; cursor[i] = 0u; });
+    if (threadIdx.x == 0) start[cells] = total;
 }
 
-__global__ void __launch_bounds__(1024) k_knn_scan(const float* __restrict__ bounds, int n, int max_cells, const uint32_t* __restrict__ count,
-                                                   uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
-    __shared__ uint32_t s_wave[16];
+__global__ void __launch_bounds__(kScanBlock) k_knn_scan(const float* __restrict__ bounds, int n, int max_cells, const uint32_t* __restrict__ count,
+                                                         uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
     const KnnGrid g = make_grid(bounds, n, max_cells);
-    scan_counts(g.gx * g.gy * g.gz, count, start, cursor, s_wave);
+    scan_counts(g.gx * g.gy * g.gz, count, start, cursor);
 }
 
 __global__ void k_knn_fill(int n, const float* __restrict__ pts, const float* __restrict__ bounds, int max_cells, const uint32_t* __restrict__ start,
@@ -161,27 +149,35 @@ __global__ void k_knn_search(int n, const float* __restrict__ pts, const float* 
     out[i] = sum / 3.0f;
 }
 
-static size_t knn_workspace_bytes(int n) {
-    const size_t cells = (size_t)(n > 2 ? n : 2);  // max_cells = n
-    return align_up(8 * sizeof(float), 256) + 3 * align_up((cells + 1) * sizeof(uint32_t), 256) + align_up((size_t)(n > 0 ? n : 1) * sizeof(uint32_t), 256);
+struct KnnCarve { int max_cells; float* bounds; uint32_t* count; uint32_t* start; uint32_t* cursor; uint32_t* unordered; uint32_t* unordered_edges; };
+
+// bounds [8] | cell counts | cell starts | cell cursors [max_cells + 1 each] | the points, cell after cell, as the cursors left them [n]
+// | the graph's reverse edges, target after target, likewise [n k] (k = 0, sr_knn3_mean_dist2: none)
+static size_t carve_knn(void* base, int n, int k, KnnCarve* out) {
+    Carver c{static_cast<char*>(base), 0};
+    KnnCarve t;
+    t.max_cells = n > 2 ? n : 2;
+    t.bounds = c.take<float>(8);
+    t.count = c.take<uint32_t>((size_t)t.max_cells + 1);
+    t.start = c.take<uint32_t>((size_t)t.max_cells + 1);
+    t.cursor = c.take<uint32_t>((size_t)t.max_cells + 1);
+    t.unordered = c.take<uint32_t>((size_t)(n > 0 ? n : 1));
+    t.unordered_edges = k > 0 ? c.take<uint32_t>((size_t)n * k) : nullptr;
+    if (out) *out = t;
+    return align_up(c.off, 256);
 }
 
 static void launch_knn3(int n, const float* pts, float* out, void* workspace, hipStream_t st) {
     if (n <= 0) return;
-    Carver c{static_cast<char*>(workspace), 0};
-    const int max_cells = n > 2 ? n : 2;
-    float* bounds = c.take<float>(8);
-    uint32_t* count = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* start = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* cursor = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* order = c.take<uint32_t>((size_t)n);
+    KnnCarve c;
+    carve_knn(workspace, n, 0, &c);
     const int nb = (n + 255) / 256;
-    hipMemsetAsync(count, 0, sizeof(uint32_t) * ((size_t)max_cells + 1), st);
-    hipLaunchKernelGGL(k_knn_bounds, dim3(1), dim3(1024), 0, st, n, pts, bounds);
-    hipLaunchKernelGGL(k_knn_count, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, count);
-    hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(1024), 0, st, bounds, n, max_cells, count, start, cursor);
-    hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, cursor, order);
-    hipLaunchKernelGGL(k_knn_search, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, order, out);
+    hipMemsetAsync(c.count, 0, sizeof(uint32_t) * ((size_t)c.max_cells + 1), st);
+    hipLaunchKernelGGL(k_knn_bounds, dim3(1), dim3(1024), 0, st, n, pts, c.bounds);
+    hipLaunchKernelGGL(k_knn_count, dim3(nb), dim3(256), 0, st, n, pts, c.bounds, c.max_cells, c.count);
+    hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(kScanBlock), 0, st, c.bounds, n, c.max_cells, c.count, c.start, c.cursor);
+    hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, c.bounds, c.max_cells, c.start, c.cursor, c.unordered);
+    hipLaunchKernelGGL(k_knn_search, dim3(nb), dim3(256), 0, st, n, pts, c.bounds, c.max_cells, c.start, c.unordered, out);
 }
 
 // ---- k-nearest-neighbour graph (self included) and its reverse adjacency: the Moran regulariser's neighbourhoods ----
@@ -269,9 +265,8 @@ __global__ void k_rev_count(int edges, const int* __restrict__ nn_ix, uint32_t* 
     if (e < edges) atomicAdd(&count[nn_ix[e]], 1u);
 }
 
-__global__ void __launch_bounds__(1024) k_rev_scan(int n, const uint32_t* __restrict__ count, uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
-    __shared__ uint32_t s_wave[16];
-    scan_counts(n, count, start, cursor, s_wave);
+__global__ void __launch_bounds__(kScanBlock) k_rev_scan(int n, const uint32_t* __restrict__ count, uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
+    scan_counts(n, count, start, cursor);
 }
 
 __global__ void k_rev_fill(int edges, const int* __restrict__ nn_ix, const uint32_t* __restrict__ start, uint32_t* __restrict__ cursor,
@@ -283,10 +278,7 @@ __global__ void k_rev_fill(int edges, const int* __restrict__ nn_ix, const uint3
 }
 
 static size_t knn_graph_workspace_bytes(int n, int k) {
-    if (n <= 0 || k < kKnnMinK || k > kKnnMaxK) return 0;
-    const size_t cells = (size_t)(n > 2 ? n : 2);
-    return align_up(8 * sizeof(float), 256) + 3 * align_up((cells + 1) * sizeof(uint32_t), 256) + align_up((size_t)n * sizeof(uint32_t), 256) +
-           align_up((size_t)n * k * sizeof(uint32_t), 256);
+    return n <= 0 || k < kKnnMinK || k > kKnnMaxK ? 0 : carve_knn(nullptr, n, k, nullptr);
 }
 
 template <int K>
@@ -297,36 +289,30 @@ static void launch_search_k(int nb, int n, const float* pts, const float* bounds
 
 static void launch_knn_graph(int n, int k, const float* pts, int* nn_ix, uint32_t* order, uint32_t* rev_start, uint32_t* rev_edges, void* workspace,
                              hipStream_t st) {
-    Carver c{static_cast<char*>(workspace), 0};
-    const int max_cells = n > 2 ? n : 2;
-    float* bounds = c.take<float>(8);
-    uint32_t* count = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* start = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* cursor = c.take<uint32_t>((size_t)max_cells + 1);
-    uint32_t* unordered = c.take<uint32_t>((size_t)n);
-    uint32_t* unordered_edges = c.take<uint32_t>((size_t)n * k);
+    KnnCarve c;
+    carve_knn(workspace, n, k, &c);
     const int nb = (n + 255) / 256, edges = n * k, eb = (edges + 255) / 256;
-    hipMemsetAsync(count, 0, sizeof(uint32_t) * ((size_t)max_cells + 1), st);
-    hipLaunchKernelGGL(k_knn_bounds, dim3(1), dim3(1024), 0, st, n, pts, bounds);
-    hipLaunchKernelGGL(k_knn_count, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, count);
-    hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(1024), 0, st, bounds, n, max_cells, count, start, cursor);
-    hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, bounds, max_cells, start, cursor, unordered);
-    hipLaunchKernelGGL(k_rank_segments, dim3(nb), dim3(256), 0, st, n, unordered, (const int*)nullptr, n, pts, bounds, max_cells, start, order);
+    hipMemsetAsync(c.count, 0, sizeof(uint32_t) * ((size_t)c.max_cells + 1), st);
+    hipLaunchKernelGGL(k_knn_bounds, dim3(1), dim3(1024), 0, st, n, pts, c.bounds);
+    hipLaunchKernelGGL(k_knn_count, dim3(nb), dim3(256), 0, st, n, pts, c.bounds, c.max_cells, c.count);
+    hipLaunchKernelGGL(k_knn_scan, dim3(1), dim3(kScanBlock), 0, st, c.bounds, n, c.max_cells, c.count, c.start, c.cursor);
+    hipLaunchKernelGGL(k_knn_fill, dim3(nb), dim3(256), 0, st, n, pts, c.bounds, c.max_cells, c.start, c.cursor, c.unordered);
+    hipLaunchKernelGGL(k_rank_segments, dim3(nb), dim3(256), 0, st, n, c.unordered, (const int*)nullptr, n, pts, c.bounds, c.max_cells, c.start, order);
     switch (k) {
-        case 2: launch_search_k<2>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        case 3: launch_search_k<3>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        case 4: launch_search_k<4>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        case 5: launch_search_k<5>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        case 6: launch_search_k<6>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        case 7: launch_search_k<7>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
-        default: launch_search_k<8>(nb, n, pts, bounds, max_cells, start, order, nn_ix, st); break;
+        case 2: launch_search_k<2>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        case 3: launch_search_k<3>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        case 4: launch_search_k<4>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        case 5: launch_search_k<5>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        case 6: launch_search_k<6>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        case 7: launch_search_k<7>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
+        default: launch_search_k<8>(nb, n, pts, c.bounds, c.max_cells, c.start, order, nn_ix, st); break;
     }
     // reverse adjacency: per target, the edges that end there, by edge id
-    hipMemsetAsync(count, 0, sizeof(uint32_t) * ((size_t)n + 1), st);
-    hipLaunchKernelGGL(k_rev_count, dim3(eb), dim3(256), 0, st, edges, nn_ix, count);
-    hipLaunchKernelGGL(k_rev_scan, dim3(1), dim3(1024), 0, st, n, count, rev_start, cursor);
-    hipLaunchKernelGGL(k_rev_fill, dim3(eb), dim3(256), 0, st, edges, nn_ix, rev_start, cursor, unordered_edges);
-    hipLaunchKernelGGL(k_rank_segments, dim3(eb), dim3(256), 0, st, edges, unordered_edges, nn_ix, n, pts, bounds, max_cells, rev_start, rev_edges);
+    hipMemsetAsync(c.count, 0, sizeof(uint32_t) * ((size_t)n + 1), st);
+    hipLaunchKernelGGL(k_rev_count, dim3(eb), dim3(256), 0, st, edges, nn_ix, c.count);
+    hipLaunchKernelGGL(k_rev_scan, dim3(1), dim3(kScanBlock), 0, st, n, c.count, rev_start, c.cursor);
+    hipLaunchKernelGGL(k_rev_fill, dim3(eb), dim3(256), 0, st, edges, nn_ix, rev_start, c.cursor, c.unordered_edges);
+    hipLaunchKernelGGL(k_rank_segments, dim3(eb), dim3(256), 0, st, edges, c.unordered_edges, nn_ix, n, pts, c.bounds, c.max_cells, rev_start, rev_edges);
 }
 
 }  // namespace sr
@@ -336,7 +322,7 @@ using sr::fail; using sr::check_hip;
 
 extern "C" {
 
-size_t sr_knn_workspace_bytes(int n) { return sr::knn_workspace_bytes(n); }
+size_t sr_knn_workspace_bytes(int n) { return sr::carve_knn(nullptr, n, 0, nullptr); }
 
 int sr_knn3_mean_dist2(int n, const float* points, float* mean_dist2, void* workspace, void* hip_stream) {
     if (n < 0 || (n > 0 && (!points || !mean_dist2 || !workspace))) return fail("bad arguments to sr_knn3_mean_dist2");

@@ -22,6 +22,7 @@
 // the CUs (they were 0.43 ms of device-scope atomics on a 39 MB accumulator, plus its clearing and conversion passes), and
 // because the sums are integer the arbitrary order of a tile's list never reaches the result.
 #include "host_api.h"
+#include "ordered_scan.h"
 
 namespace sr {
 
@@ -155,32 +156,12 @@ __global__ void __launch_bounds__(kBlock) k_tp_bin(int N, int H, int W, const fl
     });
 }
 
-// exclusive prefix of the 3 tiles x kTpCopies counts (one workgroup); count[] becomes the cursor array of the scattering pass
-__global__ void __launch_bounds__(1024) k_tp_bin_scan(int bins, const TpBins b) {   // bins: a multiple of 4 (kTpCopies)
-    __shared__ uint32_t s_wave[16];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    uint32_t carry = 0;
-    for (int base = 0; base < bins; base += 4096) {   // four consecutive counters per thread
-        const int i = base + 4 * tid;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (i < bins) v = *reinterpret_cast<const uint4*>(b.count + i);
-        const uint32_t sum = v.x + v.y + v.z + v.w;
-        const uint32_t inc = wave_inclusive_scan(sum);
-        if (lane == 63) s_wave[w] = inc;
-        __syncthreads();
-        uint32_t wave_base = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const uint32_t x = s_wave[k]; if (k < w) wave_base += x; all += x; }
-        if (i < bins) {
-            const uint32_t e0 = carry + wave_base + inc - sum;
-            const uint4 ex = make_uint4(e0, e0 + v.x, e0 + v.x + v.y, e0 + v.x + v.y + v.z);
-            *reinterpret_cast<uint4*>(b.start + i) = ex;
-            *reinterpret_cast<uint4*>(b.count + i) = ex;
-        }
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) b.start[bins] = carry;
+// exclusive prefix of the 3 tiles x kTpCopies counts (one workgroup, ordered_scan.h); count[] becomes the cursor array of the
+// scattering pass
+__global__ void __launch_bounds__(kScanBlock) k_tp_bin_scan(int bins, uint32_t* __restrict__ count, uint32_t* __restrict__ start) {
+    const uint32_t total = ordered_scan(bins, [&](long long i) { return count[i]; },
+                                        [&](long long i, uint32_t offset) { start[i] = offset; count[i] = offset; });
+    if (threadIdx.x == 0) start[bins] = total;
 }
 
 // One workgroup per (tile, plane): the tile's pairs -> TILE x TILE x C 64-bit accumulators in LDS -> dL/dplanes [3][C][HW].
@@ -333,10 +314,10 @@ int launch_triplane_backward(int N, int C, int H, int W, const float* planes_hwc
             hipLaunchKernelGGL(k_tp_absmax, dim3(blocks > 0 ? blocks : 1), dim3(kBlock), 0, st, count, g, b.gmax);
             const unsigned pair_blocks = (unsigned)(((long long)N * 3 + kBlock - 1) / kBlock);
             hipLaunchKernelGGL(k_tp_bin<false>, dim3(pair_blocks), dim3(kBlock), 0, st, N, H, W, pts, b);
-            hipLaunchKernelGGL(k_tp_bin_scan, dim3(1), dim3(1024), 0, st, bins, b);
+            hipLaunchKernelGGL(k_tp_bin_scan, dim3(1), dim3(kScanBlock), 0, st, bins, b.count, b.start);
             hipLaunchKernelGGL(k_tp_bin<true>, dim3(pair_blocks), dim3(kBlock), 0, st, N, H, W, pts, b);
         } else {
-            hipLaunchKernelGGL(k_tp_bin_scan, dim3(1), dim3(1024), 0, st, bins, b);   // all starts 0
+            hipLaunchKernelGGL(k_tp_bin_scan, dim3(1), dim3(kScanBlock), 0, st, bins, b.count, b.start);   // all starts 0
         }
         const size_t lds = (size_t)b.tile * b.tile * C * sizeof(unsigned long long);
         if (b.tile == 16) hipLaunchKernelGGL(k_tp_accumulate<16>, dim3(nt, 3), dim3(kBlock), lds, st, N, C, H, W, pts, g, b, d_planes_chw);

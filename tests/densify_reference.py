@@ -31,6 +31,8 @@ from collections import namedtuple
 
 import torch
 
+from tests.scan_round import BLOCK, SCAN_ROUND
+
 PARAM_NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
 KINDS = ("self", "clone", "first child", "second child")
 Result = namedtuple("Result", "params moments counts source kind")
@@ -327,10 +329,16 @@ def single_row_case(cls: str, seed: int = 0) -> dict:
     return c
 
 
+def full_scan_pass_case(seed: int = 0) -> dict:
+    """k_densify_scan is one ordered_scan (csrc/ordered_scan.h) over four counts per workgroup of 256 rows.  SCAN_ROUND / 4
+    workgroups, the last one full: exactly one round of it.  No moments: 262 144 rows of them prove no more than 1000 do."""
+    return make_case(SCAN_ROUND // 4 * BLOCK, seed * 1000 + 5, max_screen_size=20.0, with_moments=False)
+
+
 def second_scan_pass_case(seed: int = 0) -> dict:
-    """1025 workgroups of 256 rows: one beyond a 1024-wide pass of k_densify_scan.  No moments: 262 145 rows of them prove no
-    more than 1000 do."""
-    return make_case(262_145, seed * 1000 + 7, max_screen_size=20.0, with_moments=False)
+    """One row more than full_scan_pass_case: one workgroup, hence four counts -- the smallest step this scan's length takes --
+    beyond a round of ordered_scan; the kinds' segments of 1025 counts straddle the round."""
+    return make_case(SCAN_ROUND // 4 * BLOCK + 1, seed * 1000 + 7, max_screen_size=20.0, with_moments=False)
 
 
 def segment_case(which: str, seed: int = 0, n: int = 1000) -> dict:
@@ -500,6 +508,7 @@ def all_cases(seed: int = 0) -> dict:
     """name -> a function that builds the case: everything tests/test_gpu_densify_edges.py runs."""
     cases = {f"boundary_{n}": (lambda n=n: boundary_case(n, seed)) for n in (2, 63, 64, 65, 255, 256, 257, 511, 513)}
     cases.update({f"single_{k}": (lambda k=k: single_row_case(k, seed)) for k in ("split", "clone")})
+    cases["full_scan_pass"] = lambda: full_scan_pass_case(seed)
     cases["second_scan_pass"] = lambda: second_scan_pass_case(seed)
     cases.update({f"segment_{k}": (lambda k=k: segment_case(k, seed)) for k in ("none_hot", "all_cloned", "all_split", "all_pruned", "empty_input", "children_only")})
     cases.update({f"tie_{k}": (lambda k=k: tie_case(k, seed)) for k in ("dense", "dense_above", "world", "opacity", "grad", "radius")})

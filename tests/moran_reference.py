@@ -17,6 +17,8 @@ import os
 import numpy as np
 import torch
 
+from tests.scan_round import SCAN_ROUND
+
 DENOM_EPS = 1e-4
 METRICS = ("term", "total", "grad_max", "grad_l2")
 REFERENCE_WIDTHS = (3, 4, 1, 48)          # scales, rotations, opacity, SH features (train.py:204-210)
@@ -180,7 +182,11 @@ def cloud_with_non_finite_rows():
 
 
 # the clouds on which the device's neighbour search is compared with the exact one: (kind, points, seed)
-KNN_CLOUDS = (("uniform", 1000, 45), ("clustered", 20000, 42), ("planar", 4000, 43), ("uniform", 300000, 44))
+# SCAN_ROUND - 1, SCAN_ROUND, SCAN_ROUND + 1 points: k_rev_scan walks one count per point (the last full round of ordered_scan, and
+# the first count of a second one; seeds whose cloud has no ambiguous point, since a single one is more than 1e-4 of so few); the
+# full-size cloud stays last
+KNN_CLOUDS = (("uniform", 1000, 45), ("clustered", 20000, 42), ("planar", 4000, 43), ("uniform", SCAN_ROUND - 1, 46),
+              ("uniform", SCAN_ROUND, 47), ("uniform", SCAN_ROUND + 1, 50), ("uniform", 300000, 44))
 
 
 def smooth_features(points: torch.Tensor, widths, noise: float, seed: int, wavelength: float = 1.0):

@@ -28,10 +28,16 @@ def test_symbols_are_declared_exported_and_bound(lib):
 
 
 def test_workspace_is_the_layout_the_plan_carves(lib):
-    """csrc/densify.hip: launch_densify_plan puts flags [N] (one byte each), then counters [4][blocks] (uint32), then the totals,
-    each part aligned to 256 bytes; N = 0 is sized like N = 1."""
+    """csrc/densify.hip: carve_densify puts flags [N] (one byte each), then counters [4][blocks] (uint32), then the totals,
+    each part aligned to 256 bytes; N = 0 is sized like N = 1.  The sizes are written out here, not read from the library: this
+    test is what pins the layout."""
+    from tests.scan_round import SCAN_ROUND
     up = lambda v: (v + 255) // 256 * 256
     sizes = []
+    for n in (0, 1, 2, 255, 256, 257, 256 * SCAN_ROUND - 1, 256 * SCAN_ROUND, 256 * SCAN_ROUND + 1, 10 ** 6, 2 ** 31 - 256, 2 ** 31 - 1):
+        rows = max(n, 1)
+        blocks = (rows + BLOCK - 1) // BLOCK
+        assert lib.sr_densify_workspace_bytes(n) == up(rows) + up(16 * blocks) + 256, n
     for n in (0, 1, 255, 256, 257, 262_145):
         rows = max(n, 1)
         blocks = (rows + BLOCK - 1) // BLOCK

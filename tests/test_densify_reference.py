@@ -82,7 +82,7 @@ def test_every_generated_case_meets_its_conditions(name):
     for row, kinds in c.get("ties", {}).items():
         assert tuple(r64.kind[r64.source == row].tolist()) == tuple(kinds), (row, kinds)
     # the layout: the last row of a wave of 64 and the first row of the next differ in class
-    if name.startswith("boundary_") or name == "second_scan_pass":
+    if name.startswith("boundary_") or name in ("full_scan_pass", "second_scan_pass"):
         cl = c["classes"]
         assert all(cl[b] != cl[b - 1] for b in range(64, n, 64))
         assert n < 255 or set(cl[:255]) == set(R.CLASSES)

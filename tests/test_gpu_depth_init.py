@@ -13,6 +13,7 @@ import torch
 
 from tests import depth_init_reference as R
 from tests.launches import stage_counts
+from tests.scan_round import BLOCK, SCAN_ROUND
 
 pytestmark = pytest.mark.gpu
 
@@ -91,7 +92,10 @@ def bounds_of(c, **kw):
 
 # ---- every size at which the kernels take another path ---------------------------------------------------------------------
 # B H W of 1, 63, 64, 65, 255, 256, 257 and 27 300 (a partial last workgroup and more than 100 workgroups); 1 x 9 and 9 x 1
-SHAPES = [(1, 1, 1), (1, 7, 9), (1, 8, 8), (1, 5, 13), (1, 15, 17), (1, 16, 16), (1, 1, 257), (3, 130, 70), (1, 1, 9), (1, 9, 1), (2, 9, 1)]
+# SCAN_ROUND and SCAN_ROUND + 1 images of 16 x 16 pixels, one workgroup each: k_depth_scan walks one count per workgroup (a full round
+# of ordered_scan, and the first count of a second one)
+SCAN_SHAPES = [(SCAN_ROUND, 16, 16), (SCAN_ROUND + 1, 16, 16)]
+SHAPES = [(1, 1, 1), (1, 7, 9), (1, 8, 8), (1, 5, 13), (1, 15, 17), (1, 16, 16), (1, 1, 257), (3, 130, 70), (1, 1, 9), (1, 9, 1), (2, 9, 1)] + SCAN_SHAPES
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -245,14 +249,18 @@ def test_bounds_as_the_box_of_the_hull():
 
 
 # ---- select -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(3, 130, 70), (1, 5, 13)], ids=["27300", "65"])
+@pytest.mark.parametrize("shape", [(3, 130, 70), (1, 5, 13), SCAN_SHAPES[1]], ids=["27300", "65", "scan_round_plus_one"])
 def test_ranks_equal_rows_of_the_full_cloud(shape):
     c = case(*shape)
     full = run(c)
     m = len(c["idx"])
     rng = np.random.default_rng(5)
     some = np.sort(rng.choice(m, min(m, 300), replace=False))
-    for ranks in (np.arange(m), some, some[::-1].copy(), np.repeat(some[:7], 3), rng.integers(0, m, 500), [0], [m - 1], [m - 1, 0, 0, m - 1]):
+    # the survivors of the first SCAN_ROUND workgroups (the first round of k_depth_scan): its last, and the first of the second round
+    first_round = int(np.searchsorted(c["idx"], SCAN_ROUND * BLOCK))
+    assert first_round == m or 0 < first_round < m
+    across = [0, first_round - 1, min(first_round, m - 1), m - 1]
+    for ranks in (np.arange(m), some, some[::-1].copy(), np.repeat(some[:7], 3), rng.integers(0, m, 500), [0], [m - 1], [m - 1, 0, 0, m - 1], across):
         got = run(c, ranks=ranks)
         pick = torch.as_tensor(np.asarray(ranks, np.int64)).cuda()
         assert all(torch.equal(a, b[pick]) for a, b in zip(got, full)), ranks

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import hull_reference as R
+from tests.scan_round import BLOCK, SCAN_ROUND
 
 pytestmark = pytest.mark.gpu
 MARGIN = 1e-9
@@ -272,23 +273,34 @@ def test_numpy_drop_ins_return_the_reference_rows():
 
 
 # ---- points mode -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 65, 1000])
+# SCAN_ROUND and SCAN_ROUND + 1 workgroups of points: k_hull_scan walks one count per workgroup (a full round of ordered_scan, and
+# the first count of a second one); these two run the one-view case only
+@pytest.mark.parametrize("n", [1, 65, 1000, SCAN_ROUND * BLOCK, SCAN_ROUND * BLOCK + 1])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_hull_filter_equals_the_restatement(n, dtype):
     import splatfields_amd as S
+    from splatfields_amd import init as I
     rng = np.random.default_rng(100 + n)
     pts = rng.uniform(-0.8, 0.8, (n, 3)).astype(dtype)
     if n == 1:
         pts[0] = [0.05, -0.1, 0.08]
-    for name in ("g33", "v5_ragged_keep", "ndc_square"):
+    for name in ("g33", "v5_ragged_keep", "ndc_square") if n <= 1000 else ("v1",):
         c = grid_case(name)
         alive, margin = R.hull_points(pts.astype(np.float64), c["masks"], c["matrices"], c["convention"], c["outside"])
         assert margin.min() >= MARGIN
         keep = S.hull_filter(torch.from_numpy(pts), c["masks"], c["matrices"], convention=c["convention"], outside=c["outside"], device="cuda")
         assert keep.is_cuda and keep.dtype is torch.bool and keep.shape == (n,)
         assert np.array_equal(keep.cpu().numpy(), alive), name
-        if n == 1000:
+        if n >= 1000:
             assert 0 < alive.sum() < n, name
+        # the survivor list itself: the count, and every index in order
+        dev = torch.device("cuda", torch.cuda.current_device())
+        table, flat = I._view_table(c["masks"], c["matrices"], c["convention"], c["outside"], dev)
+        on_dev = torch.from_numpy(pts).to(dev)
+        ws, count = I._carve(table, flat, None, 0, on_dev, n, dev)
+        assert int(count.item()) == int(alive.sum()), name
+        idx, _ = I._gather(None, 0, on_dev, n, ws, int(count.item()), dev, want_points=False)
+        assert np.array_equal(idx.cpu().numpy(), np.nonzero(alive)[0]), name
 
 
 def test_blender_load_fixture():

@@ -5,6 +5,8 @@ import pytest
 import torch
 from scipy.spatial import cKDTree
 
+from tests.scan_round import SCAN_ROUND
+
 pytestmark = pytest.mark.gpu
 
 
@@ -30,7 +32,8 @@ def oracle_mean_dist2(pts: np.ndarray) -> np.ndarray:
 
 
 @pytest.mark.parametrize("n,kind", [(1, "uniform"), (2, "uniform"), (3, "uniform"), (5, "uniform"), (1000, "uniform"),
-                                     (20000, "clustered"), (300000, "uniform"), (5000, "duplicates"), (4000, "planar")])
+                                     (20000, "clustered"), (300000, "uniform"), (5000, "duplicates"), (4000, "planar"),
+                                     (SCAN_ROUND - 1, "uniform"), (SCAN_ROUND, "uniform"), (SCAN_ROUND + 1, "uniform")])
 def test_matches_exact_knn(hip_device, n, kind):
     from simple_knn._C import distCUDA2
     rng = np.random.default_rng(n)

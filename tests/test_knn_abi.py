@@ -36,6 +36,22 @@ def test_workspace_is_positive_256_byte_granular_and_monotone(lib):
     assert lib.sr_knn_workspace_bytes(-5) == lib.sr_knn_workspace_bytes(0)
 
 
+def test_workspace_sizes_follow_the_layout(lib):
+    """csrc/knn.hip: carve_knn puts the bounds (8 floats), three arrays of max(n, 2) + 1 uint32 (cell counts, starts, cursors), the
+    n points cell after cell (uint32; n = 0 is sized like n = 1) and, for the graph, its n k reverse edges (uint32), each part
+    aligned to 256 bytes.  The sizes are written out here, not read from the library: this test is what pins the layout."""
+    from tests.scan_round import SCAN_ROUND
+    up = lambda v: (v + 255) // 256 * 256
+    grid = (0, 1, 2, 255, 256, 257, 256 * SCAN_ROUND - 1, 256 * SCAN_ROUND, 256 * SCAN_ROUND + 1, 10 ** 6)
+    for n in grid + (2 ** 31 - 1,):
+        assert lib.sr_knn_workspace_bytes(n) == 256 + 3 * up(4 * (max(n, 2) + 1)) + up(4 * max(n, 1)), n
+    for k in range(2, 9):
+        for n in grid + (2 ** 31 - 1,):              # the size query takes any n > 0; sr_knn_graph itself stops at (2^31 - 1) / 24 points
+            want = 0 if n == 0 else 256 + 3 * up(4 * (max(n, 2) + 1)) + up(4 * n) + up(4 * n * k)
+            assert lib.sr_knn_graph_workspace_bytes(n, k) == want, (n, k)
+    assert lib.sr_knn_graph_workspace_bytes(1000, 1) == lib.sr_knn_graph_workspace_bytes(1000, 9) == 0
+
+
 def test_bad_calls_are_refused_on_the_host(lib):
     buf = (C.c_float * 1024)()
     p = C.c_void_p(C.addressof(buf))       # host memory: never dereferenced, every check comes before the launch

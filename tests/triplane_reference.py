@@ -18,6 +18,8 @@ from collections import namedtuple
 
 import torch
 
+from tests.scan_round import SCAN_ROUND
+
 AXES = ([0, 1], [1, 2], [2, 0])           # xy, yz, zx (reference scene/tripFields.py:399)
 TENSORS = ("out", "d_planes", "d_pts")
 
@@ -101,7 +103,11 @@ CASES = (
     Case("c8_1x64", 8, 1, 64, 1000, 108, False, "one row"),
     Case("c8_64x1", 8, 64, 1, 1000, 109, False, "one column"),
     Case("c16_24x24_wide", 16, 24, 24, 4099, 110, True, "probe rows scaled per point by 2^u, u uniform in [-30, 0]"),
+    # one row of 16 x 16 tiles, 3 planes x 32 counter copies = 96 bins a tile: the first tile count whose bins exceed SCAN_ROUND
+    Case(f"c4_16x{16 * (SCAN_ROUND // 96) + 1}_scan", 4, 16, 16 * (SCAN_ROUND // 96) + 1, 4099, 111, False,
+         "the bin scan's second round of ordered_scan, partial last tile"),
 )
+SCAN_CASE = CASES[-1].name
 CASE_BY_NAME = {c.name: c for c in CASES}
 
 
