@@ -3,7 +3,7 @@
 `fused_flow_head(model, hidden, pts, weights, biases, bases)` evaluates one `FlowHead` of reference utils/time_utils.py:194-304
 -- the branch linears z = hidden W^T + b of the model, and the per-point epilogue that turns z and the point into `flow` and
 `means3D` -- in ONE launch, and is differentiable: the backward is one kernel that re-derives the epilogue from the saved z
-(doubles) and writes dL/dpts, dL/dz and dL/dhidden = dz W, plus one sr_mlp_weight_grad call (two kernels) for the weight and bias
+(doubles) and writes dL/dpts, dL/dz and dL/dhidden = dz W, plus one weight_grad.run call (two kernels) for the weight and bias
 gradients of every branch.  For the two DCT models the same backward kernel leaves one partial sum of dL/dbases per workgroup
 (doubles, workgroup = 256 consecutive points, whatever the device), which a `sum(0)` adds.  float32 tensors, double arithmetic
 inside the kernels, one rounding per stored value, no atomics, no host wait: repeated calls are bit-identical.  No CPU path.
@@ -12,16 +12,15 @@ Opt-in: `FlowHead(path="fused")`, `SplatFields(flow_head="fused")`, `set_flow_he
 process default is "torch" (the PyTorch-op path of splatfields_amd/deform_field.py)."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, weight_grad
 
 FLOW_HEADS = ("torch", "fused")
-FLOW_HEAD_LAUNCHES = (1, 3)      # library kernels of the "fused" head: (forward, backward: the epilogue + sr_mlp_weight_grad's two)
+FLOW_HEAD_LAUNCHES = (1, 3)      # library kernels of the "fused" head: (forward, backward: the epilogue + weight_grad.run's two)
 # model -> (SR_FLOW_* code, rows of its branches in the order of the z layout; None = 3 * n_basis)
 MODELS = {"offset": (_lib.FLOW_OFFSET, (3,)), "se3": (_lib.FLOW_SE3, (3, 3)), "se3Affine": (_lib.FLOW_SE3_AFFINE, (3, 3, 3)),
           "se3Scaled": (_lib.FLOW_SE3_SCALED, (3, 3, 1, 3)), "affine": (_lib.FLOW_AFFINE, (9, 3)), "dct": (_lib.FLOW_DCT, (None,)),
@@ -121,8 +120,7 @@ class _FlowHeadFn(torch.autograd.Function):
         g_flow = _lib.f32c(g_flow) if g_flow is not None else None        # null: the training loop's case (nothing reads `flow`)
         rows = [w.shape[0] for w in weights]
         dz_row = lib.sr_flow_head_dz_row(code, n_basis)
-        # one row more than points: a branch's weight-gradient job reads whole rows from its own first column on
-        dz = torch.empty(n + 1, dz_row, dtype=torch.float32, device=dev)
+        dz = torch.empty(weight_grad.dz_rows(n), dz_row, dtype=torch.float32, device=dev)      # a branch's job starts at its own column
         d_hidden = torch.empty_like(hidden) if need_hidden else None
         d_pts = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_pts else None
         ws = torch.empty(lib.sr_flow_head_workspace_bytes(code, n, width, n_basis) // 8, dtype=torch.float64, device=dev)
@@ -138,48 +136,25 @@ class _FlowHeadFn(torch.autograd.Function):
             d_bases = ws[: (n + 255) // 256 * n_basis].view(-1, n_basis).sum(0).to(ctx.bases_dtype)
         dWs, dbs = [None] * nb, [None] * nb
         if need_W:
-            dWs, dbs = _branch_weight_grads(lib, hidden, dz, dz_row, weights, n)
+            dWs, dbs = _branch_weight_grads(hidden, dz, dz_row, weights, n)
             dWs = [g if ctx.needs_input_grad[6 + j] else None for j, g in enumerate(dWs)]
             dbs = [g if ctx.needs_input_grad[6 + nb + j] else None for j, g in enumerate(dbs)]
         return (None, None, None, d_hidden, d_pts, d_bases, *dWs, *dbs)
 
 
-def _branch_weight_grads(lib, hidden, dz, dz_row, weights, n):
-    """dW_b = dz_b^T hidden, db_b = sum dz_b of every branch in one sr_mlp_weight_grad call: one job per branch, whose dz
-    pointer is the branch's first column (a multiple of 4 floats) of the shared [N, dz_row] matrix.  Chunked over the points as
-    `_PointLinearFn` does it (the kernel addresses its operands with 32-bit byte offsets)."""
-    dev, width, nb = hidden.device, hidden.shape[1], len(weights)
-    jobs = (_lib.SrMlpGradJob * nb)()
-    col0 = []
-    at = 0
-    for j, w in enumerate(weights):
-        m = w.shape[0]
-        jobs[j].dz_row, jobs[j].m, jobs[j].x_row, jobs[j].k, jobs[j].dw_row, jobs[j].dw_col0 = dz_row, m, width, width, width, 0
-        col0.append(at)
-        at += (m + 3) // 4 * 4
-    n_max = max(64, ((1 << 31) - 1) // (4 * max(dz_row, width)) // 64 * 64)
-    total_W, total_b = None, None
-    for lo in range(0, n, n_max):
-        cnt = min(n_max, n - lo)
-        dWs = [torch.empty_like(w) for w in weights]
-        dbs = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in weights]
-        for j in range(nb):
-            jobs[j].dz, jobs[j].x = dz.data_ptr() + 4 * (lo * dz_row + col0[j]), hidden.data_ptr() + 4 * lo * width
-            jobs[j].dw, jobs[j].db = dWs[j].data_ptr(), dbs[j].data_ptr()
-        ws_bytes = lib.sr_mlp_weight_grad_workspace(cnt, nb, jobs)
-        if ws_bytes == 0:
-            raise ValueError("unsupported weight-gradient job list: " + lib.sr_last_error().decode("utf-8", "replace"))
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_mlp_weight_grad(cnt, nb, jobs, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
-        if total_W is None:
-            total_W, total_b = dWs, dbs
-        else:      # fixed chunk order: still deterministic
-            for a_, b_ in zip(total_W, dWs):
-                a_.add_(b_)
-            for a_, b_ in zip(total_b, dbs):
-                a_.add_(b_)
-    return total_W, total_b
+def _branch_weight_grads(hidden, dz, dz_row, weights, n):
+    """dW_b = dz_b^T hidden, db_b = sum dz_b of every branch in one weight_grad.run call: one job per branch, whose dz address is
+    the branch's first column (a multiple of 4 floats) of the shared [N, dz_row] matrix."""
+    dev, width = hidden.device, hidden.shape[1]
+    fields, dz_at, at = [], [], dz.data_ptr()
+    for w in weights:
+        fields.append((dz_row, w.shape[0], width, width, width, 0))
+        dz_at.append(at)
+        at += 4 * ((w.shape[0] + 3) // 4 * 4)
+    dWs = [torch.empty_like(w) for w in weights]
+    dbs = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in weights]
+    weight_grad.run(n, dev, weight_grad.job_list(tuple(fields)), dz_at, [hidden.data_ptr()] * len(weights), dWs, dbs)
+    return dWs, dbs
 
 
 def fused_flow_head(model: str, hidden: torch.Tensor, pts: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor],

@@ -1,5 +1,5 @@
-"""Fused MLPs of the SplatFields deform network, forward and backward (include/splatraster.h: sr_mlp_chain, sr_mlp_pack,
-sr_mlp_weight_grad; csrc/mlp.hip).
+"""Fused MLPs of the SplatFields deform network, forward and backward (include/splatraster.h: sr_mlp_chain, sr_mlp_pack;
+csrc/mlp.hip; the weight gradients through splatfields_amd/weight_grad.py).
 
 `fused_general_mlp` evaluates one `GeneralMLP` of reference utils/time_utils.py:123-191 -- `h = act(layer_i(h))` for every
 layer, `h = cat([h_in, h])` after the layers listed in `skips`, act = leaky ReLU -- for all points in one kernel
@@ -29,12 +29,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from operator import itemgetter
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, weight_grad
 
 
 PRECISIONS = ("fp32", "bf16")
@@ -316,8 +317,8 @@ def _top_gradient(lib, shape: _Shape, y, dY, slope: float, G):
     """G[:, :out] = dY * leaky'(y), zero padding behind: one launch (sr_mlp_top_gradient)"""
     dev = y.device
     with torch.cuda.device(dev):
-        _lib.check(lib.sr_mlp_top_gradient(y.shape[0], shape.out_features, shape.out_pad, C.c_void_p(y.data_ptr()), C.c_void_p(dY.data_ptr()),
-                                           slope, C.c_void_p(G.data_ptr()), _lib.stream(dev)))
+        _lib.check(lib.sr_mlp_top_gradient(y.shape[0], shape.out_features, shape.out_pad, _lib.ptr(y), _lib.ptr(dY),
+                                           slope, _lib.ptr(G), _lib.stream(dev)))
 
 
 def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input: bool, signs=None, precision: str = "fp32"):
@@ -338,66 +339,39 @@ def _backward(shape: _Shape, x0, acts, y, dY, weights, slope: float, need_input:
 
 
 def _grad_jobs(shape: _Shape):
-    """static part of the weight-gradient job list: (layer, dz symbol, dz_row, m, x symbol, x_row, k, dw_row, dw_col0, first)"""
+    """static part of the weight-gradient job list: (its JobList, then per job as itemgetters: dz and x out of the addresses
+    [G, x0, dz_0.., acts_0..], dw out of the layers' dW, db out of [the layers' db.., None]: the first job of a layer carries it)"""
     if "grad" not in shape.plans:
-        H, L, out = shape.hidden, shape.n_layers, []
+        H, L, fields, picks = shape.hidden, shape.n_layers, [], []
         for j in range(L):
-            top = j == L - 1
-            dz_sym, dz_row, m = (("G", 0), shape.out_pad, shape.out_features) if top else (("dz", j), H, H)
-            col0, first = 0, True
+            dz_at, dz_row, m = (0, shape.out_pad, shape.out_features) if j == L - 1 else (2 + j, H, H)
+            col0 = 0
             segments = []
             if shape.reads_input[j]:
-                segments.append((("x0", 0), shape.mem_pad, shape.d_in))
+                segments.append((1, shape.mem_pad, shape.d_in))
             if j > 0:
-                segments.append((("acts", j - 1), H, H))
-            for x_sym, x_row, k in segments:
-                out.append((j, dz_sym, dz_row, m, x_sym, x_row, k, shape.layer_dims[j][1], col0, first))
+                segments.append((L + j, H, H))
+            for x_at, x_row, k in segments:
+                fields.append((dz_row, m, x_row, k, shape.layer_dims[j][1], col0))
+                picks.append((dz_at, x_at, j, j if col0 == 0 else L))
                 col0 += k
-                first = False
-        if len(out) > _lib.MLP_MAX_GRAD_JOBS:
-            raise ValueError("network too deep for one weight-gradient launch")
-        arr = (_lib.SrMlpGradJob * len(out))()
-        for i, (j, _, dz_row, m, _, x_row, k, dw_row, col0, _) in enumerate(out):
-            arr[i].dz_row, arr[i].m, arr[i].x_row, arr[i].k, arr[i].dw_row, arr[i].dw_col0 = dz_row, m, x_row, k, dw_row, col0
-        shape.plans["grad"] = (out, arr, threading.Lock())
+        jobs = weight_grad.JobList(fields)      # raises for a network too deep for one launch
+        shape.plans["grad"] = (jobs, *[itemgetter(*column) for column in zip(*picks)])
     return shape.plans["grad"]
 
 
 def _weight_grads(shape: _Shape, x0, acts, G, dz, weights):
-    """dW_j = dZ_j^T [h_in | h_{j-1}], db_j = sum over points of dZ_j, all layers in one launch (sr_mlp_weight_grad).  The kernel
-    addresses its operands with 32-bit byte offsets: larger point sets are cut into chunks whose partial gradients are added
-    (a reference-sized network reaches that limit at ~2.4 M points)."""
-    lib = _lib.load()
+    """dW_j = dZ_j^T [h_in | h_{j-1}], db_j = sum over points of dZ_j, all layers in one launch: one job per column block of a dW
+    (the input segment, the hidden segment), the bias on the first (weight_grad.run; a reference-sized network reaches its chunk
+    limit at ~2.4 M points)."""
     dev, n, H, L = x0.device, x0.shape[0], shape.hidden, shape.n_layers
-    jobs, arr, lock = _grad_jobs(shape)
-    row_bytes = 4 * max(shape.mem_pad, shape.out_pad, H)
-    n_max = max(64, ((1 << 31) - 1) // row_bytes // 64 * 64)
-    total_W, total_b = None, None
-    for lo in range(0, n, n_max):
-        cnt = min(n_max, n - lo)
-        dWs = [torch.empty_like(W) for W in weights]
-        dbs = [torch.empty(W.shape[0], dtype=torch.float32, device=dev) for W in weights]
-        base = {"G": (G.data_ptr() + 4 * lo * shape.out_pad,), "x0": (x0.data_ptr() + 4 * lo * shape.mem_pad,),
-                "dz": [dz.data_ptr() + 4 * (j * n + lo) * H for j in range(L - 1)],
-                "acts": [acts.data_ptr() + 4 * (j * n + lo) * H for j in range(L - 1)]}
-        with lock:
-            for i, (j, dz_sym, _, _, x_sym, _, _, _, _, first) in enumerate(jobs):
-                arr[i].dz, arr[i].x = base[dz_sym[0]][dz_sym[1]], base[x_sym[0]][x_sym[1]]
-                arr[i].dw, arr[i].db = dWs[j].data_ptr(), (dbs[j].data_ptr() if first else None)
-            ws_bytes = lib.sr_mlp_weight_grad_workspace(cnt, len(jobs), arr)
-            if ws_bytes == 0:
-                raise ValueError("unsupported weight-gradient job list: " + lib.sr_last_error().decode("utf-8", "replace"))
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.sr_mlp_weight_grad(cnt, len(jobs), arr, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
-        if total_W is None:
-            total_W, total_b = dWs, dbs
-        else:      # fixed chunk order: still deterministic
-            for a_, b_ in zip(total_W, dWs):
-                a_.add_(b_)
-            for a_, b_ in zip(total_b, dbs):
-                a_.add_(b_)
-    return total_W, total_b
+    jobs, pick_dz, pick_x, pick_dw, pick_db = _grad_jobs(shape)
+    dWs = [torch.empty_like(W) for W in weights]
+    dbs = [torch.empty(W.shape[0], dtype=torch.float32, device=dev) for W in weights]
+    dz0, acts0 = dz.data_ptr(), acts.data_ptr()
+    at = [G.data_ptr(), x0.data_ptr(), *[dz0 + 4 * j * n * H for j in range(L - 1)], *[acts0 + 4 * j * n * H for j in range(L - 1)]]
+    weight_grad.run(n, dev, jobs, pick_dz(at), pick_x(at), pick_dw(dWs), pick_db(dbs + [None]))
+    return dWs, dbs
 
 
 class _FusedMLPFn(torch.autograd.Function):
@@ -452,9 +426,8 @@ class _FusedMLPPointsFn(torch.autograd.Function):
         n_feat = 0 if f32 is None else f32.shape[1]
         x0 = torch.empty(n, shape.mem_pad, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.sr_mlp_input_forward(n, multires, n_feat, time_multires, shape.mem_pad, C.c_void_p(x32.data_ptr()),
-                                                C.c_void_p(f32.data_ptr()) if f32 is not None else None,
-                                                C.c_void_p(t32.data_ptr()) if t32 is not None else None, C.c_void_p(x0.data_ptr()), _lib.stream(dev)))
+            _lib.check(lib.sr_mlp_input_forward(n, multires, n_feat, time_multires, shape.mem_pad, _lib.ptr(x32), _lib.ptr(f32),
+                                                _lib.ptr(t32), _lib.ptr(x0), _lib.stream(dev)))
         need = grad_enabled and any(ctx.needs_input_grad)
         y, acts, signs = _forward(shape, x0, weights, biases, slope, save=need, precision=precision)
         if need:
@@ -476,9 +449,8 @@ class _FusedMLPPointsFn(torch.autograd.Function):
         d_feat = torch.empty(n, ctx.n_feat, dtype=torch.float32, device=dev) if need_feat else None
         if need_xyz or need_feat:
             with torch.cuda.device(dev):
-                _lib.check(lib.sr_mlp_input_backward(n, ctx.multires, ctx.n_feat, shape.mem_pad, C.c_void_p(x32.data_ptr()),
-                                                     C.c_void_p(dx0.data_ptr()), C.c_void_p(d_xyz.data_ptr()) if need_xyz else None,
-                                                     C.c_void_p(d_feat.data_ptr()) if need_feat else None, _lib.stream(dev)))
+                _lib.check(lib.sr_mlp_input_backward(n, ctx.multires, ctx.n_feat, shape.mem_pad, _lib.ptr(x32), _lib.ptr(dx0),
+                                                     _lib.ptr(d_xyz), _lib.ptr(d_feat), _lib.stream(dev)))
         dWs, dbs = [None] * L, [None] * L
         if any(ctx.needs_input_grad[9:]):
             dWs, dbs = _weight_grads(shape, x0, acts, G, dz, weights)
@@ -553,7 +525,7 @@ class _PointLinearFn(torch.autograd.Function):
     weight are library GEMMs, but dL/dW = dY^T x and dL/db = column sums of dY contract over the POINTS -- the shape library
     GEMMs and reductions serialise (0.29 ms per 48 x 48 x 100k product and 0.14 ms per bias on MI355X; the tri-plane refine MLP
     and the flow head were 1.4 ms of an 8.5 ms network step) -- and go through the slab kernel of the fused MLPs
-    (sr_mlp_weight_grad: deterministic, ~0.03 ms)."""
+    (weight_grad.run with one job, dY padded to a multiple of 4 columns: deterministic, ~0.03 ms)."""
 
     @staticmethod
     def forward(ctx, x, W, b):
@@ -564,7 +536,6 @@ class _PointLinearFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dY):
-        lib = _lib.load()
         x, W = ctx.saved_tensors
         dev, n, m, k = x.device, x.shape[0], W.shape[0], W.shape[1]
         need_x, need_W = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -577,23 +548,7 @@ class _PointLinearFn(torch.autograd.Function):
             dz = dY if m_pad == m else F.pad(dY, (0, m_pad - m))
             dW = torch.empty_like(W)
             db = torch.empty(m, dtype=torch.float32, device=dev)
-            job = (_lib.SrMlpGradJob * 1)()
-            job[0].dz_row, job[0].m, job[0].x_row, job[0].k, job[0].dw_row, job[0].dw_col0 = m_pad, m, k, k, k, 0
-            n_max = max(64, ((1 << 31) - 1) // (4 * max(m_pad, k)) // 64 * 64)
-            for lo in range(0, n, n_max):
-                cnt = min(n_max, n - lo)
-                pW, pb = (dW, db) if lo == 0 else (torch.empty_like(W), torch.empty_like(db))
-                job[0].dz, job[0].x = dz.data_ptr() + 4 * lo * m_pad, x.data_ptr() + 4 * lo * k
-                job[0].dw, job[0].db = pW.data_ptr(), pb.data_ptr()
-                ws_bytes = lib.sr_mlp_weight_grad_workspace(cnt, 1, job)
-                if ws_bytes == 0:
-                    raise ValueError("unsupported weight-gradient job: " + lib.sr_last_error().decode("utf-8", "replace"))
-                ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-                with torch.cuda.device(dev):
-                    _lib.check(lib.sr_mlp_weight_grad(cnt, 1, job, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
-                if lo:
-                    dW.add_(pW)
-                    db.add_(pb)
+            weight_grad.run(n, dev, weight_grad.job_list(((m_pad, m, k, k, k, 0),)), [dz.data_ptr()], [x.data_ptr()], [dW], [db])
         return dX, (dW if need_W else None), (db if need_b else None)
 
 
@@ -635,7 +590,7 @@ class FusedGeneralMLP:
 # Several GeneralMLPs that read the same (xyz, features, time) run through ONE autograd function: one input kernel, one output
 # kernel, one top-gradient kernel and one input-backward kernel for all of them, and per group of nets of one hidden width and
 # precision one pack launch and one chain launch per direction (include/splatraster.h: sr_mlp_chain_group, sr_mlp_group_*; DESIGN.md
-# section 20).  Weight gradients stay one sr_mlp_weight_grad call per net.
+# section 20).  Weight gradients stay one _weight_grads call per net.
 
 HEADS = ("separate", "grouped")
 OUT_ACTIVATIONS = {"none": _lib.MLP_OUT_NONE, "sigmoid": _lib.MLP_OUT_SIGMOID, "normalize": _lib.MLP_OUT_NORMALIZE}
@@ -928,7 +883,7 @@ class _GroupedHeadsFn(torch.autograd.Function):
         if need_input:
             _group_input_backward(lib, heads_, ctx.n_feat, x32, dx0s, d_xyz, d_feat)
         grads, at = [], 5
-        for i, h in enumerate(heads_):       # weight and bias gradients: sr_mlp_weight_grad per net, unchanged
+        for i, h in enumerate(heads_):       # weight and bias gradients: one slab-kernel call per net, unchanged
             L = h.shape.n_layers
             want = ctx.needs_input_grad[at:at + 2 * L]
             if any(want):

@@ -19,7 +19,6 @@ Supported: the configurations `SplatFields` constructs (utils/time_utils.py:343-
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
@@ -94,7 +93,7 @@ class _ResFieldCompose(torch.autograd.Function):
             jobs[j].w, jobs[j].weights_t, jobs[j].matrix_t, jobs[j].out = Ws[j].data_ptr(), wts[j].data_ptr(), Ms[j].data_ptr(), outs[j].data_ptr()
             jobs[j].count, jobs[j].rank, jobs[j].capacity = Ws[j].numel(), wts[j].shape[1], wts[j].shape[0]
         with torch.cuda.device(dev):
-            _lib.check(lib.sr_resfield_compose(n, jobs, C.c_void_p(frame.data_ptr()), _lib.stream(dev)))
+            _lib.check(lib.sr_resfield_compose(n, jobs, _lib.ptr(frame), _lib.stream(dev)))
         ctx.save_for_backward(frame, *wts, *Ms)
         ctx.n = n
         return tuple(outs)
@@ -121,7 +120,7 @@ class _ResFieldCompose(torch.autograd.Function):
             raise ValueError("unsupported ResField job list")
         ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.sr_resfield_backward(n, jobs, C.c_void_p(frame.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
+            _lib.check(lib.sr_resfield_backward(n, jobs, _lib.ptr(frame), _lib.ptr(ws), ws_bytes, _lib.stream(dev)))
         grads = [None]
         for j in range(n):       # dL/dW is dL/dW_eff itself
             grads += [gouts[j] if ctx.needs_input_grad[1 + 3 * j] else None, d_wts[j], d_Ms[j]]

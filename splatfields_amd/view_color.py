@@ -8,7 +8,7 @@ gaussian_renderer/__init__.py:43-46 evaluates once per view around utils/time_ut
 -- for ALL V views of a step in ONE launch that reads the [N, F] feature once, and is differentiable: the backward is one kernel
 that writes dL/dfeature once (the sum over the views times W[:, :F]), dL/dmeans3D (summed in view order), the per-point sum of
 dL/dz and one partial sum of dW[:, F:] and db per workgroup (doubles, workgroup = 256 consecutive points, whatever the device), plus
-one sr_mlp_weight_grad call (two kernels) for dW[:, :F].  With `dirs=[V, N, 3]` instead of the camera centres the directions
+one weight_grad.run call (two kernels) for dW[:, :F].  With `dirs=[V, N, 3]` instead of the camera centres the directions
 are taken as given and receive the gradient (V = 1: the reference's `rgb_fnc(viewdir)`).  float32 tensors, double arithmetic
 inside the kernels, one rounding per stored value, no atomics, no host wait: repeated calls are bit-identical.  No CPU path.
 The one limit: a point that coincides with a camera centre gives non-finite values in that view, as in the reference.
@@ -20,16 +20,15 @@ Opt-in: `SplatFields(view_color="fused")`, `set_view_color("fused")` or SPLATFIE
 "torch" (the PyTorch ops of splatfields_amd/deform_field.py and render.py)."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, weight_grad
 
 VIEW_COLORS = ("torch", "fused")
-VIEW_COLOR_LAUNCHES = (1, 3)     # library kernels of the "fused" head for up to 16 views: (forward, backward: its own + sr_mlp_weight_grad's two)
+VIEW_COLOR_LAUNCHES = (1, 3)     # library kernels of the "fused" head for up to 16 views: (forward, backward: its own + weight_grad.run's two)
 
 
 def checked_view_color(name) -> str:
@@ -109,8 +108,7 @@ class _ViewColorFn(torch.autograd.Function):
         ws_bytes = lib.sr_view_color_workspace_bytes(n, width, 1)
         total = None
         for lo, hi in _chunks(n_views):
-            # one row more than points, as every dL/dz matrix handed to sr_mlp_weight_grad (include/splatraster.h)
-            dz = torch.empty(n + 1, 4, dtype=torch.float32, device=dev)
+            dz = torch.empty(weight_grad.dz_rows(n), 4, dtype=torch.float32, device=dev)      # the kernel's layout: [N + 1, 4]
             d_feature = torch.empty_like(feature) if need_feature else None
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
             if mode == _lib.VIEW_FROM_CAMERAS:
@@ -133,7 +131,7 @@ class _ViewColorFn(torch.autograd.Function):
         dz, d_feature, ws = total
         d_weight, d_bias = None, None
         if need_weight or need_bias:
-            d_weight = _weight_grads(lib, feature, dz, n)
+            d_weight = _weight_grads(feature, dz, n)
             # one partial per workgroup of 256 consecutive points: the shape alone fixes the order of this sum
             sums = ws[: blocks * 12].view(blocks, 12).sum(0)
             d_weight[:, width:] = sums[:9].view(3, 3)
@@ -141,31 +139,14 @@ class _ViewColorFn(torch.autograd.Function):
         return (None, None, d_feature, d_weight if need_weight else None, d_bias if need_bias else None, d_pos, None)
 
 
-def _weight_grads(lib, feature, dz, n):
-    """dW[:, :F] = dz^T feature written into a [3, F + 3] matrix (the job's dw_row addresses it directly), in one
-    sr_mlp_weight_grad call.  Chunked over the points as `flow_head._branch_weight_grads` does it (the kernel addresses its
-    operands with 32-bit byte offsets)."""
-    dev, width = feature.device, feature.shape[1]
-    jobs = (_lib.SrMlpGradJob * 1)()
-    jobs[0].dz_row, jobs[0].m, jobs[0].x_row, jobs[0].k, jobs[0].dw_row, jobs[0].dw_col0 = 4, 3, width, width, width + 3, 0
-    n_max = max(64, ((1 << 31) - 1) // (4 * width) // 64 * 64)
-    total_W = None
-    for lo in range(0, n, n_max):
-        cnt = min(n_max, n - lo)
-        dW = torch.empty(3, width + 3, dtype=torch.float32, device=dev)
-        jobs[0].dz, jobs[0].x = dz.data_ptr() + 16 * lo, feature.data_ptr() + 4 * lo * width
-        jobs[0].dw, jobs[0].db = dW.data_ptr(), None
-        ws_bytes = lib.sr_mlp_weight_grad_workspace(cnt, 1, jobs)
-        if ws_bytes == 0:
-            raise ValueError("unsupported weight-gradient job list: " + lib.sr_last_error().decode("utf-8", "replace"))
-        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sr_mlp_weight_grad(cnt, 1, jobs, C.c_void_p(ws.data_ptr()), ws_bytes, _lib.stream(dev)))
-        if total_W is None:
-            total_W = dW
-        else:      # fixed chunk order: still deterministic
-            total_W[:, :width].add_(dW[:, :width])
-    return total_W
+def _weight_grads(feature, dz, n):
+    """dW[:, :F] = dz^T feature written into a [3, F + 3] matrix (the job's dw_row addresses it directly) by one weight_grad.run
+    job; the columns behind F are left as allocated, for the caller to fill."""
+    width = feature.shape[1]
+    dW = torch.empty(3, width + 3, dtype=torch.float32, device=feature.device)
+    weight_grad.run(n, feature.device, weight_grad.job_list(((4, 3, width, width, width + 3, 0),)), [dz.data_ptr()], [feature.data_ptr()],
+                    [dW], [None])
+    return dW
 
 
 def fused_view_color(feature: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, means3D: Optional[torch.Tensor] = None,
