@@ -21,6 +21,9 @@
  *   sr_backward
  *        <- [EXT] `_C.rasterize_gaussians_backward(...)`, reached from autograd when
  *           reference train.py:252 runs `loss.backward()`.
+ *   sr_forward_prepare_views + sr_forward_render_views, sr_sum_views
+ *        <- the loop of reference train.py:158-177 around those two (up to `num_views` views per iteration, one backward):
+ *           the forward of all views with one host wait, and the sum autograd forms of the views' gradients of a shared input.
  *   sr_mark_visible
  *        <- [EXT] `_C.mark_visible(...)` (`GaussianRasterizer.markVisible`; never called by
  *           SplatFields, exported for completeness).
@@ -217,6 +220,46 @@ long long sr_last_long_tiles(void);
  * have: a wrong expectation costs time, never a result.  Returns 0. */
 int sr_expect_long_tiles(long long tiles);
 int sr_ticket_release(void* ticket);
+
+/* The forward of the n_views views of one training step (reference train.py:158-177 renders up to `num_views` views and
+ * back-propagates once) in two calls with ONE host wait between them.  Every table has n_views entries: `views` and `splats`
+ * are arrays of the structs themselves, the others arrays of what the one-view entries take.
+ *   sr_forward_prepare_views  launches stage 1 of every view back to back, each with a status block of its own from the ticket
+ *       pool, then waits once on the host -- for the last view's block first, by which time the others have long arrived -- and
+ *       returns per view the instance count, the longest tile list and the number of tiles that can hold a list of more than 2048
+ *       entries (what sr_forward learns by waiting, and sr_last_longest_list / sr_last_long_tiles report).  It counts as one
+ *       host wait in sr_debug_counters.  The blocks go back to the pool on every path, with sr_forward_async's rule for a failed
+ *       launch (the stream is drained first) and sr_ticket_wait's for figures that never arrive (that block is not reused).
+ *   sr_forward_render_views   launches stage 2 of every view with those figures: binning buffers of capacities[v] >= the
+ *       view's instance count (sr_binning_bytes(capacities[v])), and exactly the sort classes a waiting sr_forward launches
+ *       for a longest list of longest[v] on a view with long_tiles[v] such tiles.  It never waits.  out_alpha, or any of its
+ *       entries, may be NULL.  Pass capacities[v] as `instances` and the view's count as `instances_rendered` to sr_backward.
+ * Outputs, state buffers and gradients of a view are bit for bit those of sr_forward / sr_backward on that view. */
+int sr_forward_prepare_views(int n_views, const SrView* views, const SrSplats* splats, void* const* geoms, int* const* radii,
+                             long long* instances_out, long long* longest_out, long long* long_tiles_out, void* hip_stream);
+int sr_forward_render_views(int n_views, const SrView* views, const SrSplats* splats, void* const* geoms, void* const* binnings,
+                            const long long* capacities, const long long* longest, const long long* long_tiles, void* const* images,
+                            float* const* out_color, float* const* out_depth, float* const* out_alpha, void* hip_stream);
+
+/* The sum over the views of a step of the gradients of the inputs the views share, ONE launch for every tensor: job j has
+ * n_views source tensors of `elems` floats, view v at src + v * view_stride, and writes
+ *   dst[i] = ((src[V-1][i] + src[V-2][i]) + ...) + src[0][i]                                      (float32, V = n_views)
+ * -- the left fold from the LAST view to the first: the order in which autograd accumulates the gradients of V rasterizer
+ * nodes that share an input (it runs the node created last first), so the sum has the bits of the per-view loop's.
+ * dst overlaps no source and no other job's dst.  All bases are 4-byte aligned; where dst, src and 4 * view_stride agree modulo 16 the body moves as 16-byte vectors
+ * and only the unaligned head and tail go element by element.  elems <= 2^31 - 1.  n_views >= 1; more than SR_SUM_MAX_VIEWS
+ * views are folded by chained launches of at most that many each, the partial sum being the first operand of the next: the
+ * association does not change.  n_jobs = 0 and jobs of 0 elements are valid and launch nothing.  The job table is the kernel
+ * argument (no copy); no LDS, no atomics, nothing waits for the device. */
+#define SR_SUM_MAX_JOBS 16
+#define SR_SUM_MAX_VIEWS 16
+typedef struct SrSumJob {
+    float* dst;
+    const float* src;
+    long long elems;
+    long long view_stride;   /* in floats */
+} SrSumJob;
+int sr_sum_views(int n_jobs, const SrSumJob* jobs, int n_views, void* hip_stream);
 
 /* Backward of both stages.  dL_ddepth / dL_dalpha may be NULL (treated as zero).  `instances` is the capacity the binning
  * buffer was rendered with; `scratch` holds sr_backward_scratch_bytes(instances) bytes.

@@ -1,6 +1,6 @@
 """MI355X-native differentiable Gaussian-splat rasterizer behind SplatFields' render() boundary."""
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
-from .render import render  # noqa: F401
+from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians, rasterize_views  # noqa: F401
+from .render import render, render_views  # noqa: F401
 from .losses import (centered_position_norm, depth_l1_loss, l1_loss, opacity_regularizer, photometric_loss, position_norm,  # noqa: F401
                      splat_regularizers, ssim, training_objective)
 from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401

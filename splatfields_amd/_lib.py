@@ -79,6 +79,10 @@ class SrAdamJob(C.Structure):
                 ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
 
 
+class SrSumJob(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("elems", C.c_longlong), ("view_stride", C.c_longlong)]
+
+
 class SrNetAdamSlot(C.Structure):
     _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("count", C.c_longlong),
                 ("chunk_end", C.c_longlong)]
@@ -126,6 +130,7 @@ MLP_MAX_GRAD_JOBS, MLP_MAX_GRAD_TASKS = 16, 128
 MLP_MAX_PACK_JOBS = 32
 MORAN_MAX_TENSORS, KNN_MAX_K = 8, 8                          # include/splatraster.h: SR_MORAN_MAX_TENSORS, SR_KNN_MAX_K
 ADAM_MAX_TENSORS = 32                                        # include/splatraster.h: SR_ADAM_MAX_TENSORS
+SUM_MAX_JOBS, SUM_MAX_VIEWS = 16, 16                          # include/splatraster.h: SR_SUM_MAX_JOBS, SR_SUM_MAX_VIEWS
 NET_ADAM_MAX_GRADS = 480                                     # include/splatraster.h: SR_NET_ADAM_MAX_GRADS
 QUANT_NONE, QUANT_PNG, QUANT_TO8B = 0, 1, 2                     # include/splatraster.h: SR_QUANT_*
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
@@ -152,6 +157,12 @@ SYMBOLS = {
                                    C.c_void_p]),
     "sr_ticket_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sr_ticket_release": (C.c_int, [C.c_void_p]),
+    "sr_forward_prepare_views": (C.c_int, [C.c_int, C.POINTER(SrView), C.POINTER(SrSplats), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "sr_forward_render_views": (C.c_int, [C.c_int, C.POINTER(SrView), C.POINTER(SrSplats), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
+    "sr_sum_views": (C.c_int, [C.c_int, C.POINTER(SrSumJob), C.c_int, C.c_void_p]),
     "sr_last_longest_list": (C.c_longlong, []),
     "sr_last_long_tiles": (C.c_longlong, []),
     "sr_expect_long_tiles": (C.c_int, [C.c_longlong]),

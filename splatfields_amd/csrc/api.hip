@@ -475,6 +475,74 @@ int sr_expect_long_tiles(long long tiles) { g_expect_long_tiles = tiles < 0 ? -1
 
 int sr_ticket_release(void* ticket) { return sr_ticket_wait(ticket, nullptr, nullptr); }
 
+int sr_forward_prepare_views(int n_views, const SrView* views, const SrSplats* splats, void* const* geoms, int* const* radii,
+                             long long* instances_out, long long* longest_out, long long* long_tiles_out, void* hip_stream) {
+    if (n_views < 1) return fail("sr_forward_prepare_views: n_views must be at least 1");
+    if (!views || !splats || !geoms || !radii || !instances_out || !longest_out || !long_tiles_out)
+        return fail("null table in sr_forward_prepare_views");
+    // everything is validated before the first launch: a refused call has launched nothing and holds no block
+    std::vector<Call> calls((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        SR_TRY(open_call(calls[v], CallContext{&views[v], &splats[v], "snapshot_fw.dump"}, hip_stream));
+        if (views[v].image_height != views[0].image_height || views[v].image_width != views[0].image_width || splats[v].count != splats[0].count)
+            return fail("sr_forward_prepare_views: the views of one call share the image size and the splat count (view " + std::to_string(v) + ")");
+        if (!geoms[v] || (splats[v].count > 0 && !radii[v])) return fail("null geom/radii in sr_forward_prepare_views (view " + std::to_string(v) + ")");
+        calls[v].carve(geoms[v], nullptr, 0, nullptr);
+    }
+    std::vector<StatusBlock*> blocks;
+    int rc = 0;
+    for (int v = 0; v < n_views && !rc; ++v) {
+        StatusBlock* t = nullptr;
+        rc = ticket_acquire(&t);
+        if (rc) break;
+        blocks.push_back(t);
+        g_call = CallContext{&views[v], &splats[v], "snapshot_fw.dump"};   // the debug snapshot of a failed stage names this view
+        rc = launch_stage1(&views[v], calls[v].v, calls[v].s, calls[v].g, radii[v], t->pinned_dev, status_block_arm(*t, calls[v].st), calls[v].st);
+    }
+    if (rc) {   // nothing of this call may still write a block when it is handed out again (sr_forward_async's rule)
+        (void)hipStreamSynchronize(static_cast<hipStream_t>(hip_stream));
+        for (StatusBlock* t : blocks) ticket_recycle(t);
+        return rc;
+    }
+    g_counters[0].fetch_add(1, std::memory_order_relaxed);   // one wait: the stream is in order, the last view's figures arrive last
+    for (int v = n_views - 1; v >= 0; --v) {
+        StatusBlock* t = blocks[(size_t)v];
+        if (rc) continue;   // figures that never arrived: neither this block nor the ones not yet looked at are reused (sr_ticket_wait)
+        rc = status_block_wait(*t, nullptr);
+        if (rc) continue;
+        instances_out[v] = (long long)t->pinned[0];
+        longest_out[v] = (long long)t->pinned[1];
+        long_tiles_out[v] = (long long)t->pinned[4];
+        ticket_recycle(t);
+    }
+    return rc;
+}
+
+int sr_forward_render_views(int n_views, const SrView* views, const SrSplats* splats, void* const* geoms, void* const* binnings,
+                            const long long* capacities, const long long* longest, const long long* long_tiles, void* const* images,
+                            float* const* out_color, float* const* out_depth, float* const* out_alpha, void* hip_stream) {
+    if (n_views < 1) return fail("sr_forward_render_views: n_views must be at least 1");
+    if (!views || !splats || !geoms || !binnings || !capacities || !longest || !long_tiles || !images || !out_color || !out_depth)
+        return fail("null table in sr_forward_render_views");
+    std::vector<Call> calls((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        const std::string at = " (view " + std::to_string(v) + ")";
+        SR_TRY(open_call(calls[v], CallContext{&views[v], &splats[v], "snapshot_fw.dump"}, hip_stream));
+        if (!geoms[v] || !binnings[v] || !images[v] || !out_color[v] || !out_depth[v]) return fail("null buffer in sr_forward_render_views" + at);
+        if (!capacity_in_range(capacities[v])) return fail("sr_forward_render_views: binning capacity out of range" + at);
+        if (longest[v] < 0 || long_tiles[v] < 0) return fail("sr_forward_render_views: the longest list and the long-tile count must be the figures of sr_forward_prepare_views" + at);
+        calls[v].carve(geoms[v], binnings[v], capacities[v], images[v]);
+    }
+    for (int v = 0; v < n_views; ++v) {
+        Call& c = calls[v];
+        g_call = CallContext{&views[v], &splats[v], "snapshot_fw.dump"};
+        // the figures are known: nobody waits, and launch_sort_tiles takes them as sr_forward's wait would have delivered them
+        SR_TRY(launch_stage2(&views[v], c.v, c.s, c.g, c.b, c.im, out_color[v], out_depth[v], out_alpha ? out_alpha[v] : nullptr, nullptr,
+                             longest[v], longest[v], long_tiles[v], c.st));
+    }
+    return 0;
+}
+
 int sr_debug_counters(long long* out4, int reset) {
     if (!out4) return fail("null pointer in sr_debug_counters");
     for (int i = 0; i < 4; ++i) out4[i] = reset ? g_counters[i].exchange(0, std::memory_order_relaxed) : g_counters[i].load(std::memory_order_relaxed);

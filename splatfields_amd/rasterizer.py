@@ -654,6 +654,164 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      torch.is_grad_enabled())
 
 
+# ---- the V views of a step in one call (include/splatraster.h: sr_forward_prepare_views / _render_views / sr_sum_views) ----------
+# The reference renders up to `num_views` views per iteration and back-propagates once (train.py:158-177, :252).  A loop over
+# `rasterize_gaussians` pays per view one host wait for the instance count, and in the backward one autograd add per shared
+# input.  Here stage 1 of every view is launched back to back and the host waits ONCE for all the figures, stage 2 of every
+# view follows with buffers that fit exactly, and the backward adds the per-view gradients of the shared inputs in one launch,
+# in autograd's own order (last view first): outputs and gradients have the bits of the loop's.  The figures are known before
+# stage 2, so the learned estimates, the tickets of the asynchronous launch and the mask shortcut play no part.
+
+def _table(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+def _pad4(count: int) -> int:
+    return (count + 3) // 4 * 4
+
+
+class _RasterizeViews(torch.autograd.Function):
+    """`_RasterizeGaussians` for V views that share the splats: means2D [V,N,3]; colors_precomp [N,3] (shared) or [V,N,3]."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
+                grad_mode: bool = True):
+        lib = _lib.load()
+        V = len(settings_list)
+        per_view_colors = colors_precomp is not None and colors_precomp.dim() == 3
+        if per_view_colors and (colors_precomp.shape[0] != V or tuple(colors_precomp.shape[1:]) != (means3D.shape[0], 3)):
+            raise RuntimeError(f"per-view colors_precomp must be [V,N,3] = {(V, means3D.shape[0], 3)}, got {tuple(colors_precomp.shape)}")
+        means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, _, sh_coeffs = _check_inputs(
+            means3D, sh, None if per_view_colors else colors_precomp, opacities, scales, rotations, cov3Ds_precomp, None, None, None)
+        dev, n = means3D.device, means3D.shape[0]
+        if per_view_colors:
+            col_c = _f32c(colors_precomp, dev) if n > 0 else None
+        if n > 0 and (sh_c is None) == (col_c is None):
+            raise RuntimeError("Please provide excatly one of either SHs or precomputed colors!")
+        if tuple(means2D.shape) != (V, n, 3):
+            raise RuntimeError(f"means2D must be [V,N,3] = {(V, n, 3)}, got {tuple(means2D.shape)}")
+        H, W = int(settings_list[0].image_height), int(settings_list[0].image_width)
+        packs = [_ViewPack.get(rs, dev, sh_coeffs) for rs in settings_list]
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+        color, depth, alpha, radii = new(V, 3, H, W), new(V, 1, H, W), new(V, 1, H, W), new(V, n, dtype=torch.int32)
+        raw_params = 0
+        if not grad_mode or not any(ctx.needs_input_grad[:8]):
+            raw_params = _lib.SR_FORWARD_ONLY   # nothing will differentiate this forward: skip what only the backward reads
+        ctx.V, ctx.n, ctx.HW, ctx.raw_params, ctx.per_view_colors = V, n, (H, W), raw_params, per_view_colors
+        ctx.opac_shape = tuple(opacities.shape)
+        ctx.in_dtypes = [None if t is None else t.dtype for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(radii)
+        if n == 0:
+            for v, pack in enumerate(packs):
+                color[v] = pack.bg.reshape(3, 1, 1)
+            depth.zero_()
+            alpha.zero_()
+            ctx.save_for_backward()
+            return color, radii, depth, alpha
+
+        with torch.cuda.device(dev):
+            stream = _lib.stream(dev)
+            geom_bytes, image_bytes = (-(-b // 256) * 256 for b in (lib.sr_geom_bytes(n, H, W), lib.sr_image_bytes(H, W)))
+            geom, image = new(V, geom_bytes, dtype=torch.uint8), new(V, image_bytes, dtype=torch.uint8)
+            views = _table(_lib.SrView, [p.struct for p in packs])
+            splats = _table(_lib.SrSplats, [_splats_struct(n, means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c,
+                                                           col_c[v] if per_view_colors else col_c, raw_params) for v in range(V)])
+            geoms = _table(C.c_void_p, [geom[v].data_ptr() for v in range(V)])
+            inst, longest, long_tiles = ((C.c_longlong * V)() for _ in range(3))
+            # stage 1 of every view, then the one host wait of this call
+            _lib.check(lib.sr_forward_prepare_views(V, views, splats, geoms, _table(C.c_void_p, [radii[v].data_ptr() for v in range(V)]),
+                                                    inst, longest, long_tiles, stream))
+            instances = [int(i) for i in inst]
+            capacities = [_round_capacity(i) for i in instances]
+            binning = [new(lib.sr_binning_bytes(c, H, W), dtype=torch.uint8) for c in capacities]
+            rows = lambda t: _table(C.c_void_p, [t[v].data_ptr() for v in range(V)])
+            _lib.check(lib.sr_forward_render_views(V, views, splats, geoms, _table(C.c_void_p, [b.data_ptr() for b in binning]),
+                                                   _table(C.c_longlong, capacities), longest, long_tiles, rows(image), rows(color),
+                                                   rows(depth), rows(alpha), stream))
+        ctx.packs, ctx.instances, ctx.capacities = packs, instances, capacities
+        ctx.sh_degree = int(settings_list[0].sh_degree)
+        ctx.save_for_backward(means3D_c, opac_c, sc_c, rot_c, cov_c, sh_c, col_c, radii, geom, image, *binning)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
+        V, n, (H, W) = ctx.V, ctx.n, ctx.HW
+        if n == 0 or (grad_color is None and grad_depth is None and grad_alpha is None):
+            return (None,) * 10
+        lib = _lib.load()
+        means3D, opac, sc, rot, cov, sh, col, radii, geom, image, *binning = ctx.saved_tensors
+        dev = means3D.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        grad_color = _f32c(grad_color, dev)
+        if grad_color is None:
+            grad_color = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)
+        grad_depth, grad_alpha = _f32c(grad_depth if _DEPTH_GRADIENT else None, dev), _f32c(grad_alpha, dev)
+        # per-view gradients of the shared inputs, view-major, every view's block on a 16-byte boundary: (name, floats per splat)
+        shared = [("means3D", 3), ("opacity", 1)] + ([("cov3D", 6)] if cov is not None else [("scales", 3), ("rotations", 4)])
+        if col is not None and not ctx.per_view_colors:
+            shared.append(("colors", 3))
+        strides = [_pad4(n * c) for _, c in shared]
+        flat = new(V * sum(strides))
+        part, at = {}, 0
+        for (name, c), stride in zip(shared, strides):
+            part[name] = (at, stride, n * c)
+            at += V * stride
+        block = lambda name, v: None if name not in part else flat.narrow(0, part[name][0] + v * part[name][1], part[name][2])
+        d_means2D = new(V, n, 3)
+        # colours of a view of its own, and the colour-gradient mode of the SH path: written in place, nothing to add
+        d_col_views = new(V, n, 3) if (ctx.per_view_colors or sh is not None) else None
+        with torch.cuda.device(dev):
+            stream = _lib.stream(dev)
+            scratch = torch.empty(lib.sr_backward_scratch_bytes(max(ctx.capacities)), dtype=torch.uint8, device=dev)
+            for v in range(V):
+                splats = _splats_struct(n, means3D, opac, sc, rot, cov, sh, col[v] if ctx.per_view_colors else col, ctx.raw_params)
+                d_col = d_col_views[v] if d_col_views is not None else block("colors", v)
+                grads = _lib.SrGrads(*map(_ptr, (block("means3D", v), d_means2D[v], block("opacity", v), block("scales", v),
+                                                 block("rotations", v), block("cov3D", v), None, d_col, None)))
+                _lib.check(lib.sr_backward(C.byref(ctx.packs[v].struct), C.byref(splats), _ptr(geom[v]), _ptr(binning[v]),
+                                           ctx.capacities[v], ctx.instances[v], _ptr(image[v]), _ptr(radii[v]), _ptr(grad_color[v]),
+                                           None if grad_depth is None else _ptr(grad_depth[v]),
+                                           None if grad_alpha is None else _ptr(grad_alpha[v]), _ptr(scratch), C.byref(grads), stream))
+            if V == 1:
+                total = {name: block(name, 0) for name in part}
+            else:   # one launch adds every shared input's V gradients, last view first: autograd's order in the per-view loop
+                total = {name: new(part[name][2]) for name in part}
+                jobs = _table(_lib.SrSumJob, [_lib.SrSumJob(total[name].data_ptr(), flat.data_ptr() + 4 * part[name][0], part[name][2],
+                                                            part[name][1]) for name in part])
+                _lib.check(lib.sr_sum_views(len(jobs), jobs, V, stream))
+        d_sh = None
+        if sh is not None:   # dL/dsh of all views from their clamp-masked colour gradients, one launch
+            from . import sh as _sh
+            campos = torch.stack([p.campos for p in ctx.packs])
+            d_sh = _sh.sh_backward(means3D, sh, campos, d_col_views, ctx.sh_degree, want_shs=True)
+        get = lambda name, *shape: total[name].reshape(*shape) if name in total else None
+        d_col = d_col_views if ctx.per_view_colors else get("colors", n, 3)
+        grads = [get("means3D", n, 3), d_means2D, d_sh, d_col, get("opacity", *ctx.opac_shape), get("scales", n, 3),
+                 get("rotations", n, 4), get("cov3D", n, 6)]
+        grads = [g_ if (g_ is None or dt is None or g_.dtype == dt) else g_.to(dt) for g_, dt in zip(grads, ctx.in_dtypes)]
+        return (*grads, None, None)
+
+
+def rasterize_views(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list):
+    """`rasterize_gaussians` for the V views of one step, which share the splats: one host wait in the forward, one launch
+    for the sum of the shared inputs' gradients in the backward.  settings_list: one GaussianRasterizationSettings per view, all
+    of one image size and SH degree.  means2D [V,N,3] (its gradient: row v is view v's dL/dmeans2D); colors_precomp [N,3],
+    shared by the views, or [V,N,3], a colour per view whose gradient is written in place.  Returns the stacked
+    (color [V,3,H,W], radii [V,N] int32, depth [V,1,H,W], alpha [V,1,H,W]); every row and every gradient has the bits of the
+    per-view loop over `rasterize_gaussians` (dL/dshs: the sum of sr_sh_backward over the views, equal up to rounding)."""
+    settings_list = list(settings_list)
+    if not settings_list:
+        raise ValueError("rasterize_views needs at least one view")
+    shapes = [(int(rs.image_height), int(rs.image_width)) for rs in settings_list]
+    if any(s != shapes[0] for s in shapes):
+        raise ValueError(f"rasterize_views: the views of one call share one image size, got (H, W) = {shapes}: group the cameras by shape")
+    if any(int(rs.sh_degree) != int(settings_list[0].sh_degree) for rs in settings_list):
+        raise ValueError("rasterize_views: the views of one call share the active SH degree")
+    return _RasterizeViews.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
+                                 torch.is_grad_enabled())
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
