@@ -63,6 +63,10 @@
  *        <- reference scene/dataset_readers.py:1476-1491 (`_gen_3dpoints`, called per camera and frame at :1376 and :1463) and
  *           what `readNeuSceneInfo` takes from the concatenated cloud: its bounds (:1603-1613, the hull's box) or `num_pts`
  *           random rows (:1653-1658, the `depth` initialisation): one streaming pass, an ordered compaction or a sample by rank.
+ *   sr_draw_rows / sr_draw_rows_ascending, sr_rows_gather / sr_rows_scatter, sr_densification_stats_rows
+ *        <- the `--n_splats` subset step: reference train.py:56-60 (`torch.randperm(N)[:n_splats]` on the host and the indexing of
+ *           xyz, scaling and features), :68 (`idx` in gaussian_dict), :281-286 and scene/gaussian_model.py:431-438 (the `_idx`
+ *           branch of the densification bookkeeping) -- and the `torch.randperm(M)[:n_pts]` of the two initialisations.
  *   SrView
  *        <- the 12-field `GaussianRasterizationSettings` built at reference
  *           gaussian_renderer/__init__.py:59-72 (and :76-89 for the alpha pass).
@@ -1033,6 +1037,81 @@ int sr_depth_points_gather(int B, int H, int W, const SrDepthCamera* cameras, co
 int sr_depth_points_select(int B, int H, int W, const SrDepthCamera* cameras, const void* depths, int depth_is_double,
                            const void* images, int color_bytes, const void* workspace, const long long* ranks, long long n_ranks,
                            float* points_out, void* colors_out, long long* indices_out, int* flag_out, void* hip_stream);
+
+/* Subset steps (reference train.py:56-60, :68, :281-286, scene/gaussian_model.py:431-438: `--n_splats`): draw n_pick of n_rows
+ * rows on the device, gather the step's tensors through them, scatter gradients and the densification bookkeeping back.
+ *
+ * The draw.  idx_out[j] = P(j), j < n_pick, where P is a keyed bijection of [0, n_rows): n_pick distinct rows, a uniform subset in
+ * random order, without a permutation of n_rows in memory.  With b = the smallest number of bits with 2^b >= n_rows, lo = b / 2
+ * (rounded down) and hi = b - lo, a value x < 2^b is split into L = its low lo bits and H = its high hi bits, and round r = 0 ..
+ * n_keys - 1 of an alternating Feistel network maps
+ *   r even:  L ^= mix(H, keys[r]) mod 2^lo          r odd:  H ^= mix(L, keys[r]) mod 2^hi
+ *   mix(v, k): h = (v + k_lo) * 0x9E3779B1;  h ^= h >> 15;  h = (h ^ k_hi) * 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ * in unsigned 32-bit arithmetic (k_lo / k_hi: the halves of the 64-bit key).  Every round is an involution of [0, 2^b), so the
+ * network F is a bijection of it for any keys, and 2^b < 2 n_rows.  P(j) = the first of F(j), F(F(j)), ... that is < n_rows (cycle
+ * walking): the walk from j < n_rows stays on j's cycle of F and meets a value < n_rows at j itself at the latest, and the first
+ * such values of different j differ -- P is a bijection of [0, n_rows) because F is one of [0, 2^b).  Each step lands below n_rows
+ * with probability > 1/2; a lane gives up after SR_DRAW_MAX_WALK steps, writes -1 and stores 1 to *flag (a correct F gets there
+ * with probability < 2^-256: the bound is there so that no lane can spin).  Integer arithmetic only; `keys` is HOST memory, passed
+ * to the kernel by value (the facade derives them from one 64-bit seed with splitmix64).
+ *
+ * sr_draw_rows: 1 launch, one lane per output, no workspace.
+ * sr_draw_rows_ascending: the same subset in ascending order (coalescing gathers, a result that does not depend on the draw
+ *   order): 3 launches and no fill.  Row i belongs to the subset iff P^-1(i) < n_pick, and P^-1 is the same walk with F^-1 (the
+ *   rounds in reverse order): one lane per ROW decides that with O(1) memory, the wavefront's members become one 64-bit word, and the
+ *   fixed-order scan and the ordered gather the hull and the depth op use write the members' numbers.  No flag byte per row, no
+ *   fill, no atomics.  `workspace`: sr_draw_rows_ascending_workspace_bytes(n_rows) bytes (one bit per row and one count per 256
+ *   rows), 8-byte aligned.  *flag also becomes 1 when the members counted differ from n_pick (impossible for a bijection).
+ *
+ * sr_rows_gather: 1 launch for up to SR_ROWS_MAX_JOBS tensors.  Job k writes, for every j < n_pick and every column c of its row,
+ *   dst[j dst_row_stride + dst_col_offset + c] = op(src[idx[j] row_floats + c]):  SR_ROWS_COPY the value, SR_ROWS_EXP its expf
+ *   (`scaling_activation`), SR_ROWS_EXP_TO3 (row_floats must be 1) expf of the one source float into three columns
+ *   (`use_isotropic`, scene/gaussian_model.py:66-67).  Stride and offset count floats: `_features_dc` [N,1,3] at offset 0 and
+ *   `_features_rest` [N,15,3] at offset 3 of stride 48 give `get_features` (:79-82) without the cat.  A job with row_floats = 0 is
+ *   skipped.  An idx[j] outside [0, n_rows) reads nothing, writes NaN to the row of every job and stores 1 to *flag.
+ * sr_rows_scatter: its backward, 1 launch, the same job table (job.src is not read; job.dst is the forward's output, read by the
+ *   two EXP ops as the saved value of expf).  dL_ddst[k] has job k's dst layout, dL_dsrc[k] its src layout [n_rows, row_floats]
+ *   (NULL: job k has no gradient to write).  dL_dsrc[k][idx[j], c] = dL_ddst[k][j, c] (times dst[j, c] for SR_ROWS_EXP;
+ *   SR_ROWS_EXP_TO3: the three columns of dL_ddst added in column order, times dst[j, 0]).  Rows that were not drawn are not
+ *   written: zero dL_dsrc first.  PRECONDITION: the idx are distinct (what the draw gives) -- every element then has one writer,
+ *   there are no atomics and repeated calls give the same bytes; with a repeated index one of its writers wins.  An idx[j] outside
+ *   [0, n_rows) writes nothing and stores 1 to *flag.
+ * sr_densification_stats_rows: sr_densification_stats with i -> idx[i] on the three full-size outputs, 1 launch: for i < n_pick
+ *   with radii[i] > 0,  grad_accum[idx[i]] += |dL_dmeans2D[i, :2]|;  denom[idx[i]] += 1;  max_radii2D[idx[i]] = max(.., radii[i]);
+ *   every other row keeps its bits.  (Reference train.py:284-286 builds the drawn rows of max_radii2D with torch.empty_like, so a
+ *   drawn row that is not visible receives uninitialised memory there; here it is unchanged, as in the `_idx is None` branch.)
+ *   Same precondition: distinct idx.  An idx[i] outside [0, n_rows) updates nothing and stores 1 to *flag.
+ *
+ * `flag` (device int32, may be NULL) is only ever set, never cleared: zero it before the call.  Rows are addressed with 64-bit
+ * offsets.  Nothing waits for the device; every launch goes to hip_stream.  Refused on the host, before any launch: n_rows outside
+ * 0 .. 2^31 - 1, n_pick outside 0 .. n_rows (the two draws) or 0 .. 2^31 - 1, n_keys outside 1 .. SR_DRAW_MAX_KEYS, n_jobs outside
+ * 0 .. SR_ROWS_MAX_JOBS, an unknown op, a negative row_floats, SR_ROWS_EXP_TO3 with another row_floats than 1, a row that does not
+ * fit into dst_row_stride, a null pointer where one is read or written, and a misaligned one.  n_pick = 0 launches nothing. */
+#define SR_DRAW_MAX_KEYS 16
+#define SR_DRAW_MAX_WALK 256
+#define SR_ROWS_MAX_JOBS 8
+#define SR_ROWS_COPY 0
+#define SR_ROWS_EXP 1
+#define SR_ROWS_EXP_TO3 2
+typedef struct SrRowsJob {
+    const float* src;          /* [n_rows, row_floats] */
+    float* dst;                /* [n_pick, dst_row_stride], written from column dst_col_offset on */
+    int row_floats;            /* floats of a source row; 0: the job is skipped */
+    int dst_row_stride;        /* floats between two rows of dst */
+    int dst_col_offset;        /* first column of dst this job writes */
+    int op;                    /* SR_ROWS_* */
+} SrRowsJob;
+int sr_draw_rows(long long n_rows, long long n_pick, const unsigned long long* keys, int n_keys, long long* idx_out,
+                 int* flag_or_null, void* hip_stream);
+size_t sr_draw_rows_ascending_workspace_bytes(long long n_rows);
+int sr_draw_rows_ascending(long long n_rows, long long n_pick, const unsigned long long* keys, int n_keys, void* workspace,
+                           long long* idx_out, int* flag_or_null, void* hip_stream);
+int sr_rows_gather(int n_jobs, const SrRowsJob* jobs, long long n_pick, const long long* idx, long long n_rows, int* flag_or_null,
+                   void* hip_stream);
+int sr_rows_scatter(int n_jobs, const SrRowsJob* jobs, const float* const* dL_ddst, float* const* dL_dsrc, long long n_pick,
+                    const long long* idx, long long n_rows, int* flag_or_null, void* hip_stream);
+int sr_densification_stats_rows(long long n_pick, const long long* idx, long long n_rows, const float* dL_dmeans2D, const int* radii,
+                                float* grad_accum, float* denom, float* max_radii2D, int* flag_or_null, void* hip_stream);
 
 /* The flow head of the deform network (reference utils/time_utils.py:194-304 `FlowHead`, the last stage of a dynamic step; replaces
  * two to four nn.Linear calls, ~25 small per-point kernels and their autograd backward): per point n, with the row h = hidden[n]

@@ -12,4 +12,6 @@ from .flow_head import flow_head_path, fused_flow_head, set_flow_head  # noqa: F
 from .view_color import fused_view_color, set_view_color, view_color_path  # noqa: F401
 from .init import (depth_point_cloud, depth_points, depth_points_bounds, gen_3dpoints, hull_filter, hull_matrices,  # noqa: F401
                    splats_from_points, visual_hull, visual_hull_samples, visual_hull_samples_list)
+from .subset import draw_rows, gather_rows, get_gaussian_dict  # noqa: F401
+from .densify_stats import densification_stats  # noqa: F401
 from .plane_generator import Tensorial2D, TimeVAEDecoder, VarTriPlaneEncoder, fused_attention, fused_layer, generate_planes, set_attention  # noqa: F401

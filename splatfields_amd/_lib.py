@@ -114,6 +114,11 @@ class SrDepthCamera(C.Structure):
     _fields_ = [("kinv", C.c_double * 9), ("pose", C.c_double * 12)]
 
 
+class SrRowsJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_floats", C.c_int), ("dst_row_stride", C.c_int),
+                ("dst_col_offset", C.c_int), ("op", C.c_int)]
+
+
 class SrFlowBranch(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("rows", C.c_int)]
 
@@ -123,6 +128,8 @@ FLOW_OFFSET, FLOW_SE3, FLOW_SE3_AFFINE, FLOW_SE3_SCALED, FLOW_AFFINE, FLOW_DCT =
 FLOW_MAX_BRANCHES, FLOW_MAX_WIDTH, FLOW_MAX_OUT, FLOW_MAX_BASIS = 4, 256, 32, 10
 VIEW_FROM_CAMERAS, VIEW_DIRS_GIVEN, VIEW_MAX_WIDTH, VIEW_MAX_VIEWS = 0, 1, 256, 16   # include/splatraster.h: SR_VIEW_*
 HULL_KRT, HULL_NDC, HULL_OUTSIDE_CARVE, HULL_OUTSIDE_KEEP, HULL_MAX_VIEWS = 0, 1, 0, 1, 1024   # include/splatraster.h: SR_HULL_*
+DRAW_MAX_KEYS, DRAW_MAX_WALK = 16, 256                       # include/splatraster.h: SR_DRAW_*
+ROWS_MAX_JOBS, ROWS_COPY, ROWS_EXP, ROWS_EXP_TO3 = 8, 0, 1, 2   # include/splatraster.h: SR_ROWS_*
 RESFIELD_MAX_JOBS, RESFIELD_MAX_RANK = 16, 64
 PLANE_MAX_JOBS = 8                                           # include/splatraster.h: SR_PLANE_MAX_JOBS
 CONV_PROLOGUE, CONV_UPSAMPLE, CONV_RESIDUAL, CONV_SILU_OUT = 1, 2, 4, 8   # include/splatraster.h: SR_CONV_*
@@ -235,6 +242,16 @@ SYMBOLS = {
                                          C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_depth_points_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(SrDepthCamera), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # `keys` is HOST memory: an array of c_ulonglong
+    "sr_draw_rows": (C.c_int, [C.c_longlong, C.c_longlong, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sr_draw_rows_ascending_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "sr_draw_rows_ascending": (C.c_int, [C.c_longlong, C.c_longlong, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "sr_rows_gather": (C.c_int, [C.c_int, C.POINTER(SrRowsJob), C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "sr_rows_scatter": (C.c_int, [C.c_int, C.POINTER(SrRowsJob), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_longlong, C.c_void_p,
+                                  C.c_longlong, C.c_void_p, C.c_void_p]),
+    "sr_densification_stats_rows": (C.c_int, [C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_mlp_pack": (C.c_int, [C.c_int, C.POINTER(SrMlpPackJob), C.c_void_p]),
     "sr_mlp_weight_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob)]),
     "sr_mlp_weight_grad": (C.c_int, [C.c_int, C.c_int, C.POINTER(SrMlpGradJob), C.c_void_p, C.c_size_t, C.c_void_p]),

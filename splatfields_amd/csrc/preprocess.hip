@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "expand.h"
 #include "sh_stage.h"
+#include "densify_stats.h"
 
 namespace sr {
 
@@ -423,9 +424,7 @@ __global__ void k_densification_stats(int N, const float* __restrict__ dL_dmeans
     const int r = radii[idx];
     if (r <= 0) return;  // visibility_filter = radii > 0
     const float gx = dL_dmeans2D[3 * (size_t)idx], gy = dL_dmeans2D[3 * (size_t)idx + 1];
-    if (grad_accum) grad_accum[idx] += sqrtf(gx * gx + gy * gy);
-    if (denom) denom[idx] += 1.0f;
-    if (max_radii2D) max_radii2D[idx] = fmaxf(max_radii2D[idx], (float)r);
+    densification_stats_row((size_t)idx, r, gx, gy, grad_accum, denom, max_radii2D);
 }
 
 void launch_densification_stats(int N, const float* dL_dmeans2D, const int* radii, float* grad_accum, float* denom, float* max_radii2D,

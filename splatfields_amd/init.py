@@ -123,7 +123,7 @@ def _axis_tables(aabb, G: int) -> np.ndarray:
 
 def visual_hull(masks, matrices, *, convention: str = "krt", outside: str = "carve", grid_resolution: int = 256, aabb=(-1., 1.),
                 n_pts: Optional[int] = None, generator: Optional[torch.Generator] = None, return_indices: bool = False,
-                capacity: Optional[int] = None, device=None):
+                capacity: Optional[int] = None, draw: str = "permutation", device=None):
     """The voxels of a ``grid_resolution``^3 grid over ``aabb`` that every view keeps: float32 [M,3] on the device, in grid order
     (linear index (iy G + ix) G + iz at (g[ix], g[iy], g[iz]): the order of ``np.meshgrid(g, g, g)`` flattened, g =
     ``np.linspace(*aabb, G)`` made on the host in float64 and uploaded).
@@ -136,13 +136,16 @@ def visual_hull(masks, matrices, *, convention: str = "krt", outside: str = "car
 
     n_pts: keep ``torch.randperm(M, generator=generator)[:n_pts]`` of the rows, drawn on the device -- a uniform subset without
     replacement, as the reference's ``np.random.shuffle(...)[:n_pts]`` and ``np.random.choice(..., replace=False)`` are; numpy's
-    random streams themselves cannot be reproduced.  return_indices: also return the int32 linear indices of the rows."""
+    random streams themselves cannot be reproduced.  draw="keyed": the rows are picked by `splatfields_amd.subset.draw_rows(M,
+    n_pts, generator=generator)` instead (a CPU generator or None; draw order): a uniform subset as well, at a cost and a memory
+    that scale with n_pts, not with M.  return_indices: also return the int32 linear indices of the rows."""
     dev = _device_of(masks, matrices, device=device)
     if dev.type != "cuda":
         raise RuntimeError("splatfields_amd.init has no CPU path: the device must be a HIP ('cuda') device")
     G = int(grid_resolution)
     if G < 1 or G ** 3 > 2 ** 31 - 1:
         raise ValueError("grid_resolution must be at least 1 with grid_resolution^3 <= 2^31 - 1")
+    _check_draw(draw)
     with torch.cuda.device(dev):
         table, flat = _view_table(masks, matrices, convention, outside, dev)
         grid = torch.from_numpy(_axis_tables(aabb, G)).to(dev).contiguous()
@@ -151,10 +154,23 @@ def visual_hull(masks, matrices, *, convention: str = "krt", outside: str = "car
         rows = m if capacity is None else min(m, int(capacity))
         idx, xyz = _gather(grid, G, None, G ** 3, ws, rows, dev)
         if n_pts is not None and rows > n_pts:
-            gen_dev = dev if generator is None else generator.device
-            pick = torch.randperm(rows, generator=generator, device=gen_dev)[:n_pts].to(dev)
+            pick = _pick_rows(rows, n_pts, generator, draw, dev).to(dev)
             idx, xyz = idx[pick], xyz[pick]
     return (xyz, idx) if return_indices else xyz
+
+
+def _check_draw(draw: str) -> None:
+    if draw not in ("permutation", "keyed"):
+        raise ValueError(f"draw must be 'permutation' or 'keyed', not {draw!r}")
+
+
+def _pick_rows(rows: int, n_pts: int, generator, draw: str, dev) -> torch.Tensor:
+    """n_pts of `rows` row numbers: the head of a permutation of all of them, or the keyed draw of subset.draw_rows"""
+    if draw == "keyed":
+        from .subset import draw_rows
+        return draw_rows(rows, n_pts, generator=generator, device=dev)
+    gen_dev = dev if generator is None else generator.device
+    return torch.randperm(rows, generator=generator, device=gen_dev)[:n_pts]
 
 
 def hull_filter(points, masks, matrices, *, convention: str = "krt", outside: str = "carve", device=None) -> torch.Tensor:
@@ -318,7 +334,7 @@ def _depth_device(device, *things):
 
 def depth_points(depths, intrinsics_inv, poses, *, images=None, masks=None, n_pts: Optional[int] = None,
                  generator: Optional[torch.Generator] = None, ranks=None, capacity: Optional[int] = None, return_indices: bool = False,
-                 return_flag: bool = False, device=None):
+                 return_flag: bool = False, draw: str = "permutation", device=None):
     """The back-projected pixels of a batch of depth maps: ``(xyz float32 [M,3], colors [M,3] or None[, indices int64 [M]])`` on the
     device, in pixel order (image after image, row-major inside an image); ``indices`` are the flat pixel indices b H W + y W + x.
 
@@ -329,7 +345,8 @@ def depth_points(depths, intrinsics_inv, poses, *, images=None, masks=None, n_pt
 
     A full gather needs one host read, of the count.  ``capacity`` bounds the rows written: an ordered prefix when it is short.
     n_pts: keep ``torch.randperm(M, generator=generator)[:n_pts]`` of the rows (the convention of `visual_hull`), picked by rank
-    on the device without materialising the cloud.  ranks: the caller's own draw instead, an int64 sequence of any order, repeats
+    on the device without materialising the cloud; draw="keyed": the ranks come from `splatfields_amd.subset.draw_rows(M, n_pts,
+    generator=generator)` instead of the permutation of M (a CPU generator or None), through the same selection.  ranks: the caller's own draw instead, an int64 sequence of any order, repeats
     allowed: row j is survivor number ranks[j], and nothing is read back; a rank outside [0, M) gives a row of NaN coordinates,
     zero colours and the index -1.  return_flag (with ranks only): the select kernel's report is appended to the result, an int32
     [1] device tensor that is 1 when any rank was outside [0, M) and 0 otherwise -- still no host read."""
@@ -338,6 +355,7 @@ def depth_points(depths, intrinsics_inv, poses, *, images=None, masks=None, n_pt
         raise ValueError("ranks excludes n_pts and capacity")
     if return_flag and ranks is None:
         raise ValueError("return_flag needs ranks: only the caller's own ranks can be out of range")
+    _check_draw(draw)
     flag = None
     with torch.cuda.device(dev):
         b = _DepthBatch(depths, intrinsics_inv, poses, images, masks, dev)
@@ -355,9 +373,7 @@ def depth_points(depths, intrinsics_inv, poses, *, images=None, masks=None, n_pt
             m = int(count.item())                                  # the one host read
             rows = m if capacity is None else min(m, int(capacity))
             if n_pts is not None and rows > n_pts:
-                gen_dev = dev if generator is None else generator.device
-                pick = torch.randperm(rows, generator=generator, device=gen_dev)[:n_pts]
-                out = b.select(ws, pick, return_indices)[:3]
+                out = b.select(ws, _pick_rows(rows, n_pts, generator, draw, dev), return_indices)[:3]
             else:
                 out = b.gather(ws, rows, return_indices)
     out = tuple(out) if return_indices else tuple(out[:2])
