@@ -41,6 +41,10 @@
  *           host) and utils/image_utils.py:19-21 (`psnr`, train.py:387-396), with the 8-bit quantisation of the image files
  *           in between (torchvision `save_image`, render.py:282 `to8b`): a batch of views in one kernel plus a fixed-order
  *           reduction.
+ *   sr_lpips_pack_weights + sr_lpips_forward
+ *        <- reference render.py:174-180 (`eval_lpips`) as `eval_all` (render.py:163-207) calls it: [EXT] the `lpips` package's
+ *           VGG-16 trunk, five taps and distance, with weights the caller supplies, for a batch of views: 13 convolution
+ *           launches, 5 head launches and a fixed-order reduction.
  *   sr_splat_reg_forward / sr_splat_reg_backward, sr_depth_l1_forward / sr_depth_l1_backward
  *        <- reference train.py:195-201 (`lambda_norm`, `lambda_norm_mean`), :244-246 (`lambda_opacity`) and :224-229
  *           (`lambda_depthl1`): the tail of the objective between `render()` and `loss.backward()`, each a streaming pass and a
@@ -378,6 +382,37 @@ size_t sr_metrics_workspace_bytes(int batch, int height, int width);
 int sr_image_metrics(int batch, int height, int width, const float* pred, const long long* pred_strides4, const float* gt,
                      const long long* gt_strides4, const float* mask, long long mask_item_stride, int quantize, void* workspace,
                      float* psnr, float* ssim, float* psnr_channels, unsigned char* frames, void* hip_stream);
+
+/* LPIPS (VGG) of a batch of image pairs, forward only, float32 throughout (exact f32-input MFMA): the published `lpips` package
+ * v0.1, net='vgg', spatial=False, eval mode, restated from its published behaviour, with weights the caller supplies:
+ *   x' = ((2 q(x) - 1) - shift_c) / scale_c, q the quantisation `quantize` (SR_QUANT_*) as in sr_image_metrics;
+ *   13 convolutions 3x3, padding 1, bias, ReLU, of widths 64,64 | 128,128 | 256,256,256 | 512,512,512 | 512,512,512, a 2x2 /
+ *   stride-2 max-pool (floor) between the groups;  taps = the output of the last convolution of each group;
+ *   tap_l = mean over the tap's pixels of sum_c lin_l[c] (f0 / (sqrt(sum_c f0^2) + 1e-10) - f1 / (sqrt(sum_c f1^2) + 1e-10))^2;
+ *   out[b] = sum of the five taps of pair b.
+ * sr_lpips_pack_weights: `conv_weights` / `conv_biases` are HOST arrays of SR_LPIPS_CONVS device pointers ([cout,cin,3,3] and
+ *   [cout], contiguous float32), `lins` a host array of SR_LPIPS_TAPS device pointers ([64], [128], [256], [512], [512]),
+ *   `shift`, `scale` device [3].  Writes the kernels' layout into `packed`: sr_lpips_packed_bytes() bytes of device memory,
+ *   256-byte aligned.  Once per set of weights, not per call.
+ * sr_lpips_forward: pred, gt as for sr_image_metrics (element strides {item, channel, row, pixel}), in [0,1].  Limits:
+ *   16 <= height, width <= 32768 (below 16 relu5_3 has no pixel), and 2 batch ceil(height / 8) ceil(width / 16) as well as
+ *   batch ceil(height width / 64) at most 2^31 - 1; anything else is refused before any launch.  `workspace`:
+ *   sr_lpips_workspace_bytes(batch, height, width) bytes (0 for a shape out of range), 256-byte aligned: two activation
+ *   buffers of 2 batch height width 64 floats, the pooled buffer, the per-workgroup partial sums in double.  Written, all to
+ *   device memory: out [batch]; out_taps (may be NULL) [batch, 5]; maps (may be NULL) sr_lpips_maps_floats(batch, height,
+ *   width) floats: the five per-pixel maps [batch, height >> l, width >> l], l = 0..4, one after another.
+ * 19 launches per call on `hip_stream`, no atomics, nothing waits: results are bit-identical from call to call, and an item's
+ * value does not depend on the other items of the batch. */
+#define SR_LPIPS_CONVS 13
+#define SR_LPIPS_TAPS 5
+size_t sr_lpips_packed_bytes(void);
+int sr_lpips_pack_weights(const float* const* conv_weights, const float* const* conv_biases, const float* const* lins,
+                          const float* shift, const float* scale, void* packed, void* hip_stream);
+size_t sr_lpips_workspace_bytes(int batch, int height, int width);
+size_t sr_lpips_maps_floats(int batch, int height, int width);
+int sr_lpips_forward(int batch, int height, int width, const float* pred, const long long* pred_strides4, const float* gt,
+                     const long long* gt_strides4, int quantize, const void* packed, void* workspace, float* out, float* out_taps,
+                     float* maps, void* hip_stream);
 
 /* SH colour evaluation as a stand-alone stage (the SH part of the forward preprocess; reference utils/sh_utils.py:57-112,
  * extract_geo.py:40-44): colors[N,3] = max(sum_k basis_k(dir) shs[k] + 0.5, 0), clamped[N] bit c set where channel c was

@@ -3,7 +3,7 @@ from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, raste
 from .render import render, render_views  # noqa: F401
 from .losses import (centered_position_norm, depth_l1_loss, l1_loss, opacity_regularizer, photometric_loss, position_norm,  # noqa: F401
                      splat_regularizers, ssim, training_objective)
-from .metrics import compute_psnr, compute_ssim, image_metrics, psnr  # noqa: F401
+from .metrics import LPIPSWeights, compute_psnr, compute_ssim, eval_lpips, image_metrics, lpips_vgg, psnr  # noqa: F401
 from .moran import knn_graph, moran_loss, morans_loss, morans_measure, query_nn  # noqa: F401
 from .optim import SplatAdam  # noqa: F401
 from .network_optim import NetworkAdam, network_optimizer, set_network_optimizer  # noqa: F401

@@ -140,6 +140,7 @@ ADAM_MAX_TENSORS = 32                                        # include/splatrast
 SUM_MAX_JOBS, SUM_MAX_VIEWS = 16, 16                          # include/splatraster.h: SR_SUM_MAX_JOBS, SR_SUM_MAX_VIEWS
 NET_ADAM_MAX_GRADS = 480                                     # include/splatraster.h: SR_NET_ADAM_MAX_GRADS
 QUANT_NONE, QUANT_PNG, QUANT_TO8B = 0, 1, 2                     # include/splatraster.h: SR_QUANT_*
+LPIPS_CONVS, LPIPS_TAPS = 13, 5                                # include/splatraster.h: SR_LPIPS_*
 MLP_MAX_OPS, MLP_NONE, MLP_LEAKY, MLP_MASK = 24, 0, 1, 2      # include/splatraster.h: SR_MLP_*
 MLP_GROUP_MAX_NETS, MLP_GROUP_MAX_OPS, MLP_GROUP_MAX_HEADS = 8, 40, 8      # include/splatraster.h: SR_MLP_GROUP_*
 MLP_OUT_NONE, MLP_OUT_SIGMOID, MLP_OUT_NORMALIZE = 0, 1, 2                 # include/splatraster.h: SR_MLP_OUT_*
@@ -213,6 +214,14 @@ SYMBOLS = {
     "sr_image_metrics": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.POINTER(C.c_longlong),
                                    C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "sr_lpips_packed_bytes": (C.c_size_t, []),
+    # the three pointer tables are HOST arrays of device pointers
+    "sr_lpips_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "sr_lpips_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sr_lpips_maps_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sr_lpips_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.POINTER(C.c_longlong),
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sr_adam_step": (C.c_int, [C.c_int, C.POINTER(SrAdamJob), C.c_void_p, C.c_longlong, C.c_void_p]),
     "sr_net_adam_plan": (C.c_int, [C.POINTER(SrNetAdamSlot), C.c_int]),
     "sr_net_adam_step": (C.c_int, [C.POINTER(SrNetAdamSlot), C.POINTER(SrNetAdamSlot), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),

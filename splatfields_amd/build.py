@@ -12,8 +12,8 @@ LIB_PATH = PKG_DIR / "libsplatraster.so"
 # same ABI with the work counters of the backward blend compiled in (-DSR_BWD_STATS): measurement aid of bench.py
 # (pairs_evaluated / pairs_blended), never the timed path
 STATS_LIB_PATH = PKG_DIR / "libsplatraster_stats.so"
-SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "blend_bwd.hip", "knn.hip", "sh.hip", "densify.hip", "mlp.hip", "triplane.hip", "loss.hip", "moran.hip", "adam.hip", "network_adam.hip", "metrics.hip", "objective.hip", "planegen.hip", "attention.hip", "hull.hip", "depth_init.hip", "flow_head.hip", "view_color.hip", "view_sum.hip", "subset.hip"]
-HEADERS = ["common.h", "kernels.h", "host_api.h", "expand.h", "sh_stage.h", "quadmask.h", "reduce.h", "window11.h", "point_tile.h", "mlp_bf16x3.h", "sort_tile.h", "adam_math.h", "ordered_scan.h", "densify_stats.h", "../../include/splatraster.h"]
+SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "blend_bwd.hip", "knn.hip", "sh.hip", "densify.hip", "mlp.hip", "triplane.hip", "loss.hip", "moran.hip", "adam.hip", "network_adam.hip", "metrics.hip", "lpips.hip", "objective.hip", "planegen.hip", "attention.hip", "hull.hip", "depth_init.hip", "flow_head.hip", "view_color.hip", "view_sum.hip", "subset.hip"]
+HEADERS = ["common.h", "kernels.h", "host_api.h", "expand.h", "sh_stage.h", "quadmask.h", "reduce.h", "quantise.h", "window11.h", "point_tile.h", "mlp_bf16x3.h", "sort_tile.h", "adam_math.h", "ordered_scan.h", "densify_stats.h", "../../include/splatraster.h"]
 
 
 def _hipcc() -> str:

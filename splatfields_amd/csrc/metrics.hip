@@ -24,6 +24,7 @@
 //
 // No floating-point atomics and no host wait: results are bit-identical from call to call.
 #include "host_api.h"
+#include "quantise.h"
 #include "reduce.h"
 #include "window11.h"
 
@@ -47,23 +48,6 @@ struct MetricDims {
     long long mask_item;         // element stride between the masks of two items (0: one mask for all)
     int vec;                     // pixel stride 1 and everything 16-byte aligned: the region is loaded as float4
 };
-
-template <int kQuant>
-__device__ __forceinline__ float quantise(float x, float& level) {
-    if (kQuant == SR_QUANT_PNG) {
-        float t = __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
-        t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);
-        level = truncf(t);
-        return __fdiv_rn(level, 255.0f);
-    }
-    if (kQuant == SR_QUANT_TO8B) {
-        const float c = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);
-        level = truncf(__fmul_rn(255.0f, c));
-        return __fdiv_rn(level, 255.0f);
-    }
-    level = 0.0f;
-    return x;
-}
 
 // the partial convolution's normalisation: n of the 11 window pixels are inside the mask
 __device__ __forceinline__ float met_normalise(float r, int n) { return n != 0 ? __fdiv_rn(r * 11.0f, (float)n) : 0.0f; }

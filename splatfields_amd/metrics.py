@@ -51,7 +51,7 @@ def _strides4(t: torch.Tensor, layout: str):
 
 
 def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, *, layout: str = "chw",
-                  quantize: Optional[str] = None, return_frames: bool = False) -> dict:
+                  quantize: Optional[str] = None, return_frames: bool = False, lpips=None) -> dict:
     """PSNR and the reference's SSIM of one image or a batch, on the device.
 
     pred, gt   [3,H,W] / [B,3,H,W] with ``layout="chw"`` (what ``render()`` returns), [H,W,3] / [B,H,W,3] with ``"hwc"``;
@@ -60,6 +60,8 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
                batch) or of every image ([B,H,W], [B,H,W,1], [B,1,H,W]); read as ``mask != 0``.  It selects the reference's
                partial convolution for the SSIM; the PSNR is never masked.
     quantize   None, ``"png"`` or ``"to8b"``: both images go through the 8-bit round trip first.
+    lpips      None, or an ``LPIPSWeights``: adds ``"lpips"`` [B], ``lpips_vgg`` of the same (quantised) images, as ``eval_all``
+               evaluates all three metrics on the image files.  Without it the call and its outputs are unchanged.
     -> ``{"psnr": [B], "ssim": [B], "psnr_channels": [B,3]}`` float32 device tensors (0-dim / [3] for one image), and with
     ``return_frames`` also ``"frames"``: the quantised prediction, uint8 [B,H,W,3] ([H,W,3])."""
     _check_pair("image_metrics", pred, gt)
@@ -112,6 +114,8 @@ def image_metrics(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
         res["frames"] = frames
     if single:
         res = {k: v[0] for k, v in res.items()}
+    if lpips is not None:
+        res["lpips"] = lpips_vgg(pred, gt, lpips, layout=layout, quantize=quantize)
     return res
 
 
@@ -144,3 +148,6 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     if img1.dim() != 3 or img1.shape[0] != 3:
         raise RuntimeError(f"psnr: expected [3,H,W] images, got {tuple(img1.shape)}")
     return image_metrics(img1, img2)["psnr_channels"].reshape(3, 1).to(img1.dtype)
+
+
+from .lpips import LPIPSWeights, eval_lpips, lpips_vgg  # noqa: E402,F401  (lpips.py builds on the helpers above)
